@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the sink hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload ns|config3|config4|config5|ns_time]
+    python bench.py --gpus N --steps K --warmup W [--workload ns|config3|config4|config5|ns_time] [--full] [--dump-outputs DIR]
 
 Default workload (the pipeline the metric and north_star name, at config 3's size):
     Mix(Signal(sin, ω=1kHz), Signal(noise[26 460 000 x 8], 44.1 kHz)) |> Until(600 s)
@@ -20,16 +20,27 @@ to-device gather).  `config4`: the 64 scenes of an Append are
 sharded over the ranks and the result slabs are all-gathered device to device.  `config5`: each
 rank owns a 128-channel slab of the 1024-channel signal; no exchange step.
 
-One JSON line is printed by rank 0 (driver contract) with these extra objects:
+One JSON line is printed by rank 0 (driver contract) with these extra objects, all taken from the timed loop itself:
   roofline        the dominant stage of the headline workload against the HBM roofline: its
                   algorithmic bytes / its hipEvent time inside the library, on the stream it runs on
   roofline_sink   the whole sink from the TIMED LOOP: algorithmic bytes of the sink / ms_per_step
   stages          every stage of the plan (hipEvent ms, launches, algorithmic bytes)
+
+A plain run does nothing else: set-up, --warmup executes, --steps timed executes, the outputs (--dump-outputs DIR)
+and the line.  `--full` adds what takes runs or checks of its own (null in a plain run's line):
+  config3         BASELINE config 3 in the same process, its own timed loop (default workload, one rank)
+  config4         N > 1 over RCCL: the sharded Append with its device-to-device gather
+  one_shot        the headline sink once in fresh child processes (plan create + first execute)
   parity_gate     engine vs CPU oracle on a prefix of the same input: checked after the timed loops and
                   before anything is printed (a failure exits without a result line)
   parity_full     the timed plan's own result against the oracle on the same noise, whole length
   cpu_baseline    the CPU oracle (a port of the reference's block-pull engine) rebuilt here with
                   -O3 -march=native, timed on this host: 1 thread, and all channels in parallel
+
+--dump-outputs DIR: after the timed loop, the result of the last timed execute (what `sink` hands its caller, frames x
+channels, in the result dtype) as DIR/output.npy; a result above 48 MB is written as a fixed sample instead: its first and
+last frames (output_head.npy, output_tail.npy) and frames drawn with a fixed seed (output_sample.npy, their frame numbers
+in output_sample_frames.npy).  The input noise is seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -318,6 +329,41 @@ def roofline_of(stage, traffic=None, source=None):
             "launches": stage["launches"], "kernel_algorithmic_bytes": stage["algorithmic_bytes"]}
 
 
+DUMP_WHOLE_BYTES = 48 << 20   # --dump-outputs: a result up to this size is written whole, a larger one as a sample
+DUMP_EDGE_FRAMES = 65536      # frames of the sample's head and of its tail
+DUMP_SEED = 20241016
+
+
+def dump_outputs(d, out):
+    """`out`: the timed plan's result, [frames x channels] (a device tensor).  Writes it, or a fixed sample of it, under
+    `d` as .npy in its own dtype (float64 or float32); returns the names written.  The sample depends on nothing but the
+    result's shape, so two builds given the same arguments write the same frames."""
+    import numpy as np
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    n, nch = out.shape
+    row = nch * out.element_size()
+    files = {}
+    if n * row <= DUMP_WHOLE_BYTES:
+        files["output"] = out.cpu().numpy()
+    else:
+        # (head and tail: the filter's start-up and the resampler's last look-ahead; between them one frame drawn from
+        #  each of n_draw equal stretches)
+        n_edge = min(DUMP_EDGE_FRAMES, DUMP_WHOLE_BYTES // (4 * row))
+        m = n - 2 * n_edge
+        n_draw = min(m, (DUMP_WHOLE_BYTES - 2 * n_edge * row) // (row + 8))  # (+ 8: its frame number, float64)
+        lo = n_edge + np.arange(n_draw + 1, dtype=np.int64) * m // n_draw
+        idx = lo[:-1] + np.random.default_rng(DUMP_SEED).integers(0, lo[1:] - lo[:-1])
+        files["output_head"] = out[:n_edge].cpu().numpy()
+        files["output_tail"] = out[n - n_edge:].cpu().numpy()
+        files["output_sample"] = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+        files["output_sample_frames"] = idx.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(files)
+
+
 FP64_MFMA_PEAK_TFLOPS = 78.6  # AMD's FP64 matrix figure for MI355X (256 CUs x 4 SIMDs x 32 FMA / clock x 2.4 GHz); the guide under
                                # /opt/skills has no fp64 row.
 FP64_MFMA_MEASURED_TFLOPS = 68.9  # what back-to-back v_mfma_f64_16x16x4_f64 reach chip-wide, operands in registers (the clock drops to
@@ -469,9 +515,18 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=600.0,
                     help="signal seconds for the CPU-oracle sample (0 = skip); the full 600 s x 8 ch pipeline "
                          "is ~10-20 s of CPU work on one core")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 object")
-    ap.add_argument("--no-one-shot", action="store_true", help="skip the one-shot latency probe (three child processes)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 object (--full)")
+    ap.add_argument("--no-one-shot", action="store_true", help="skip the one-shot latency probe (three child processes; --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beyond the headline: config 3, config 4 at N > 1, the one-shot "
+                         "probe, the parity gate, parity_full and the CPU baseline (--cpu-seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (or a fixed sample of it) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload not in ("ns", "config3"):
+        ap.error("--dump-outputs: only the ns and config3 workloads")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
 
@@ -547,12 +602,13 @@ def main():
     # (all plans before the first timed loop: plan creation is host work -- the replay of DSP.jl's phase accumulator --
     #  during which the device idles and its power management falls back; the second workload then starts right behind
     #  the first loop instead of behind such a gap)
-    do_secondary = rank == 0 and world == 1 and args.workload == "ns" and not args.no_secondary
+    do_secondary = args.full and rank == 0 and world == 1 and args.workload == "ns" and not args.no_secondary
     if do_secondary:
         p3, o3_t, o3, n3, plan3_ms = prepare(tree_config3)
     series = []
     elapsed = timed_loop(plan, optr, stream, args.steps, args.warmup, torch, dist, dev, series=series, profile=True)
     host_side = series.pop() if series and isinstance(series[-1], dict) else None
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
     stages = stage_means(plan)  # per-kernel means over the timed executes themselves
     st = plan.stats()
     issue = dict(plan.counters(), profiling="deferred: per-kernel events recorded during the timed executes, never "
@@ -589,12 +645,12 @@ def main():
     checksum = float(out_t[:, :: max(1, n_out // 4096)].double().abs().sum().item())
     plan.close()
     gpu_result = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         gpu_result = np.asfortranarray(out_t.t().cpu().numpy())  # [n_out x nch], for the full-length comparison
     del out_t, out
 
     # ---- N > 1 over RCCL: the path that has an exchange step, next to the headline (every rank takes part) ----
-    if dist is not None and dist.get_backend() == "nccl" and args.workload == "ns":
+    if args.full and dist is not None and dist.get_backend() == "nccl" and args.workload == "ns":
         import bench_multi
 
         a4 = argparse.Namespace(**vars(args))
@@ -607,7 +663,7 @@ def main():
 
     # ---- correctness gate (rank 0, same device noise, a prefix); the whole length: parity_full below ----
     gate = None
-    if rank == 0:
+    if args.full and rank == 0:
         m = min(n_in, 150_000)
         pre = np.asfortranarray(noise_t[:, :m].t().cpu().numpy())
         gate = parity_gate(so, headline_fn, pre, 1e-6)
@@ -662,10 +718,12 @@ def main():
             "parity_gate": gate,
             "config3": secondary,
             "config4": config4,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
-        if world == 1 and args.workload == "ns" and not args.no_one_shot and not args.no_secondary:
+        if args.full and world == 1 and args.workload == "ns" and not args.no_one_shot and not args.no_secondary:
             res["one_shot"] = one_shot_probe()
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             noise_host = np.asfortranarray(noise_t.t().cpu().numpy())
             full, res["cpu_baseline"] = cpu_baseline(so, headline_fn, args.cpu_seconds, nch, ndt, noise_host, gpu_result)
             res["parity_full"] = full

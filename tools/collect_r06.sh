@@ -11,12 +11,12 @@ S=$R/gpurun_out/prof_summary
 rm -rf $OUT $S; mkdir -p $OUT $S
 cd $R
 python3 -c "import bench; print(bench.kernel_sources_sha16())" > $OUT/kernel_sources_sha16.txt
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python3 bench.py --cpu-seconds 0 > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python3 bench.py --full --cpu-seconds 0 > $OUT/trace.log 2>&1
 pmc() {  # tag, bench.py arguments
   local tag=$1; shift
-  timeout 900 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch_$tag -o bench --output-format csv -- python3 bench.py "$@" > $OUT/fetch_$tag.log 2>&1
-  timeout 900 rocprofv3 --pmc WRITE_SIZE -d $OUT/write_$tag -o bench --output-format csv -- python3 bench.py "$@" > $OUT/write_$tag.log 2>&1
-  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/stats_$tag -o bench --output-format csv -- python3 bench.py "$@" > $OUT/stats_$tag.log 2>&1
+  timeout 900 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch_$tag -o bench --output-format csv -- python3 bench.py --full "$@" > $OUT/fetch_$tag.log 2>&1
+  timeout 900 rocprofv3 --pmc WRITE_SIZE -d $OUT/write_$tag -o bench --output-format csv -- python3 bench.py --full "$@" > $OUT/write_$tag.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/stats_$tag -o bench --output-format csv -- python3 bench.py --full "$@" > $OUT/stats_$tag.log 2>&1
   f=$(find $OUT/stats_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cut -c1-400 "$f" | head -12 > $S/kernel_stats_$tag.csv
 }
 pmc ns --workload ns --no-secondary --steps 100 --warmup 10 --cpu-seconds 0 --no-one-shot
@@ -27,13 +27,13 @@ pmc ns_f32 --workload ns --dtype f32 --no-secondary --steps 100 --warmup 10 --cp
 pmc ns_2ch --workload ns --channels 2 --seconds 2400 --no-secondary --steps 100 --warmup 10 --cpu-seconds 0 --no-one-shot
 python3 tools/summarize_profiles.py $OUT $S
 grep "^{" $OUT/trace.log > $S/bench_default.json
-python3 bench.py --steps 20 --warmup 5 > $S/bench_20_5.json 2>/dev/null
-python3 bench.py --steps 200 --warmup 30 --no-one-shot > $S/bench_200_30.json 2>/dev/null
-SIGOPS_NO_RSOS=1 python3 bench.py --steps 200 --warmup 30 --cpu-seconds 0 --no-secondary --no-one-shot > $S/bench_200_30_two_kernels.json 2>/dev/null
-python3 bench.py --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot > $S/bench_ns_f32.json 2>/dev/null
-SIGOPS_RSOS_NO_F32MFMA=1 python3 bench.py --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot --no-secondary > $S/bench_ns_f32_f64products.json 2>/dev/null
-python3 bench.py --channels 2 --seconds 2400 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot --no-secondary > $S/bench_ns_2ch.json 2>/dev/null
-python3 bench.py --workload config3 --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot > $S/bench_config3_f32.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $S/bench_20_5.json 2>/dev/null
+python3 bench.py --full --steps 200 --warmup 30 --no-one-shot > $S/bench_200_30.json 2>/dev/null
+SIGOPS_NO_RSOS=1 python3 bench.py --full --steps 200 --warmup 30 --cpu-seconds 0 --no-secondary --no-one-shot > $S/bench_200_30_two_kernels.json 2>/dev/null
+python3 bench.py --full --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot > $S/bench_ns_f32.json 2>/dev/null
+SIGOPS_RSOS_NO_F32MFMA=1 python3 bench.py --full --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot --no-secondary > $S/bench_ns_f32_f64products.json 2>/dev/null
+python3 bench.py --full --channels 2 --seconds 2400 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot --no-secondary > $S/bench_ns_2ch.json 2>/dev/null
+python3 bench.py --full --workload config3 --dtype f32 --steps 200 --warmup 30 --cpu-seconds 0 --no-one-shot > $S/bench_config3_f32.json 2>/dev/null
 python3 bench.py --workload config4 --steps 100 --warmup 20 --no-one-shot > $S/bench_config4_1gpu.json 2>/dev/null
 python3 bench.py --workload config5 --steps 50 --warmup 10 --no-one-shot > $S/bench_config5_slab.json 2>/dev/null
 python3 bench_configs.py > $S/bench_configs.jsonl 2>/dev/null

@@ -21,7 +21,7 @@ STAGES = {"k_rsos": ["k_rsos", "k_sos_poison"], "k_resample_periodic": ["k_resam
           "k_sos": ["k_sos_tiled", "k_sos_scan", "k_sos_onepass", "k_sos_batch", "k_sos_"], "k_pointwise": ["k_pointwise"]}
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402  (kernel_sources_sha16: bench.py quotes these counters only while the kernel sources are the same)
-res = {"note": ("separate --pmc passes of `python3 bench.py --workload W --no-secondary --steps 100 --warmup 10 "
+res = {"note": ("separate --pmc passes of `python3 bench.py --full --workload W --no-secondary --steps 100 --warmup 10 "
                 "--cpu-seconds 0`.  Per /opt/skills/guides/MI355X_MICROARCH.md (HBM / rocprofv3 section): FETCH_SIZE and "
                 "WRITE_SIZE are in KB; FETCH_SIZE under-reports wide coalesced reads by exactly 2x on gfx950, WRITE_SIZE is "
                 "exact; corrected HBM traffic = 2*FETCH + WRITE.  Per execute = summed over the stage's kernels / number of "
