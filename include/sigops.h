@@ -91,10 +91,12 @@ typedef enum so_fn {
     SO_FN_IDENTITY = 2
 } so_fn_t;
 
-/* RAMP shaping functions (src/ramps.jl:4 `sinramp`, tests use `identity`) */
+/* RAMP shaping functions (src/ramps.jl:4 `sinramp`, tests use `identity`; any other
+ * function as an expression program, src/ramps.jl:60-72) */
 typedef enum so_rampfn {
     SO_RAMP_SINRAMP = 0, /* sinpi(0.5x) */
-    SO_RAMP_IDENTITY = 1
+    SO_RAMP_IDENTITY = 1,
+    SO_RAMP_EXPR = 2     /* fn(x) as an expression program (so_eop_t) of one argument, x */
 } so_rampfn_t;
 
 /* MAP functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184) */
@@ -108,8 +110,67 @@ typedef enum so_mapfn {
     SO_MAP_AS1CHANNEL = 6, /* ToChannels(x,1) = sum over channels                   */
     SO_MAP_ASNCHANNELS = 7,/* ToChannels(x,n) = replicate channel 1, i3 = n         */
     SO_MAP_TOELTYPE = 8,   /* ToEltype(x,T), i3 = so_dtype_t                        */
-    SO_MAP_REVERSECH = 9   /* OperateOn(reverse,x,bychannel=false) (runtests.jl:273) */
+    SO_MAP_REVERSECH = 9,  /* OperateOn(reverse,x,bychannel=false) (runtests.jl:273) */
+    SO_MAP_EXPR = 10       /* OperateOn(fn, xs...) with fn given as an expression program
+                              (so_eop_t, below; src/mapsignal.jl:131-145,249-272)    */
 } so_mapfn_t;
+
+/*
+ * Expression programs: an elementwise closure (`OperateOn(fn, xs...)`, `Signal(fn)`, a ramp
+ * shape) written out as a postfix program over its arguments, evaluated once per sample on
+ * the device.  Every value on the stack is a Float64; a Float32 closure rounds explicitly
+ * (SO_EOP_ROUND32 after every Float32 operation), booleans are 0.0 / 1.0.
+ *   SO_EOP_ARG k      push argument k (MAP: child k; RAMP: the ramp position, k = 0)
+ *   SO_EOP_CONST k    push constants[k] (the node's p1 table)
+ *   SO_EOP_UN f       x -> f(x), f one of so_un_t
+ *   SO_EOP_BIN f      a, b -> f(a, b), f one of so_bin_t; b is on top of the stack
+ *   SO_EOP_CMP f      a, b -> a f b, f one of so_cmp_t; 1.0 true, 0.0 false, and NaN compares
+ *                     false except under SO_CMP_NE
+ *   SO_EOP_SELECT     c, a, b -> c != 0 ? a : b, NumPy's `where`
+ *   SO_EOP_ROUND32    x -> (double)(float)x
+ * A program must leave exactly one value; the planner rejects stack underflow, argument
+ * indexes out of range and unknown codes with SO_ERR_INVALID.  Semantics follow NumPy's
+ * ufuncs: SO_BIN_MINIMUM / MAXIMUM propagate NaN, SO_BIN_FMIN / FMAX ignore it,
+ * SO_BIN_REMAINDER has the sign of the divisor (Python `%`), SO_UN_RINT rounds half to even.
+ */
+typedef struct so_eop {
+    int32_t code; /* so_eop_code_t        */
+    int32_t arg;  /* argument / constant index or function id */
+} so_eop_t;
+
+typedef enum so_eop_code {
+    SO_EOP_ARG = 0,
+    SO_EOP_CONST = 1,
+    SO_EOP_UN = 2,
+    SO_EOP_BIN = 3,
+    SO_EOP_CMP = 4,
+    SO_EOP_SELECT = 5,
+    SO_EOP_ROUND32 = 6
+} so_eop_code_t;
+
+typedef enum so_un {
+    SO_UN_NEG = 0, SO_UN_ABS = 1, SO_UN_SQRT = 2, SO_UN_CBRT = 3, SO_UN_SQUARE = 4,
+    SO_UN_RECIPROCAL = 5, SO_UN_EXP = 6, SO_UN_EXP2 = 7, SO_UN_EXPM1 = 8, SO_UN_LOG = 9,
+    SO_UN_LOG2 = 10, SO_UN_LOG10 = 11, SO_UN_LOG1P = 12, SO_UN_SIN = 13, SO_UN_COS = 14,
+    SO_UN_TAN = 15, SO_UN_ARCSIN = 16, SO_UN_ARCCOS = 17, SO_UN_ARCTAN = 18, SO_UN_SINH = 19,
+    SO_UN_COSH = 20, SO_UN_TANH = 21, SO_UN_ARCSINH = 22, SO_UN_ARCCOSH = 23,
+    SO_UN_ARCTANH = 24, SO_UN_FLOOR = 25, SO_UN_CEIL = 26, SO_UN_TRUNC = 27, SO_UN_RINT = 28,
+    SO_UN_SIGN = 29,
+    SO_UN_COUNT = 30
+} so_un_t;
+
+typedef enum so_bin {
+    SO_BIN_ADD = 0, SO_BIN_SUB = 1, SO_BIN_MUL = 2, SO_BIN_DIV = 3, SO_BIN_POW = 4,
+    SO_BIN_REMAINDER = 5, SO_BIN_FMOD = 6, SO_BIN_MINIMUM = 7, SO_BIN_MAXIMUM = 8,
+    SO_BIN_FMIN = 9, SO_BIN_FMAX = 10, SO_BIN_ARCTAN2 = 11, SO_BIN_HYPOT = 12,
+    SO_BIN_COPYSIGN = 13,
+    SO_BIN_COUNT = 14
+} so_bin_t;
+
+typedef enum so_cmp {
+    SO_CMP_LT = 0, SO_CMP_LE = 1, SO_CMP_GT = 2, SO_CMP_GE = 3, SO_CMP_EQ = 4, SO_CMP_NE = 5,
+    SO_CMP_COUNT = 6
+} so_cmp_t;
 
 /* PAD kinds (src/padding.jl:150-192) */
 typedef enum so_padkind {
@@ -153,8 +214,15 @@ typedef enum so_rskind {
  *  RAMP      i0=direction(0 :on, 1 :off)  i1=so_rampfn_t  l0=R=resolvelen
  *            (max(1,frames), src/ramps.jl:26); child 0 = the signal being ramped
  *            (gives length/nch/dtype); the node's VALUE is the gain
+ *            SO_RAMP_EXPR: p0=const so_eop_t* program of one argument (the ramp position),
+ *            i2=its length, p1=const double* constants; the gain is fn(x) inside the ramp
+ *            and 1 outside it (src/ramps.jl:56-59)
  *  MAP       i0=so_mapfn_t  i1=bychannel  i2=so_padkind_t of `padding`  d0=pad value
  *            i3=extra (see so_mapfn_t); children = x.signals (un-extended)
+ *            SO_MAP_EXPR: p0=const so_eop_t* program (ARG k = child k), i3=its length,
+ *            p1=const double* constants, i1=1 (bychannel; a bychannel=false closure is
+ *            written as one program per output channel over GETCHAN children, joined by
+ *            TUPLECAT); dtype = the closure's result type (Float32 / Float64)
  *  FILT_SOS  i0=nsections  p0=double[6*nsec] rows (b0,b1,b2,a0,a1,a2), a0==1
  *            d0=gain  i1=blocksize (reference `blocksize`; results are invariant)
  *  RESAMPLE  i0=so_rskind_t  i1=Nphi  l0=num l1=den (RATIONAL)  d0=rate (ARBITRARY)

@@ -4,7 +4,7 @@ from .units import s, ms, Hz, kHz, frames, kframes, dB, rad, deg, Quantity  # no
 from .signals import (  # noqa: F401
     ErrorException, inflen, isinf, nframes, nchannels, framerate, sampletype, duration, pipe,
     Signal, Until, After, Window, Pad, Extend, cycle, mirror, lastframe, zero, one,
-    Append, Prepend, Mix, Amplify, AddChannel, SelectChannel, OperateOn, Operate,
+    Append, Prepend, Mix, Amplify, AddChannel, SelectChannel, OperateOn, Operate, elementwise, Elementwise,
     RampOn, RampOff, Ramp, FadeTo, sinramp, identity, randn,
     Filt, Normpower, Lowpass, Highpass, Bandpass, Bandstop, Butterworth, Chebyshev1,
     ToFramerate, ToChannels, ToEltype, Format, Uniform,

@@ -12,9 +12,19 @@ SO_LEN_INF, SO_LEN_MISSING, SO_LEN_UNCHECKED = -1, -2, -3
 (NODE_ARRAY, NODE_CONST, NODE_FUNC, NODE_UNTIL, NODE_AFTER, NODE_PAD, NODE_APPEND, NODE_RAMP,
  NODE_MAP, NODE_FILT_SOS, NODE_RESAMPLE, NODE_NORMPOWER) = range(12)
 FN = {"sin": 0, "cos": 1, "identity": 2}
-RAMPFN = {"sinramp": 0, "identity": 1}
+RAMPFN = {"sinramp": 0, "identity": 1, "expr": 2}
 MAPFN = {"add": 0, "mul": 1, "sub": 2, "div": 3, "tuplecat": 4, "getchan": 5, "as1channel": 6,
-         "asnchannels": 7, "toeltype": 8, "reversech": 9}
+         "asnchannels": 7, "toeltype": 8, "reversech": 9, "expr": 10}
+# expression programs (so_eop_t): opcodes and function ids
+EOP = {"arg": 0, "const": 1, "un": 2, "bin": 3, "cmp": 4, "select": 5, "round32": 6}
+UN = {name: i for i, name in enumerate((
+    "neg", "abs", "sqrt", "cbrt", "square", "reciprocal", "exp", "exp2", "expm1", "log", "log2", "log10", "log1p",
+    "sin", "cos", "tan", "arcsin", "arccos", "arctan", "sinh", "cosh", "tanh", "arcsinh", "arccosh", "arctanh",
+    "floor", "ceil", "trunc", "rint", "sign"))}
+BIN = {name: i for i, name in enumerate((
+    "add", "sub", "mul", "div", "pow", "remainder", "fmod", "minimum", "maximum", "fmin", "fmax", "arctan2", "hypot",
+    "copysign"))}
+CMP = {"lt": 0, "le": 1, "gt": 2, "ge": 3, "eq": 4, "ne": 5}
 PAD = {"value": 0, "vector": 1, "zero": 2, "one": 3, "lastframe": 4, "cycle": 5, "mirror": 6}
 RS_RATIONAL, RS_ARBITRARY, RS_FIR = 0, 1, 2
 FILT = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}

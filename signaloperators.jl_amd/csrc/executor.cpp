@@ -535,7 +535,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                             fail(SO_ERR_RUNTIME, "hipRTC kernel launch failed");
                     } else
                         launch_pointwise(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_ops, P->d_leaves, ov, w.deep, st, w.chain,
-                                         w.il || (ov.fstride > 1 && ov.cstride == 1));
+                                         w.il || (ov.fstride > 1 && ov.cstride == 1), w.math);
                     s.launches = 1;
                     launches++;
                 }

@@ -14,6 +14,7 @@
 #include "sigops_internal.h"
 
 #include "kleaf.h"
+#include "kmath.h"
 
 namespace so {
 
@@ -105,12 +106,44 @@ __device__ __forceinline__ void slot_eval2(int kind, const DLeaf& L, int64_t n, 
         SO_POP1()                                       \
     }
 
+// The operations of expression programs (kmath.h) for the interpreter: one out-of-line call per operation and element,
+// so that the ~30 elementary functions do not all sit inline in the interpreter's opcode switch (registers, code size).
+static __device__ __attribute__((noinline)) double so_un_dispatch(int f, double x) {
+    switch (f) {
+#define SO_X(i, n) \
+    case i: return so_m_##n(x);
+        SO_UN_LIST(SO_X)
+#undef SO_X
+    default: return __builtin_nan("");
+    }
+}
+static __device__ __attribute__((noinline)) double so_bin_dispatch(int f, double a, double b) {
+    switch (f) {
+#define SO_X(i, n) \
+    case i: return so_m_##n(a, b);
+        SO_BIN_LIST(SO_X)
+#undef SO_X
+    default: return __builtin_nan("");
+    }
+}
+static __device__ __attribute__((noinline)) double so_cmp_dispatch(int f, double a, double b) {
+    switch (f) {
+#define SO_X(i, n) \
+    case i: return so_c_##n(a, b);
+        SO_CMP_LIST(SO_X)
+#undef SO_X
+    default: return __builtin_nan("");
+    }
+}
+
 // HEAVY == false drops the generator/ramp opcodes (the planner always hoists them into the
 // per-frame program), so the per-sample interpreter carries no transcendental code.
 // PAIR (E == 2, n[1] == n[0] + 1 for every lane, same parity of n[0] across the wave): array
 // leaves with unit frame stride are read with one 16-byte (fp64) / 8-byte (fp32) load per lane
 // when the pair is naturally aligned -- the widest, best-coalesced form of a streaming read.
-template <int E, bool CV, int D, bool HEAVY, bool PAIR = false>
+// MATH == true (k_pointwise's separate math instantiation, used only by steps that contain an expression-program
+// operation): OP_UN / OP_BIN / OP_CMP / OP_SELECT as well.  Every other instantiation compiles exactly as before.
+template <int E, bool CV, int D, bool HEAVY, bool PAIR = false, bool MATH = false>
 __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc, int len,
                                             const DLeaf* __restrict__ leaves,
                                             const int64_t (&n)[CV ? 1 : E], int c,
@@ -226,7 +259,30 @@ __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc,
             default: SO_PUSH(F[3][CV ? 0 : e]); break;
             }
             break;
-        default: break;
+        default:
+            if constexpr (MATH) {
+                if (op.code == OP_UN) {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) st[0][e] = so_un_dispatch(op.arg, st[0][e]);
+                } else if (op.code == OP_BIN || op.code == OP_CMP) {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) {
+                        st[0][e] = op.code == OP_BIN ? so_bin_dispatch(op.arg, st[1][e], st[0][e])
+                                                     : so_cmp_dispatch(op.arg, st[1][e], st[0][e]);
+                        SO_POP1()
+                    }
+                } else if (op.code == OP_SELECT) {
+                    if constexpr (D >= 3) {
+#pragma unroll
+                        for (int e = 0; e < E; ++e) {
+                            st[0][e] = so_select(st[2][e], st[1][e], st[0][e]);
+#pragma unroll
+                            for (int d = 1; d < D - 2; ++d) st[d][e] = st[d + 2][e];
+                        }
+                    }
+                }
+            }
+            break;
         }
     }
 #pragma unroll

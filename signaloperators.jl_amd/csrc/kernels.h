@@ -5,8 +5,21 @@
 #include "sigops_internal.h"
 
 namespace so {
+// Opcodes of the expression-program operations (include/sigops.h so_eop_t) in the fused pointwise programs, next to
+// sigops_internal.h's OpCode; arg = the so_un_t / so_bin_t / so_cmp_t function id.  Only k_pointwise's math
+// instantiation (launch_pointwise(..., math = true)) and the hipRTC kernels execute them.
+enum MathOpCode : int32_t {
+    OP_UN = 13,     // x -> f(x)
+    OP_BIN = 14,    // a, b -> f(a, b)
+    OP_CMP = 15,    // a, b -> (a f b) ? 1 : 0
+    OP_SELECT = 16  // c, a, b -> c != 0 ? a : b
+};
 void launch_pointwise(const DPiece* d_pieces, int npieces, int64_t nblocks, const DOp* d_ops,
-                      const DLeaf* d_leaves, OutView out, bool deep, hipStream_t st, bool chain = false, bool il = false);
+                      const DLeaf* d_leaves, OutView out, bool deep, hipStream_t st, bool chain = false, bool il = false,
+                      bool math = false);
+// the math instantiation (k_pointwise_math.hip, compiled with -ffp-contract=off); launch_pointwise(..., math = true) calls it
+void launch_pointwise_math(const DPiece* d_pieces, int npieces, int64_t nblocks, const DOp* d_ops, const DLeaf* d_leaves,
+                           OutView out, hipStream_t st);
 // returns number of kernel launches
 int launch_sos_poison(void* y, const SosGeom& g, hipStream_t st);
 int launch_fill_u32(void* p, size_t n, uint32_t v, hipStream_t st);  // (returns the launch's hipError_t)  // (instead of hipMemsetAsync: see k_sos.hip)

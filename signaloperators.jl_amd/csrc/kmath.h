@@ -1,0 +1,90 @@
+// Device implementation of the operations of expression programs (include/sigops.h so_eop_t: SO_UN_*, SO_BIN_*,
+// SO_CMP_*, select) -- the traced elementwise closures of `OperateOn(fn, xs...)`, `Signal(fn)` and custom ramp shapes
+// (reference src/mapsignal.jl:131-145, src/functions.jl:53-60, src/ramps.jl:60-72).  Used by the interpreter's math
+// instantiation (kcommon.h, run_program<..., MATH = true>) and, as TEXT embedded by build.py into rtc_embed.inc, by the
+// hipRTC kernels of steps that contain such an operation (rtc.cpp): both call these very functions, so the two paths
+// give the same values bit for bit.  Self-contained: no standard headers, no SO_* constants.
+//
+// Semantics are NumPy's ufuncs on Float64: minimum / maximum propagate NaN, fmin / fmax ignore it, remainder has the
+// sign of the divisor (npy_divmod), sign(±0) = +0, rint rounds half to even.  Every value is a Float64 (booleans are
+// 0.0 / 1.0); Float32 closures round with an explicit ROUND32 after each operation.
+#pragma once
+
+namespace so {
+
+// (function id, name): the ids are include/sigops.h's so_un_t / so_bin_t / so_cmp_t
+#define SO_UN_LIST(X)                                                                                              \
+    X(0, neg) X(1, abs) X(2, sqrt) X(3, cbrt) X(4, square) X(5, reciprocal) X(6, exp) X(7, exp2) X(8, expm1)      \
+    X(9, log) X(10, log2) X(11, log10) X(12, log1p) X(13, sin) X(14, cos) X(15, tan) X(16, arcsin) X(17, arccos)  \
+    X(18, arctan) X(19, sinh) X(20, cosh) X(21, tanh) X(22, arcsinh) X(23, arccosh) X(24, arctanh) X(25, floor)   \
+    X(26, ceil) X(27, trunc) X(28, rint) X(29, sign)
+#define SO_BIN_LIST(X)                                                                                             \
+    X(0, add) X(1, sub) X(2, mul) X(3, div) X(4, pow) X(5, remainder) X(6, fmod) X(7, minimum) X(8, maximum)      \
+    X(9, fmin) X(10, fmax) X(11, arctan2) X(12, hypot) X(13, copysign)
+#define SO_CMP_LIST(X) X(0, lt) X(1, le) X(2, gt) X(3, ge) X(4, eq) X(5, ne)
+
+#define SO_MF __device__ __forceinline__ double
+SO_MF so_m_neg(double x) { return -x; }
+SO_MF so_m_abs(double x) { return __builtin_fabs(x); }
+SO_MF so_m_sqrt(double x) { return ::sqrt(x); }
+SO_MF so_m_cbrt(double x) { return ::cbrt(x); }
+SO_MF so_m_square(double x) { return x * x; }
+SO_MF so_m_reciprocal(double x) { return 1.0 / x; }
+SO_MF so_m_exp(double x) { return ::exp(x); }
+SO_MF so_m_exp2(double x) { return ::exp2(x); }
+SO_MF so_m_expm1(double x) { return ::expm1(x); }
+SO_MF so_m_log(double x) { return ::log(x); }
+SO_MF so_m_log2(double x) { return ::log2(x); }
+SO_MF so_m_log10(double x) { return ::log10(x); }
+SO_MF so_m_log1p(double x) { return ::log1p(x); }
+SO_MF so_m_sin(double x) { return ::sin(x); }
+SO_MF so_m_cos(double x) { return ::cos(x); }
+SO_MF so_m_tan(double x) { return ::tan(x); }
+SO_MF so_m_arcsin(double x) { return ::asin(x); }
+SO_MF so_m_arccos(double x) { return ::acos(x); }
+SO_MF so_m_arctan(double x) { return ::atan(x); }
+SO_MF so_m_sinh(double x) { return ::sinh(x); }
+SO_MF so_m_cosh(double x) { return ::cosh(x); }
+SO_MF so_m_tanh(double x) { return ::tanh(x); }
+SO_MF so_m_arcsinh(double x) { return ::asinh(x); }
+SO_MF so_m_arccosh(double x) { return ::acosh(x); }
+SO_MF so_m_arctanh(double x) { return ::atanh(x); }
+SO_MF so_m_floor(double x) { return ::floor(x); }
+SO_MF so_m_ceil(double x) { return ::ceil(x); }
+SO_MF so_m_trunc(double x) { return ::trunc(x); }
+SO_MF so_m_rint(double x) { return ::rint(x); }
+SO_MF so_m_sign(double x) { return x > 0.0 ? 1.0 : x < 0.0 ? -1.0 : x == 0.0 ? 0.0 : x; }
+
+SO_MF so_m_add(double a, double b) { return a + b; }
+SO_MF so_m_sub(double a, double b) { return a - b; }
+SO_MF so_m_mul(double a, double b) { return a * b; }
+SO_MF so_m_div(double a, double b) { return a / b; }
+SO_MF so_m_pow(double a, double b) { return ::pow(a, b); }
+SO_MF so_m_fmod(double a, double b) { return ::fmod(a, b); }
+SO_MF so_m_remainder(double a, double b) {  // npy_divmod's modulus (Python `%` on floats)
+    double m = ::fmod(a, b);
+    if (b == 0.0) return m;
+    if (m != 0.0) {
+        if ((b < 0.0) != (m < 0.0)) m = m + b;
+    } else m = __builtin_copysign(0.0, b);
+    return m;
+}
+SO_MF so_m_minimum(double a, double b) { return a != a ? a : b != b ? b : (a < b ? a : b); }
+SO_MF so_m_maximum(double a, double b) { return a != a ? a : b != b ? b : (a > b ? a : b); }
+SO_MF so_m_fmin(double a, double b) { return a != a ? b : b != b ? a : (a < b ? a : b); }
+SO_MF so_m_fmax(double a, double b) { return a != a ? b : b != b ? a : (a > b ? a : b); }
+SO_MF so_m_arctan2(double a, double b) { return ::atan2(a, b); }
+SO_MF so_m_hypot(double a, double b) { return ::hypot(a, b); }
+SO_MF so_m_copysign(double a, double b) { return __builtin_copysign(a, b); }
+
+SO_MF so_c_lt(double a, double b) { return a < b ? 1.0 : 0.0; }
+SO_MF so_c_le(double a, double b) { return a <= b ? 1.0 : 0.0; }
+SO_MF so_c_gt(double a, double b) { return a > b ? 1.0 : 0.0; }
+SO_MF so_c_ge(double a, double b) { return a >= b ? 1.0 : 0.0; }
+SO_MF so_c_eq(double a, double b) { return a == b ? 1.0 : 0.0; }
+SO_MF so_c_ne(double a, double b) { return a != b ? 1.0 : 0.0; }
+
+SO_MF so_select(double c, double a, double b) { return c != 0.0 ? a : b; }
+#undef SO_MF
+
+}  // namespace so

@@ -66,11 +66,18 @@ struct Node {
 };
 
 // ---- expressions -------------------------------------------------------------
-enum { E_CONST, E_LOAD, E_SCALAR, E_FUNC, E_RAMP, E_ADD, E_SUB, E_MUL, E_DIV, E_NEG, E_ROUND32, E_RETYPE };
+// E_UN / E_BIN / E_CMP / E_SELECT: the operations of expression programs (traced closures, include/sigops.h so_eop_t)
+// other than + - * / and negation, which become E_ADD ... E_NEG; `fn` = the so_un_t / so_bin_t / so_cmp_t id.  Their
+// values are Float64 (a Float32 closure rounds with explicit E_ROUND32) and they count as heavy: a closure of the time
+// argument alone is evaluated once per frame.
+enum { E_CONST, E_LOAD, E_SCALAR, E_FUNC, E_RAMP, E_ADD, E_SUB, E_MUL, E_DIV, E_NEG, E_ROUND32, E_RETYPE,
+       E_UN, E_BIN, E_CMP, E_SELECT };
+inline bool is_math_op(int op) { return op >= E_UN; }
 struct Expr {
     int op;
     int dtype;
-    int a = -1, b = -1;
+    int a = -1, b = -1, c = -1;  // operands (E_SELECT: a = the condition, b / c = the values)
+    int fn = 0;
     DLeaf leaf{};
     int array_node = -1;  // E_LOAD of an ARRAY node (for so_plan_set_array)
     bool mono = true, heavy = false;
@@ -208,6 +215,7 @@ struct PwStep {
     int64_t bytes = 0;
     bool deep = false;  // some piece needs the 4-deep interpreter
     bool chain = false;  // some piece takes k_pointwise's chain path
+    bool math = false;   // some program has an expression-program operation (k_pointwise's math instantiation)
     bool il = false;     // ... with an interleaved leaf (the LDS-transposing instantiation)
     std::vector<int> pre;  // pointwise steps that materialise sub-expressions this one reads (run first)
     const void* rtc = nullptr;  // hipRTC-specialised kernel of this step (rtc.cpp), or null: the interpreter (k_pointwise)
@@ -354,6 +362,25 @@ struct Plan {
         e.heavy = exprs[a].heavy;
         return add_expr(e);
     }
+    // an expression-program operation: E_UN (a), E_BIN / E_CMP (a, b), E_SELECT (a = condition, b, c)
+    int mk_math(int op, int fn, int a, int b = -1, int c = -1) {
+        Expr e;
+        e.op = op;
+        e.fn = fn;
+        e.dtype = SO_F64;
+        e.a = a;
+        e.b = b;
+        e.c = c;
+        e.mono = exprs[a].mono && (b < 0 || exprs[b].mono) && (c < 0 || exprs[c].mono);
+        e.heavy = true;
+        return add_expr(e);
+    }
+    bool has_math(int e) const {
+        if (e < 0) return false;
+        const Expr& x = exprs[e];
+        if (is_math_op(x.op)) return true;
+        return x.op >= E_ADD && (has_math(x.a) || has_math(x.b));
+    }
     bool is_const(int e, double v) const { return exprs[e].op == E_CONST && exprs[e].leaf.v0 == v; }
     int mk_bin(int op, int a, int b) {
         int ta = exprs[a].dtype, tb = exprs[b].dtype;
@@ -398,7 +425,10 @@ struct Plan {
     std::vector<Piece> pad_pieces(int child, int padkind, double padvalue, const double* padvec,
                                   Rect r, Map m);
     std::vector<Piece> combine(const std::vector<std::vector<Piece>>& kids, Rect r, int op,
-                               int force_dtype);
+                               int force_dtype, const so_node_t* prog = nullptr);
+    // SO_MAP_EXPR / SO_RAMP_EXPR: the node's expression program over `args` (one expression per ARG index), converted
+    // to `dtype` at the end (-1: left as the program leaves it)
+    int prog_expr(const so_node_t& nd, const so_eop_t* prog, int len, const std::vector<int>& args, int dtype);
     int stage_for(int ni, int kind);
     void use_stage(Stage& S, const Rect& r, const Map& m);
     int in_norm = 0;  // > 0: lowering below a Normpower (stages created or used here are marked Stage::under_norm)
@@ -407,6 +437,7 @@ struct Plan {
     void process_stage(int sid);
     int emit_pointwise(const std::vector<Piece>& ps, int out_buf, int out_dtype);
     std::string rtc_expr(int e, std::vector<int>& monos, bool in_mono);
+    bool rtc_math = false;  // rtc_source: some piece calls kmath.h (its text goes in front of the source)
     std::vector<int>* rtc_loads = nullptr;  // rtc_source: the array leaves of the piece being written, read as frame pairs
     std::string rtc_source(const std::vector<Piece>& ps);
     bool match_carrier(int ei, DCarrier& C, std::vector<int>& monos);

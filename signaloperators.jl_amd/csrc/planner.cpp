@@ -14,6 +14,48 @@
 namespace so {
 
 // ===========================================================================
+// An expression program (include/sigops.h so_eop_t) must be well formed before anything evaluates it: known codes and
+// function ids, arguments in range, no stack underflow, exactly one value left.
+static void check_program(int node, const so_node_t& nd, const void* p, int len, int nargs) {
+    const std::string where = "node " + std::to_string(node) + ": expression program";
+    if (!p || len < 1) fail(SO_ERR_INVALID, where + " missing (null or empty)");
+    if (len > (1 << 16)) fail(SO_ERR_INVALID, where + " longer than 65536 operations");
+    const so_eop_t* prog = (const so_eop_t*)p;
+    int sp = 0;
+    for (int i = 0; i < len; ++i) {
+        const so_eop_t o = prog[i];
+        const std::string at = where + ", operation " + std::to_string(i) + ": ";
+        int need = 0, push = 1;
+        switch (o.code) {
+        case SO_EOP_ARG:
+            if (o.arg < 0 || o.arg >= nargs)
+                fail(SO_ERR_INVALID, at + "argument " + std::to_string(o.arg) + " out of range (" + std::to_string(nargs) + " arguments)");
+            break;
+        case SO_EOP_CONST:
+            if (o.arg < 0 || !nd.p1) fail(SO_ERR_INVALID, at + "constant " + std::to_string(o.arg) + " without a constant table");
+            break;
+        case SO_EOP_UN:
+            if (o.arg < 0 || o.arg >= SO_UN_COUNT) fail(SO_ERR_INVALID, at + "unknown unary function " + std::to_string(o.arg));
+            need = 1;
+            break;
+        case SO_EOP_BIN:
+            if (o.arg < 0 || o.arg >= SO_BIN_COUNT) fail(SO_ERR_INVALID, at + "unknown binary function " + std::to_string(o.arg));
+            need = 2;
+            break;
+        case SO_EOP_CMP:
+            if (o.arg < 0 || o.arg >= SO_CMP_COUNT) fail(SO_ERR_INVALID, at + "unknown comparison " + std::to_string(o.arg));
+            need = 2;
+            break;
+        case SO_EOP_SELECT: need = 3; break;
+        case SO_EOP_ROUND32: need = 1; break;
+        default: fail(SO_ERR_INVALID, at + "unknown code " + std::to_string(o.code));
+        }
+        if (sp < need) fail(SO_ERR_INVALID, at + "stack underflow");
+        sp += push - need;
+    }
+    if (sp != 1) fail(SO_ERR_INVALID, where + " leaves " + std::to_string(sp) + " values (must leave exactly one)");
+}
+
 void Plan::build_nodes(const so_node_t* in, int n) {
     nodes.resize(n);
     for (int i = 0; i < n; ++i) {
@@ -108,6 +150,9 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.nch = c.nch;
             N.dtype = float_of(c.dtype);
             if (nd.l0 < 1) fail(SO_ERR_INVALID, "ramp length must be >= 1 frame");
+            if (nd.i1 == SO_RAMP_EXPR) check_program(i, nd, nd.p0, nd.i2, 1);
+            else if (nd.i1 != SO_RAMP_SINRAMP && nd.i1 != SO_RAMP_IDENTITY)
+                fail(SO_ERR_INVALID, "node " + std::to_string(i) + ": unknown ramp function " + std::to_string(nd.i1));
             break;
         }
         case SO_NODE_MAP: {
@@ -120,6 +165,13 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             for (size_t j = 1; j < N.kids.size(); ++j) t = promote(t, nodes[N.kids[j]].dtype);
             if (fn == SO_MAP_DIV && t == SO_I64) t = SO_F64;
             if (fn == SO_MAP_TOELTYPE) t = nd.i3;
+            if (fn == SO_MAP_EXPR) {  // the program's own result type (the host traced it)
+                check_program(i, nd, nd.p0, nd.i3, (int)N.kids.size());
+                if (!nd.i1) fail(SO_ERR_INVALID, "node " + std::to_string(i) + ": expression maps are bychannel (one program per output channel)");
+                if (nd.dtype != SO_F32 && nd.dtype != SO_F64)
+                    fail(SO_ERR_UNSUPPORTED, "node " + std::to_string(i) + ": expression maps yield Float32 or Float64");
+                t = nd.dtype;
+            }
             N.dtype = t;
             if (nd.i1) {  // bychannel: Uniform(channels=true) already applied by the host
                 for (int k : N.kids)
@@ -355,7 +407,7 @@ std::vector<Piece> Plan::lower_padded(int ni, int padkind, double padvalue, cons
 
 // intersect the children's piece partitions of `r` and fold `op` left to right
 std::vector<Piece> Plan::combine(const std::vector<std::vector<Piece>>& kids, Rect r, int op,
-                                 int force_dtype) {
+                                 int force_dtype, const so_node_t* prog) {
     std::vector<int64_t> fb{r.a, r.b};
     std::vector<int> cb{r.c0, r.c1};
     for (auto& ps : kids)
@@ -375,6 +427,7 @@ std::vector<Piece> Plan::combine(const std::vector<std::vector<Piece>>& kids, Re
             Rect cell{fb[fi], fb[fi + 1], cb[ci], cb[ci + 1]};
             if (cell.a < r.a || cell.b > r.b || cell.c0 < r.c0 || cell.c1 > r.c1) continue;
             int acc = -1;
+            std::vector<int> args;
             for (auto& ps : kids) {
                 int e = -1;
                 for (auto& p : ps)
@@ -383,13 +436,58 @@ std::vector<Piece> Plan::combine(const std::vector<std::vector<Piece>>& kids, Re
                         break;
                     }
                 if (e < 0) fail(SO_ERR_RUNTIME, "internal: child pieces do not cover the cell");
-                acc = acc < 0 ? e : mk_bin(op, acc, e);
+                if (prog) args.push_back(e);
+                else acc = acc < 0 ? e : mk_bin(op, acc, e);
             }
-            (void)force_dtype;
+            // an expression map (SO_MAP_EXPR): the node's program over the cell's operands, converted to force_dtype
+            if (prog) acc = prog_expr(*prog, (const so_eop_t*)prog->p0, prog->i3, args, force_dtype);
+            else (void)force_dtype;
             // merge with the previous piece along frames when the expression is identical
             out.push_back({cell, acc});
         }
     return out;
+}
+
+int Plan::prog_expr(const so_node_t& nd, const so_eop_t* prog, int len, const std::vector<int>& args, int dtype) {
+    const double* consts = (const double*)nd.p1;
+    std::vector<int> st;  // (check_program has validated the program)
+    for (int i = 0; i < len; ++i) {
+        const so_eop_t o = prog[i];
+        int a, b, c;
+        switch (o.code) {
+        case SO_EOP_ARG: st.push_back(args[o.arg]); break;
+        case SO_EOP_CONST: st.push_back(mk_const(consts[o.arg], SO_F64)); break;
+        case SO_EOP_UN:
+            a = st.back();
+            st.back() = o.arg == SO_UN_NEG ? mk_un(E_NEG, a, exprs[a].dtype) : mk_math(E_UN, o.arg, a);
+            break;
+        case SO_EOP_BIN:
+        case SO_EOP_CMP:
+            b = st.back();
+            st.pop_back();
+            a = st.back();
+            if (o.code == SO_EOP_BIN && o.arg <= SO_BIN_DIV)  // + - * /: the arithmetic every map uses
+                st.back() = mk_bin(o.arg == SO_BIN_ADD ? E_ADD : o.arg == SO_BIN_SUB ? E_SUB : o.arg == SO_BIN_MUL ? E_MUL : E_DIV, a, b);
+            else st.back() = mk_math(o.code == SO_EOP_BIN ? E_BIN : E_CMP, o.arg, a, b);
+            break;
+        case SO_EOP_SELECT:
+            c = st.back();
+            st.pop_back();
+            b = st.back();
+            st.pop_back();
+            a = st.back();
+            st.back() = mk_math(E_SELECT, 0, a, b, c);
+            break;
+        default:  // SO_EOP_ROUND32
+            a = st.back();
+            st.back() = exprs[a].dtype == SO_F32 ? a : mk_un(E_ROUND32, a, SO_F32);
+            break;
+        }
+    }
+    int e = st.back();
+    if (dtype == SO_F32 && exprs[e].dtype != SO_F32) e = mk_un(E_ROUND32, e, SO_F32);
+    else if (dtype == SO_F64 && exprs[e].dtype != SO_F64) e = mk_un(E_RETYPE, e, SO_F64);
+    return e;
 }
 
 std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
@@ -489,7 +587,14 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         }
         auto region = [&](Rect rr, bool first) {
             bool is_ramp = (nd.i0 == 0) ? first : !first;
-            out.push_back({rr, is_ramp ? ramp_expr() : mk_const(1.0, onedt)});
+            int g;
+            if (!is_ramp) g = mk_const(1.0, onedt);  // (Ramp::Nothing: one(T), not fn(1) -- src/ramps.jl:56-59)
+            else if (nd.i1 == SO_RAMP_EXPR) {  // fn(x) of the ramp position x (the identity ramp)
+                const int x = ramp_expr();
+                exprs[x].leaf.mode = SO_RAMP_IDENTITY;
+                g = prog_expr(nd, (const so_eop_t*)nd.p0, nd.i2, {x}, -1);
+            } else g = ramp_expr();
+            out.push_back({rr, g});
         };
         if (m.sf == 0) {
             region(r, m.df < B);
@@ -517,6 +622,11 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             }
             int op = fn == SO_MAP_ADD ? E_ADD : fn == SO_MAP_MUL ? E_MUL : fn == SO_MAP_SUB ? E_SUB : E_DIV;
             return combine(ks, r, op, -1);
+        }
+        case SO_MAP_EXPR: {  // the program over the children's pieces, padded / combined as the arithmetic maps above
+            std::vector<std::vector<Piece>> ks;
+            for (int k : N.kids) ks.push_back(lower_padded(k, nd.i2, nd.d0, pv, r, m, false));
+            return combine(ks, r, -1, N.dtype, &nd);
         }
         case SO_MAP_TOELTYPE: {
             auto ps = lower_padded(N.kids[0], nd.i2, nd.d0, pv, r, m, false);
@@ -691,7 +801,9 @@ int Plan::depth(int ei) const {
     case E_RAMP: return 1;
     case E_NEG:
     case E_ROUND32:
-    case E_RETYPE: return depth(e.a);
+    case E_RETYPE:
+    case E_UN: return depth(e.a);
+    case E_SELECT: return std::max({depth(e.a), depth(e.b) + 1, depth(e.c) + 2});
     default: return std::max(depth(e.a), depth(e.b) + 1);
     }
 }
@@ -735,6 +847,22 @@ void Plan::gen(int ei, std::vector<DOp>& code, std::map<int, int>& hoisted,
         gen(e.a, code, hoisted, fcode, allow_hoist);
         code.push_back(DOp{OP_ROUND32, 0});
         return;
+    case E_UN:
+        gen(e.a, code, hoisted, fcode, allow_hoist);
+        code.push_back(DOp{OP_UN, e.fn});
+        return;
+    case E_BIN:
+    case E_CMP:
+        gen(e.a, code, hoisted, fcode, allow_hoist);
+        gen(e.b, code, hoisted, fcode, allow_hoist);
+        code.push_back(DOp{e.op == E_BIN ? OP_BIN : OP_CMP, e.fn});
+        return;
+    case E_SELECT:
+        gen(e.a, code, hoisted, fcode, allow_hoist);
+        gen(e.b, code, hoisted, fcode, allow_hoist);
+        gen(e.c, code, hoisted, fcode, allow_hoist);
+        code.push_back(DOp{OP_SELECT, 0});
+        return;
     default: {
         // `per-frame value (+|*) samples`: samples first (the same sum / product bit for bit), so that
         // Mix(sin, x) and Amplify(gain, x) compile to the kernel's chain form like Mix(x, sin)
@@ -766,7 +894,9 @@ int Plan::frame_slots(int ei) const {
     case E_RAMP: return 0;
     case E_NEG:
     case E_ROUND32:
-    case E_RETYPE: return frame_slots(e.a);
+    case E_RETYPE:
+    case E_UN: return frame_slots(e.a);
+    case E_SELECT: return frame_slots(e.a) + frame_slots(e.b) + frame_slots(e.c);
     default: return frame_slots(e.a) + frame_slots(e.b);
     }
 }
@@ -787,10 +917,12 @@ int Plan::shift_expr(int ei, int64_t a, int c0) {
         return add_expr(e);
     case E_NEG:
     case E_ROUND32:
-    case E_RETYPE: e.a = shift_expr(e.a, a, c0); return add_expr(e);
+    case E_RETYPE:
+    case E_UN: e.a = shift_expr(e.a, a, c0); return add_expr(e);
     default:
         e.a = shift_expr(e.a, a, c0);
         e.b = shift_expr(e.b, a, c0);
+        if (e.c >= 0) e.c = shift_expr(e.c, a, c0);
         return add_expr(e);
     }
 }
@@ -830,12 +962,33 @@ int Plan::legalise(int ei, const Rect& r, std::vector<int>& pre) {
     case E_RAMP: return ei;
     case E_NEG:
     case E_ROUND32:
-    case E_RETYPE: {
+    case E_RETYPE:
+    case E_UN: {
         const int a = legalise(e.a, r, pre);
         if (a == e.a) return ei;
         e.a = a;
         e.mono = exprs[a].mono;
-        e.heavy = exprs[a].heavy;
+        e.heavy = exprs[a].heavy || e.op == E_UN;
+        return add_expr(e);
+    }
+    case E_SELECT: {  // where(a, b, c): depth max(d(a), d(b) + 1, d(c) + 2)
+        int a = legalise(e.a, r, pre), b = legalise(e.b, r, pre), c = legalise(e.c, r, pre);
+        if (std::max({depth(a), depth(b) + 1, depth(c) + 2}) > kStackDepth) c = materialise(c, r, pre);
+        if (std::max({depth(a), depth(b) + 1, depth(c) + 2}) > kStackDepth) b = materialise(b, r, pre);
+        auto slots = [&]() {
+            return exprs[a].mono && exprs[b].mono && exprs[c].mono ? 1 : frame_slots(a) + frame_slots(b) + frame_slots(c);
+        };
+        while (slots() > kMaxFrameSlots) {
+            const int fa = frame_slots(a), fb = frame_slots(b), fc = frame_slots(c);
+            if (fa >= fb && fa >= fc) a = materialise(a, r, pre);
+            else if (fb >= fc) b = materialise(b, r, pre);
+            else c = materialise(c, r, pre);
+        }
+        if (a == e.a && b == e.b && c == e.c) return ei;
+        e.a = a;
+        e.b = b;
+        e.c = c;
+        e.mono = exprs[a].mono && exprs[b].mono && exprs[c].mono;
         return add_expr(e);
     }
     default: break;
@@ -853,7 +1006,7 @@ int Plan::legalise(int ei, const Rect& r, std::vector<int>& pre) {
     e.a = a;
     e.b = b;
     e.mono = exprs[a].mono && exprs[b].mono;
-    e.heavy = exprs[a].heavy || exprs[b].heavy;
+    e.heavy = exprs[a].heavy || exprs[b].heavy || is_math_op(e.op);
     return add_expr(e);
 }
 
@@ -874,7 +1027,7 @@ int Plan::emit_pointwise(const std::vector<Piece>& ps_in, int out_buf, int out_d
     {
         const char* ev = std::getenv("SIGOPS_RTC");
         const int mode = ev ? std::atoi(ev) : 2;
-        bool over = false;
+        bool over = false, math = false;
         int64_t elems = 0;
         int np = 0;
         for (auto& p : ps) {
@@ -882,8 +1035,12 @@ int Plan::emit_pointwise(const std::vector<Piece>& ps_in, int out_buf, int out_d
             ++np;
             elems += (p.r.b - p.r.a) * (int64_t)(p.r.c1 - p.r.c0);
             over = over || depth(p.e) > kStackDepth || frame_slots(p.e) > kMaxFrameSlots;
+            math = math || has_math(p.e);
         }
-        const bool want = np > 0 && np <= 32 && (mode == 1 || (mode == 2 && over && elems >= (1 << 20)));
+        // (a step with an expression-program operation -- a traced closure -- is compiled whenever hipRTC is allowed:
+        //  straight-line calls of kmath.h instead of the interpreter's out-of-line dispatch; the math instantiation of
+        //  k_pointwise runs it where hipRTC is switched off, missing, or fails)
+        const bool want = np > 0 && np <= 32 && (mode == 1 || (mode == 2 && over && elems >= (1 << 20)) || (mode != 0 && math));
         // ... and big steps the interpreter can run as they are: the specialised kernel if it is already there (this
         // process, or the code objects on disk), else the interpreter now and a background compile for later plans
         // (the straight-line form runs 15-20 % faster on Float64 maps, 1.6-2.1x on Float32 ones: tools/k1_probe.py)
@@ -953,6 +1110,9 @@ int Plan::emit_pointwise(const std::vector<Piece>& ps_in, int out_buf, int out_d
         for (auto& o : code)
             if (o.code == OP_FUNC || o.code == OP_RAMP)
                 fail(SO_ERR_UNSUPPORTED, "more than 4 distinct generator/ramp sub-expressions in one fused piece");
+        for (const auto* prog : {&code, &fcode})
+            for (auto& o : *prog)
+                if (o.code >= OP_UN) st.math = true;
         // a Float32 operation at the root of a piece that is stored as Float32: its rounding IS the store's (the same value
         // rounded twice) -- without the op the program of `x32 ./ rms` is `array (op) scalar` and takes the chain path below
         if (out_dtype == SO_F32 && code.size() >= 2 && code.back().code == OP_ROUND32 && !std::getenv("SIGOPS_K1_KEEPROUND")) code.pop_back();
@@ -1036,7 +1196,8 @@ void Plan::try_window_alias(std::vector<Piece>& rootp) {
             if (ex.op == E_LOAD && ex.leaf.buf >= 0) ls.push_back(x);
             if (ex.op >= E_ADD) {
                 stk.push_back(ex.a);
-                if (ex.op <= E_DIV) stk.push_back(ex.b);
+                if (ex.op <= E_DIV || is_math_op(ex.op)) stk.push_back(ex.b);
+                if (ex.op == E_SELECT) stk.push_back(ex.c);
             }
         }
     };

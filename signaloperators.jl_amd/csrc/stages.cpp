@@ -1269,6 +1269,9 @@ void Plan::process_stage(int sid) {
 // e == carrier load combined with channel-independent operands by a short chain of ops?
 bool Plan::match_carrier(int ei, DCarrier& C, std::vector<int>& monos) {
     const Expr e = exprs[ei];
+    // (a traced closure's operations are not part of the loaders' step language: such a source is materialised by a
+    //  pointwise step and arrives as a plain buffer)
+    if (has_math(ei)) return false;
     auto add_step = [&](int op, int mono_expr, bool flip, bool round32) {
         if (C.nsteps >= 4) return false;
         int slot = 0;

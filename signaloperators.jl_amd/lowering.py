@@ -336,6 +336,34 @@ def lower(x, nframes_out=None, rng=None):
             idx = lw.add(**r3)
         return idx
 
+    def program_fields(prog):
+        """p0 / p1 / length of an expression program (trace.py -> include/sigops.h so_eop_t)"""
+        code, consts = prog
+        lw.keep.append(code)
+        lw.keep.append(consts)
+        return dict(p0=code.ctypes.data, p1=consts.ctypes.data if consts.size else None), int(code.shape[0])
+
+    def expr_map(s, kids):
+        """an `elementwise` MapSignal: one SO_MAP_EXPR node over the operands (bychannel), or one per output channel
+        over every operand channel (SO_MAP_GETCHAN), joined by SO_MAP_TUPLECAT (bychannel=false)"""
+        pk, pv, _ = _pad_fields(s.padding, s.nch)
+        base = dict(kind=K.NODE_MAP, dtype=_DT[s.dtype], nch=1, nframes=_len_code(S.nframes(s)), fs=fs_of(s))
+        if s.bychannel:
+            f, n = program_fields(s.programs[0])
+            return lw.add(**dict(base, nch=s.nch), **f, i0=K.MAPFN["expr"], i1=1, i2=pk, d0=pv, i3=n, children=kids)
+        chans = []
+        for c, k in zip(s.signals, kids):
+            for j in range(c.nch):
+                chans.append(lw.add(kind=K.NODE_MAP, dtype=_DT[c.dtype], nch=1, nframes=_len_code(S.nframes(c)),
+                                    fs=fs_of(c), i0=K.MAPFN["getchan"], i1=0, i2=K.PAD["zero"], i3=j + 1, children=(k,)))
+        outs = []
+        for prog in s.programs:
+            f, n = program_fields(prog)
+            outs.append(lw.add(**base, **f, i0=K.MAPFN["expr"], i1=1, i2=pk, d0=pv, i3=n, children=tuple(chans)))
+        if len(outs) == 1:
+            return outs[0]
+        return lw.add(**dict(base, nch=len(outs)), i0=K.MAPFN["tuplecat"], i1=0, i2=pk, d0=pv, children=tuple(outs))
+
     def rec(s):
         key = id(s)
         if key in lw.memo and not (isinstance(s, S.FuncSig) and s.fn == S.RANDN):
@@ -378,6 +406,19 @@ def lower(x, nframes_out=None, rng=None):
             elif s.fn == S.OPAQUE:
                 n, _ = need.get(id(s), (0, 0))
                 idx = host_leaf(s, _host_function_leaf(s, max(n, 0)), infinite=True)
+            elif s.fn == S.EXPR:
+                # `elementwise` closure of the time argument: its program over the FUNC identity node, which yields
+                # 2π·fmod(tω+ϕ, 1) or t+ϕ as _host_function_leaf computes them
+                if s.fs is None:
+                    S.error("Unknown frame rate: function signals need a frame rate before `sink` (use ToFramerate)")
+                r = common(s, K.NODE_FUNC)
+                r.update(i0=K.FN["identity"], i1=0 if s.omega is None else 1,
+                         d0=0.0 if s.omega is None else float(s.omega), d1=s.phi, nch=1)
+                t = lw.add(**r)
+                (prog,), _ = s.pyfn.program([S.F64])
+                f, n = program_fields(prog)
+                idx = lw.add(**common(s, K.NODE_MAP), **f, i0=K.MAPFN["expr"], i1=1, i2=K.PAD["zero"], i3=n,
+                             children=(t,))
             else:
                 if s.fs is None:
                     S.error("Unknown frame rate: function signals need a frame rate before `sink` "
@@ -414,7 +455,13 @@ def lower(x, nframes_out=None, rng=None):
             if R is None:
                 S.error("Unknown number of frames in signal.")
             r = common(s, K.NODE_RAMP)
-            r.update(i0=0 if s.direction == "on" else 1, i1=K.RAMPFN[s.fn], l0=int(R), children=(c,))
+            r.update(i0=0 if s.direction == "on" else 1, l0=int(R), children=(c,))
+            if isinstance(s.fn, S.Elementwise):  # a custom shape: its program of the ramp position
+                (prog,), _ = s.fn.program([S.F64])
+                f, n = program_fields(prog)
+                r.update(f, i1=K.RAMPFN["expr"], i2=n)
+            else:
+                r["i1"] = K.RAMPFN[s.fn]
             idx = lw.add(**r)
         elif isinstance(s, S.MapSignal) and isinstance(s.fn, S.OpaqueFn):
             n, _ = need.get(id(s), (0, 0))
@@ -422,6 +469,8 @@ def lower(x, nframes_out=None, rng=None):
             if total is None:
                 S.error("Unknown number of frames in signal.")
             idx = host_leaf(s, _host_map_leaf(s, max(n, 0), rng), infinite=S.isknowninf(total), total=total)
+        elif isinstance(s, S.MapSignal) and isinstance(s.fn, S.ExprFn):
+            idx = expr_map(s, tuple(rec(c) for c in s.signals))
         elif isinstance(s, S.MapSignal):
             kids = tuple(rec(c) for c in s.signals)
             pk, pv, _ = _pad_fields(s.padding, s.nch)

@@ -18,6 +18,7 @@ import operator
 import numpy as np
 
 from . import units as U
+from .trace import Elementwise, elementwise  # noqa: F401
 from .units import Quantity
 
 
@@ -232,6 +233,7 @@ class NumberSig(AbstractSignal):
 
 SIN, COS, IDENTITY, RANDN = "sin", "cos", "identity", "randn"
 OPAQUE = "opaque"  # any other callable: evaluated on the host at sink time and handed to the engine as an array leaf
+EXPR = "expr"  # an `elementwise` closure: traced into a device program over the time argument (trace.py)
 
 
 def _fn_code(fn):
@@ -480,8 +482,11 @@ def _map_code(fn):
         return fn
     if isinstance(fn, str) and fn in (ADD, MUL, SUB, DIV, TUPLECAT, AS1CHANNEL, REVERSECH):
         return fn
-    if isinstance(fn, OpaqueFn):
+    if isinstance(fn, (OpaqueFn, ExprFn)):
         return fn
+    if isinstance(fn, Elementwise):
+        # a closure marked pure and elementwise: traced into a device program (trace.py; include/sigops.h SO_MAP_EXPR)
+        return ExprFn(fn)
     try:
         if fn in table:
             return table[fn]
@@ -505,8 +510,18 @@ class OpaqueFn:
         return f"OpaqueFn({self.fn!r})"
 
 
+class ExprFn:
+    """an `elementwise` closure used as a map function (traced, never called per sample)"""
+
+    def __init__(self, fn):
+        self.fn = fn  # the Elementwise marker (callable)
+
+    def __repr__(self):
+        return f"ExprFn({self.fn!r})"
+
+
 def default_pad(fn):  # src/mapsignal.jl:274-276
-    if isinstance(fn, OpaqueFn):
+    if isinstance(fn, (OpaqueFn, ExprFn)):
         return zero
     return one if fn in (MUL, DIV) else zero
 
@@ -528,7 +543,7 @@ class MapSignal(AbstractSignal):
         t = dts[0]
         for d in dts[1:]:
             t = promote_type(t, d)
-        if isinstance(fn, OpaqueFn):
+        if isinstance(fn, (OpaqueFn, ExprFn)):
             # test-value type inference (src/mapsignal.jl:139-143): the closure applied to ones
             try:
                 if bychannel:
@@ -543,6 +558,13 @@ class MapSignal(AbstractSignal):
                 error(f"OperateOn: could not apply {fn.fn!r} to test values: {e}")
             self.dtype = t
             self.nch = self.signals[0].nch if bychannel else self._opaque_nch
+            if isinstance(fn, ExprFn):  # the device program(s): one, or one per output channel (bychannel=false)
+                self.programs, odt = fn.fn.program([c.dtype for c in self.signals], bychannel,
+                                                   [c.nch for c in self.signals])
+                tdt = F32 if odt == F32 else F64
+                if tdt != t or len(self.programs) != (1 if bychannel else self.nch):
+                    error(f"OperateOn: the traced program of {fn.fn!r} yields {len(self.programs)} x {tdt}, its test "
+                          f"values {self.nch} x {t}")
             return
         if fn == DIV and t == I64:
             t = F64
@@ -671,9 +693,13 @@ def Signal(x=None, fs=None, *, ω=None, frequency=None, ϕ=0, phase=None, omega=
     if isinstance(x, (list, range)) or isinstance(x, np.ndarray) or _is_torch(x):
         return ArraySig(x, fs)
     if callable(x) or (isinstance(x, str) and x in (SIN, COS, IDENTITY, RANDN)):
-        code = _fn_code(x)
+        code = None if isinstance(x, Elementwise) else _fn_code(x)
         pyfn = None
-        if code is None:
+        if isinstance(x, Elementwise):
+            # traced into a device program over the time argument (include/sigops.h SO_MAP_EXPR over a FUNC identity)
+            x.program([F64])  # (traced here: what cannot be traced fails at construction, not at sink time)
+            code, pyfn = EXPR, x
+        elif code is None:
             # what the engine cannot lower is materialised on the host and passed
             # as an array leaf (here: the closure is evaluated with NumPy at sink time, lowering.py)
             code, pyfn = OPAQUE, x
@@ -950,6 +976,11 @@ def _ramp_args(args):
             fn = a
         else:
             ln = a
+    if isinstance(fn, np.ufunc):  # (a bare ufunc in the ramp position counts as marked: it is elementwise by definition)
+        fn = Elementwise(fn)
+    if isinstance(fn, Elementwise):  # any shape, as a device program of the ramp position (SO_RAMP_EXPR)
+        fn.program([F64])
+        return ln, fn
     if fn is sinramp:
         fn = "sinramp"
     elif fn is identity or getattr(fn, "__name__", "") == "identity":

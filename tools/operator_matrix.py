@@ -50,6 +50,11 @@ cases = {
     "Amplify(x, y) | ToFramerate": lambda: so.Amplify(X, Y) | so.ToFramerate(48 * so.kHz),
     "Mix(x, y) | Filt | ToFramerate": lambda: so.Mix(X, Y) | so.Filt(so.Lowpass, 3 * so.kHz) | so.ToFramerate(48 * so.kHz),
     "ToEltype(Float32)": lambda: so.ToEltype(X, np.float32),
+    # `elementwise` closures (traced device programs, include/sigops.h SO_MAP_EXPR / SO_RAMP_EXPR)
+    "closure tanh(2.5 x)": lambda: so.OperateOn(so.elementwise(lambda a: np.tanh(2.5 * a)), X),
+    "closure hypot(x, y)": lambda: so.OperateOn(so.elementwise(lambda a, b: np.hypot(a, b)), X, Y),
+    "Amplify(closure exp(-t/2))": lambda: so.Amplify(X, so.Signal(so.elementwise(lambda t: np.exp(-0.5 * t)), fs)) | so.Until(n * so.frames),
+    "RampOn 1 s closure u^2": lambda: X | so.RampOn(1 * so.s, so.elementwise(lambda u: u ** 2)),
 }
 only = os.environ.get("ONLY")
 WARM, REPS = int(os.environ.get("WARM", "20")), int(os.environ.get("REPS", "30"))
