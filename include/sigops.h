@@ -88,7 +88,9 @@ typedef enum so_kind {
 typedef enum so_fn {
     SO_FN_SIN = 0,     /* specialised through sinpi, src/functions.jl:57-60 */
     SO_FN_COS = 1,
-    SO_FN_IDENTITY = 2
+    SO_FN_IDENTITY = 2,
+    SO_FN_RANDN = 3    /* counter-based white noise, src/functions.jl:98-114: frame i is a pure function of
+                          (seed l0, stream l1, i) -- Philox4x32-10 + Box-Muller, DESIGN.md "Device noise" */
 } so_fn_t;
 
 /* RAMP shaping functions (src/ramps.jl:4 `sinramp`, tests use `identity`; any other
@@ -207,6 +209,7 @@ typedef enum so_rskind {
  *  CONST     d0=value  i0=literal type (so_dtype_t; SO_I64 promotes like Julia Int)
  *  FUNC      i0=so_fn_t  i1=has_omega  d0=omega(Hz)  d1=phi (cycles if has_omega
  *            else seconds, src/functions.jl:92-95)       fs = frame rate (required)
+ *            i0=SO_FN_RANDN: l0=seed  l1=stream (unsigned 64-bit bit patterns); i1, d0, d1 unused
  *  UNTIL     l0 = resolvelen (frames, may be <0: src/cutting.jl:32,130)
  *  AFTER     l0 = resolvelen (frames)
  *  PAD       i0=so_padkind_t  i1=extend(0 Pad / 1 Extend)  d0=value  p0=vector

@@ -5,7 +5,7 @@ from .signals import (  # noqa: F401
     ErrorException, inflen, isinf, nframes, nchannels, framerate, sampletype, duration, pipe,
     Signal, Until, After, Window, Pad, Extend, cycle, mirror, lastframe, zero, one,
     Append, Prepend, Mix, Amplify, AddChannel, SelectChannel, OperateOn, Operate, elementwise, Elementwise,
-    RampOn, RampOff, Ramp, FadeTo, sinramp, identity, randn,
+    RampOn, RampOff, Ramp, FadeTo, sinramp, identity, randn, DeviceRNG,
     Filt, Normpower, Lowpass, Highpass, Bandpass, Bandstop, Butterworth, Chebyshev1,
     ToFramerate, ToChannels, ToEltype, Format, Uniform,
     ArraySig, NumberSig, FuncSig, CutApply, PaddedSignal, AppendSignals, RampSignal,

@@ -530,7 +530,9 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 if (w.nblocks > 0) {
                     static const int il_scalar = std::getenv("SIGOPS_K1_ILSCALAR") ? 1 : 0;  // ablation knob
                     ov.pad = il_scalar;
-                    if (w.rtc) {
+                    if (w.fill)
+                        launch_randn_fill(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_leaves, ov, st);
+                    else if (w.rtc) {
                         if (rtc_launch(w.rtc, w.nblocks, P->d_pieces + w.piece0, w.npieces, P->d_leaves, ov, st) != 0)
                             fail(SO_ERR_RUNTIME, "hipRTC kernel launch failed");
                     } else

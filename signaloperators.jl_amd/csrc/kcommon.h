@@ -15,6 +15,7 @@
 
 #include "kleaf.h"
 #include "kmath.h"
+#include "krand.h"
 
 namespace so {
 
@@ -142,7 +143,7 @@ static __device__ __attribute__((noinline)) double so_cmp_dispatch(int f, double
 // leaves with unit frame stride are read with one 16-byte (fp64) / 8-byte (fp32) load per lane
 // when the pair is naturally aligned -- the widest, best-coalesced form of a streaming read.
 // MATH == true (k_pointwise's separate math instantiation, used only by steps that contain an expression-program
-// operation): OP_UN / OP_BIN / OP_CMP / OP_SELECT as well.  Every other instantiation compiles exactly as before.
+// operation or a counter-based noise leaf): OP_UN / OP_BIN / OP_CMP / OP_SELECT and OP_FUNC's SO_FN_RANDN as well.  Every other instantiation compiles exactly as before.
 template <int E, bool CV, int D, bool HEAVY, bool PAIR = false, bool MATH = false>
 __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc, int len,
                                             const DLeaf* __restrict__ leaves,
@@ -217,6 +218,14 @@ __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc,
         case OP_FUNC:
             if constexpr (HEAVY) {
                 const DLeaf& L = leaves[op.arg];
+                // (SO_FN_RANDN, krand.h: only the math instantiation ever sees such a leaf -- the planner routes a step
+                //  that contains one there -- so the others carry no generator code)
+                if constexpr (MATH) {
+                    if (L.mode == SO_FN_RANDN) {
+                        SO_PUSH(randn_eval(L, n[CV ? 0 : e]));
+                        break;
+                    }
+                }
                 SO_PUSH(func_eval(L, n[CV ? 0 : e]));
             }
             break;

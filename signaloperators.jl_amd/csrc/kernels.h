@@ -20,6 +20,24 @@ void launch_pointwise(const DPiece* d_pieces, int npieces, int64_t nblocks, cons
 // the math instantiation (k_pointwise_math.hip, compiled with -ffp-contract=off); launch_pointwise(..., math = true) calls it
 void launch_pointwise_math(const DPiece* d_pieces, int npieces, int64_t nblocks, const DOp* d_ops, const DLeaf* d_leaves,
                            OutView out, hipStream_t st);
+// Counter-based noise over frame ranges (k_randn_fill.hip, -ffp-contract=off).  A piece of such a step has no programs
+// (frame_len = samp_len = 0: neither the interpreter nor Plan::plan_lanes reads the op table for it), and three of the
+// fields the programs would use carry its operands instead -- read and written through these names only:
+constexpr int32_t& fill_noise_leaf(DPiece& p) { return p.frame_pc; }              // index of the noise leaf
+constexpr int32_t fill_noise_leaf(const DPiece& p) { return p.frame_pc; }
+constexpr int32_t& fill_scale_leaf(DPiece& p) { return p.samp_pc; }               // leaf of a constant factor, or -1
+constexpr int32_t fill_scale_leaf(const DPiece& p) { return p.samp_pc; }
+constexpr int32_t& fill_flags(DPiece& p) { return p.chain; }                      // kFillRound*
+constexpr int32_t fill_flags(const DPiece& p) { return p.chain; }
+constexpr int kFillRoundNoise = 1, kFillRoundProduct = 2;  // round the noise / the product to Float32 (Julia Float32 arithmetic)
+// nblk_f = workgroups of kBlock Box-Muller pairs; the value goes to every channel [c0, c1) of the piece.
+// The noise leaf itself (SO_FN_RANDN) keeps the seed in DLeaf::modn and the stream in DLeaf::fstride, fields a generator
+// has no other use for; krand.h reads them back (randn_seed / randn_stream).
+constexpr void set_randn_leaf(DLeaf& L, uint64_t seed, uint64_t stream) {
+    L.modn = (int64_t)seed;
+    L.fstride = (int64_t)stream;
+}
+void launch_randn_fill(const DPiece* d_pieces, int npieces, int64_t nblocks, const DLeaf* d_leaves, OutView out, hipStream_t st);
 // returns number of kernel launches
 int launch_sos_poison(void* y, const SosGeom& g, hipStream_t st);
 int launch_fill_u32(void* p, size_t n, uint32_t v, hipStream_t st);  // (returns the launch's hipError_t)  // (instead of hipMemsetAsync: see k_sos.hip)

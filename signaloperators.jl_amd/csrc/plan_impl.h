@@ -215,7 +215,8 @@ struct PwStep {
     int64_t bytes = 0;
     bool deep = false;  // some piece needs the 4-deep interpreter
     bool chain = false;  // some piece takes k_pointwise's chain path
-    bool math = false;   // some program has an expression-program operation (k_pointwise's math instantiation)
+    bool math = false;   // some program has an expression-program operation or a noise leaf (k_pointwise's math instantiation)
+    bool fill = false;   // every piece is a noise leaf alone, optionally times a constant: k_randn_fill (its pieces: kernels.h fill_*)
     bool il = false;     // ... with an interleaved leaf (the LDS-transposing instantiation)
     std::vector<int> pre;  // pointwise steps that materialise sub-expressions this one reads (run first)
     const void* rtc = nullptr;  // hipRTC-specialised kernel of this step (rtc.cpp), or null: the interpreter (k_pointwise)
@@ -379,6 +380,9 @@ struct Plan {
         if (e < 0) return false;
         const Expr& x = exprs[e];
         if (is_math_op(x.op)) return true;
+        // (a counter-based noise leaf counts: only the math instantiation and the hipRTC kernels evaluate it, and no
+        //  stage kernel takes it as a carrier's per-frame value -- match_carrier)
+        if (x.op == E_FUNC && x.leaf.mode == SO_FN_RANDN) return true;
         return x.op >= E_ADD && (has_math(x.a) || has_math(x.b));
     }
     bool is_const(int e, double v) const { return exprs[e].op == E_CONST && exprs[e].leaf.v0 == v; }
@@ -436,8 +440,13 @@ struct Plan {
     void check_frames(int ni, int64_t upto);
     void process_stage(int sid);
     int emit_pointwise(const std::vector<Piece>& ps, int out_buf, int out_dtype);
+    // a piece of the fill form: the noise leaf's expression, the constant factor's (or -1), kFillRound* flags
+    struct RandnFill { int noise = -1, scale = -1, flags = 0; };
+    bool match_randn_fill(int ei, RandnFill& m) const;
+    int emit_randn_fill(const std::vector<Piece>& ps, int out_buf, int out_dtype);
     std::string rtc_expr(int e, std::vector<int>& monos, bool in_mono);
     bool rtc_math = false;  // rtc_source: some piece calls kmath.h (its text goes in front of the source)
+    bool rtc_rand = false;  // ... krand.h (a counter-based noise leaf)
     std::vector<int>* rtc_loads = nullptr;  // rtc_source: the array leaves of the piece being written, read as frame pairs
     std::string rtc_source(const std::vector<Piece>& ps);
     bool match_carrier(int ei, DCarrier& C, std::vector<int>& monos);

@@ -91,7 +91,10 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = nd.i0;
             break;
         case SO_NODE_FUNC:
-            if (!(nd.fs > 0)) fail(SO_ERR_LENGTH, "Unknown frame rate: function signals need a frame rate");
+            if (nd.i0 < SO_FN_SIN || nd.i0 > SO_FN_RANDN)
+                fail(SO_ERR_INVALID, "node " + std::to_string(i) + ": unknown function " + std::to_string(nd.i0));
+            // (counter-based noise does not depend on time: the frame rate is only the node's rate)
+            if (nd.i0 != SO_FN_RANDN && !(nd.fs > 0)) fail(SO_ERR_LENGTH, "Unknown frame rate: function signals need a frame rate");
             N.len = Len{LK_INF, 0};
             N.nch = 1;
             N.dtype = SO_F64;
@@ -533,6 +536,11 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         e.leaf.v0 = nd.d0;
         e.leaf.v1 = nd.d1;
         e.leaf.v2 = nd.fs;
+        if (nd.i0 == SO_FN_RANDN) {  // krand.h randn_eval: seed and stream where a generator has no use for the fields
+            e.leaf.flag = 0;
+            e.leaf.v0 = e.leaf.v1 = e.leaf.v2 = 0.0;
+            set_randn_leaf(e.leaf, (uint64_t)nd.l0, (uint64_t)nd.l1);
+        }
         e.heavy = true;
         out.push_back({r, add_expr(e)});
         return out;
@@ -1012,12 +1020,86 @@ int Plan::legalise(int ei, const Rect& r, std::vector<int>& pre) {
 
 void Plan::push_pw_step(int idx) {
     for (int q : pw[idx].pre) push_pw_step(q);
-    steps.push_back(Step{0, idx, pw[idx].rtc ? "k_pointwise_rtc" : "k_pointwise", pw[idx].bytes});
+    steps.push_back(Step{0, idx, pw[idx].fill ? "k_randn_fill" : pw[idx].rtc ? "k_pointwise_rtc" : "k_pointwise", pw[idx].bytes});
+}
+
+// The fill form of counter-based noise (k_randn_fill.hip): every piece is a noise leaf over a frame range, optionally
+// times a constant, replicated to the piece's channels.  One lane makes BOTH frames of a Box-Muller pair and stores them,
+// where the expression form spends a whole evaluation on each frame.  The same functions, the same rounding: the two
+// forms agree bit for bit (krand.h).  Returns the new pointwise step, or -1 where some piece is anything else
+// (SIGOPS_RANDN_NOFILL: always).
+bool Plan::match_randn_fill(int ei, RandnFill& m) const {
+    auto strip = [&](int x, int bit) {  // conversions around a value; a rounding to Float32 sets `bit`
+        for (;;) {
+            const Expr& ex = exprs[x];
+            if (ex.op == E_RETYPE) x = ex.a;
+            else if (ex.op == E_ROUND32) { m.flags |= bit; x = ex.a; }
+            else return x;
+        }
+    };
+    int x = strip(ei, kFillRoundProduct);
+    if (exprs[x].op == E_MUL) {
+        int a = exprs[x].a, b = exprs[x].b;
+        if (exprs[a].op == E_CONST) std::swap(a, b);
+        if (exprs[b].op != E_CONST) return false;
+        m.scale = b;
+        if (exprs[x].dtype == SO_F32) m.flags |= kFillRoundProduct;  // (Float32 arithmetic: the product is rounded, as Plan::gen does)
+        x = strip(a, kFillRoundNoise);
+    }
+    const Expr& f = exprs[x];
+    if (f.op != E_FUNC || f.leaf.mode != SO_FN_RANDN || f.leaf.sf != 1 || !f.mono) return false;
+    m.noise = x;
+    return true;
+}
+
+int Plan::emit_randn_fill(const std::vector<Piece>& ps, int out_buf, int out_dtype) {
+    if (dry || std::getenv("SIGOPS_RANDN_NOFILL")) return -1;
+    std::vector<RandnFill> fills;
+    for (auto& p : ps) {
+        if (p.r.a >= p.r.b || p.r.c0 >= p.r.c1) continue;
+        RandnFill m;
+        if (!match_randn_fill(p.e, m) || p.r.a + exprs[m.noise].leaf.df < 0) return -1;
+        fills.push_back(m);
+    }
+    if (fills.empty()) return -1;
+    PwStep st;
+    st.fill = true;
+    st.piece0 = (int)pieces.size();
+    st.out_buf = out_buf;
+    int64_t blk = 0;
+    size_t k = 0;
+    for (auto& p : ps) {
+        if (p.r.a >= p.r.b || p.r.c0 >= p.r.c1) continue;
+        const RandnFill& m = fills[k++];
+        DPiece d{};  // (no programs: frame_len = samp_len = 0, so nothing walks the op table for this piece)
+        d.a = p.r.a;
+        d.b = p.r.b;
+        d.c0 = p.r.c0;
+        d.c1 = p.r.c1;
+        fill_noise_leaf(d) = add_leaf(exprs[m.noise]);
+        fill_scale_leaf(d) = m.scale >= 0 ? add_leaf(exprs[m.scale]) : -1;
+        fill_flags(d) = m.flags;
+        d.depth = 2;
+        d.sub = 1;
+        d.chc = d.c1 - d.c0;
+        const int64_t i0 = d.a + exprs[m.noise].leaf.df, i1 = d.b - 1 + exprs[m.noise].leaf.df;  // absolute frames, inclusive
+        d.nblk_f = ((i1 >> 1) - (i0 >> 1) + 1 + kBlock - 1) / kBlock;                             // one lane per pair
+        d.block0 = blk;
+        blk += d.nblk_f;
+        pieces.push_back(d);
+        st.bytes += (d.b - d.a) * (int64_t)(d.c1 - d.c0) * (int64_t)dsize(out_dtype);
+    }
+    st.npieces = (int)pieces.size() - st.piece0;
+    st.nblocks = blk;
+    pw.push_back(st);
+    return (int)pw.size() - 1;
 }
 
 // compile pieces into one pointwise launch writing `out_buf` (or the final output)
 int Plan::emit_pointwise(const std::vector<Piece>& ps_in, int out_buf, int out_dtype) {
     std::vector<Piece> ps = ps_in;
+    // a step that is nothing but counter-based noise over frame ranges: the fill kernel, not a program
+    if (const int fill = emit_randn_fill(ps, out_buf, out_dtype); fill >= 0) return fill;
     // ---- hipRTC (rtc.cpp): the step as straight-line source instead of interpreter programs.
     //      SIGOPS_RTC=1: every pointwise step of up to 32 pieces; 0: never; default: steps the interpreter
     //      could only run after materialising sub-expressions (too deep / too many per-frame values), when
@@ -1112,7 +1194,7 @@ int Plan::emit_pointwise(const std::vector<Piece>& ps_in, int out_buf, int out_d
                 fail(SO_ERR_UNSUPPORTED, "more than 4 distinct generator/ramp sub-expressions in one fused piece");
         for (const auto* prog : {&code, &fcode})
             for (auto& o : *prog)
-                if (o.code >= OP_UN) st.math = true;
+                if (o.code >= OP_UN || (o.code == OP_FUNC && leaves[o.arg].mode == SO_FN_RANDN)) st.math = true;
         // a Float32 operation at the root of a piece that is stored as Float32: its rounding IS the store's (the same value
         // rounded twice) -- without the op the program of `x32 ./ rms` is `array (op) scalar` and takes the chain path below
         if (out_dtype == SO_F32 && code.size() >= 2 && code.back().code == OP_ROUND32 && !std::getenv("SIGOPS_K1_KEEPROUND")) code.pop_back();

@@ -243,8 +243,10 @@ def stream(x, blocksize, to=None, *, device=0):
     time before the block and a resampler a few periods before it (warm start), and the
     resampler's DSP.jl phase accumulator resumes from the previous block's end (a rate without a period -- non-integer
     frame rates, x pi -- starts exactly at the block: its stage stages taps + 2 input frames before the block's first
-    output and lists the accumulator's deviations from the nearest checkpoint of an earlier replay).  Host arrays of the tree are uploaded once.  `Normpower` needs its whole child for every block and `randn` leaves
-    draw new numbers for every block: neither is meant for streaming."""
+    output and lists the accumulator's deviations from the nearest checkpoint of an earlier replay).  Host arrays of the tree are uploaded once.  `Normpower` needs its whole child for every block and a `randn` leaf
+    with a host generator draws new numbers for every block: neither is meant for streaming.  `Signal(randn,
+    rng=DeviceRNG(...))` streams like any generator: its frames depend on their index alone, so the blocks are the whole
+    sink's frames and a filter's warm start re-reads the noise the previous block emitted."""
     from . import lowering as LW
     from .units import frames
 

@@ -194,6 +194,8 @@ def _demand(x, n, out, skip=0):
     if n is None or S.isknowninf(n) or n <= 0:
         return  # (infinite demands are rejected by the planner with the reference's error)
     if isinstance(x, S.FuncSig):
+        if x.fn == S.RANDN and isinstance(x.rng, S.DeviceRNG):
+            return  # generated on the device from the frame index: nothing to size
         if x.fn in (S.RANDN, S.OPAQUE):
             n0, s0 = out.get(id(x), (0, skip))
             out[id(x)] = (max(n0, n), min(s0, skip))
@@ -302,7 +304,17 @@ def _host_map_leaf(s, n, rng):
     return np.asfortranarray(np.asarray(out, dtype=s.dtype if s.dtype != S.I64 else np.float64).reshape(n, -1))
 
 
+def _as_i64(u):
+    """an unsigned 64-bit value as the signed integer with the same bits (so_node_t l0 / l1)"""
+    return u - (1 << 64) if u >= 1 << 63 else u
+
+
 def lower(x, nframes_out=None, rng=None):
+    if isinstance(rng, S.DeviceRNG):
+        # (a sink-level default would have to number the leaves it is handed to, and that numbering is what differs
+        #  between a whole sink, its blocks and its shards)
+        S.error("sink(x, rng=DeviceRNG(...)): a counter-based generator belongs to the leaf -- "
+                "write Signal(randn, rng=DeviceRNG(seed, stream)), one stream per independent noise")
     x = S._assignal(x)
     lw = Lowered()
     need = {}
@@ -366,7 +378,7 @@ def lower(x, nframes_out=None, rng=None):
 
     def rec(s):
         key = id(s)
-        if key in lw.memo and not (isinstance(s, S.FuncSig) and s.fn == S.RANDN):
+        if key in lw.memo and not (isinstance(s, S.FuncSig) and s.fn == S.RANDN and not isinstance(s.rng, S.DeviceRNG)):
             return lw.memo[key]
         lw.keep.append(s)
         if isinstance(s, S.ArraySig):
@@ -385,7 +397,13 @@ def lower(x, nframes_out=None, rng=None):
             r.update(d0=float(s.val), i0=_DT[s.dtype], nch=1)
             idx = lw.add(**r)
         elif isinstance(s, S.FuncSig):
-            if s.fn == S.RANDN:
+            if s.fn == S.RANDN and isinstance(s.rng, S.DeviceRNG):
+                # counter-based noise (include/sigops.h SO_FN_RANDN): one FUNC node, the seed and the stream as the
+                # bit patterns of l0 / l1; the frame rate is only the node's rate
+                r = common(s, K.NODE_FUNC)
+                r.update(i0=K.FN["randn"], l0=_as_i64(s.rng.seed), l1=_as_i64(s.rng.stream), nch=1)
+                idx = lw.add(**r)
+            elif s.fn == S.RANDN:
                 # randn leaves are host-materialised (SURVEY.md §7 hard part 7): one
                 # N(0,1) draw per evaluated frame, in increasing frame order
                 n, skipped = need.get(id(s), (0, 0))

@@ -261,6 +261,46 @@ def randn(*a):
     return np.random.randn(*a)
 
 
+class DeviceRNG:
+    """A counter-based generator for `Signal(randn, fs, rng=DeviceRNG(seed, stream))`: the noise is made on the GPU and
+    frame `i` of the leaf is a pure function of `(seed, stream, i)` -- Philox4x32-10 on the pair index `i >> 1`, the
+    two 53-bit uniforms through Box-Muller ("Device noise").  So a window, a block of `stream`, a time-range
+    shard and a second execute of a plan all see the same samples, and nothing is drawn on the host or uploaded.
+
+    The one deliberate difference from a stateful NumPy `Generator`: the object holds no state.  Two leaves with equal
+    `(seed, stream)` are the SAME noise; independent noises take different streams (`g.spawn(k)` is
+    `DeviceRNG(seed, stream + k)`).  `seed` and `stream` are unsigned 64-bit; the value is immutable, compares and
+    hashes by `(seed, stream)`."""
+
+    __slots__ = ("_seed", "_stream")
+
+    def __init__(self, seed, stream=0):
+        for name, v in (("seed", seed), ("stream", stream)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 64:
+                error(f"DeviceRNG: {name} must be an integer in [0, 2^64)")
+        object.__setattr__(self, "_seed", int(seed))
+        object.__setattr__(self, "_stream", int(stream))
+
+    seed = property(lambda self: self._seed)
+    stream = property(lambda self: self._stream)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("DeviceRNG is immutable")
+
+    def spawn(self, k):
+        """the generator `k` streams further on (same seed): an independent noise"""
+        return DeviceRNG(self._seed, (self._stream + int(k)) % (1 << 64))
+
+    def __eq__(self, other):
+        return isinstance(other, DeviceRNG) and (self._seed, self._stream) == (other._seed, other._stream)
+
+    def __hash__(self):
+        return hash(("DeviceRNG", self._seed, self._stream))
+
+    def __repr__(self):
+        return f"DeviceRNG(seed={self._seed}, stream={self._stream})"
+
+
 class FuncSig(AbstractSignal):
     """SignalFunction, reference src/functions.jl:11-60,88-96"""
 

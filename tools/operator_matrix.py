@@ -55,6 +55,21 @@ cases = {
     "closure hypot(x, y)": lambda: so.OperateOn(so.elementwise(lambda a, b: np.hypot(a, b)), X, Y),
     "Amplify(closure exp(-t/2))": lambda: so.Amplify(X, so.Signal(so.elementwise(lambda t: np.exp(-0.5 * t)), fs)) | so.Until(n * so.frames),
     "RampOn 1 s closure u^2": lambda: X | so.RampOn(1 * so.s, so.elementwise(lambda u: u ** 2)),
+    # counter-based device noise (`Signal(randn, rng=so.DeviceRNG(...))`, csrc/krand.h): the fill kernel, the same leaf as
+    # an expression (hipRTC, K1's math instantiation: `case_env`), replicated to the channels, and the headline's tree
+    # with the noise in place of its array leaf next to the array-leaf form (FRAMES=26.46e6 for the headline's own size)
+    "noise fill (mono, n x nch)": lambda: NOISE() | so.Until(n * nch * so.frames),
+    "noise expr hipRTC (mono)": lambda: NOISE() | so.Until(n * nch * so.frames),
+    "noise expr K1 math (mono)": lambda: NOISE() | so.Until(n * nch * so.frames),
+    "ToChannels(noise) fill": lambda: NOISE() | so.Until(n * so.frames) | so.ToChannels(nch),
+    "headline, array leaf": lambda: so.Mix(tone, X) | so.Until(n * so.frames) | so.Filt(so.Bandstop, 0.5 * so.kHz, 2 * so.kHz) | so.ToFramerate(48 * so.kHz),
+    "headline, noise leaf": lambda: so.Mix(tone, so.ToChannels(NOISE(), nch)) | so.Until(n * so.frames) | so.Filt(so.Bandstop, 0.5 * so.kHz, 2 * so.kHz) | so.ToFramerate(48 * so.kHz),
+}
+NOISE = lambda: so.Signal(so.randn, fs, rng=so.DeviceRNG(2024, 0))  # noqa: E731
+# environment of a case while its plan is created (the planner reads its knobs then)
+case_env = {
+    "noise expr hipRTC (mono)": {"SIGOPS_RANDN_NOFILL": "1", "SIGOPS_RTC": "1"},
+    "noise expr K1 math (mono)": {"SIGOPS_RANDN_NOFILL": "1", "SIGOPS_RTC": "0"},
 }
 only = os.environ.get("ONLY")
 WARM, REPS = int(os.environ.get("WARM", "20")), int(os.environ.get("REPS", "30"))
@@ -67,7 +82,13 @@ for name, mk in cases.items():
         odt = np.float32 if ("Float32" in name or NDT == np.float32) else np.float64
         tdt = torch.float32 if odt == np.float32 else torch.float64
         out = torch.empty((co, nout), dtype=tdt, device="cuda").t()
-        plan = so.Plan(so.ToChannels(tree, co), (nout, co), odt, (out.stride(0), out.stride(1)), True)
+        saved = {k: os.environ.get(k) for k in case_env.get(name, {})}
+        os.environ.update(case_env.get(name, {}))
+        try:
+            plan = so.Plan(so.ToChannels(tree, co), (nout, co), odt, (out.stride(0), out.stride(1)), True)
+        finally:
+            for k, v in saved.items():
+                os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
         st = torch.cuda.current_stream().cuda_stream
         for _ in range(WARM):
             plan.execute(out.data_ptr(), st)
@@ -94,3 +115,22 @@ for name, mk in cases.items():
         del out
     except Exception as exc:  # (a case the mirror does not spell this way)
         print(f"{name:28s} skipped: {type(exc).__name__}: {str(exc)[:80]}", flush=True)
+
+# Whole `sink` of white noise into a device-resident result, host wall clock: the counter-based generator against a NumPy
+# generator (drawn on the host and uploaded).  Inside the timer: building the tree, `so.sink(tree, "torch")` -- lowering,
+# plan creation, the result's allocation, the execute, the plan's check -- and a device synchronise.  SINKS sinks in a
+# row in this process; the first pays the one-time costs (code object load).
+if not only or only in "whole sink of noise":
+    import time
+
+    secs, SINKS = float(os.environ.get("NOISE_SECONDS", "60")), int(os.environ.get("SINKS", "5"))
+    for label, mk in (("DeviceRNG(0)", lambda: so.DeviceRNG(0)), ("np.random.default_rng(0)", lambda: np.random.default_rng(0))):
+        ts = []
+        for _ in range(SINKS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res, _ = so.sink(so.Signal(so.randn, fs, rng=mk()) | so.Until(secs * so.s) | so.ToChannels(nch), "torch")
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            del res
+        print(f"whole sink of noise, {secs:g} s x {nch} ch, {label:26s} wall ms: " + " ".join(f"{t:.2f}" for t in ts), flush=True)
