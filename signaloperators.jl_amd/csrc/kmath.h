@@ -6,8 +6,11 @@
 // give the same values bit for bit.  Self-contained: no standard headers, no SO_* constants.
 //
 // Semantics are NumPy's ufuncs on Float64: minimum / maximum propagate NaN, fmin / fmax ignore it, remainder has the
-// sign of the divisor (npy_divmod), sign(±0) = +0, rint rounds half to even.  Every value is a Float64 (booleans are
-// 0.0 / 1.0); Float32 closures round with an explicit ROUND32 after each operation.
+// sign of the divisor (npy_divmod), sign(±0) = +0, rint rounds half to even, a zero result has the sign C99 gives it
+// (expm1(-0) = log1p(-0) = -0).  minimum / maximum / fmin / fmax of the pair (+0, -0) return the SECOND operand (NumPy's
+// answer there depends on how it was built).  Every value is a Float64 (booleans are 0.0 / 1.0); Float32 closures round
+// with an explicit ROUND32 after each operation, so Float32 results overflow to ±Inf and keep their subnormals as
+// Float32 arithmetic does.  Checked function by function on the device: tests/test_gpu_elementwise_ops.py.
 #pragma once
 
 namespace so {
@@ -32,11 +35,11 @@ SO_MF so_m_square(double x) { return x * x; }
 SO_MF so_m_reciprocal(double x) { return 1.0 / x; }
 SO_MF so_m_exp(double x) { return ::exp(x); }
 SO_MF so_m_exp2(double x) { return ::exp2(x); }
-SO_MF so_m_expm1(double x) { return ::expm1(x); }
+SO_MF so_m_expm1(double x) { return x == 0.0 ? x : ::expm1(x); }  // (the library's expm1(-0) is +0; C99 and NumPy: -0)
 SO_MF so_m_log(double x) { return ::log(x); }
 SO_MF so_m_log2(double x) { return ::log2(x); }
 SO_MF so_m_log10(double x) { return ::log10(x); }
-SO_MF so_m_log1p(double x) { return ::log1p(x); }
+SO_MF so_m_log1p(double x) { return x == 0.0 ? x : ::log1p(x); }  // (as expm1: log1p(-0) = -0)
 SO_MF so_m_sin(double x) { return ::sin(x); }
 SO_MF so_m_cos(double x) { return ::cos(x); }
 SO_MF so_m_tan(double x) { return ::tan(x); }

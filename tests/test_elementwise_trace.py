@@ -13,50 +13,9 @@ import sigops_amd as so
 from sigops_amd import _capi as K
 from sigops_amd import lowering as LW
 from sigops_amd import signals as S
+from eop_ref import run_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UN_NAMES = {v: k for k, v in K.UN.items()}
-BIN_NAMES = {v: k for k, v in K.BIN.items()}
-CMP_NAMES = {v: k for k, v in K.CMP.items()}
-NP_UN = {"neg": np.negative, "abs": np.absolute, "square": np.square, "reciprocal": np.reciprocal}
-NP_BIN = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.true_divide, "pow": np.power}
-NP_CMP = {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal, "eq": np.equal,
-          "ne": np.not_equal}
-
-
-def run_program(code, consts, args):
-    """a NumPy evaluator of the so_eop_t format: every value Float64; an operation followed by ROUND32 is applied in
-    Float32 (what the recorded type says), then widened"""
-    st = []
-    code = [tuple(int(v) for v in row) for row in code]
-    for i, (op, arg) in enumerate(code):
-        f32 = i + 1 < len(code) and code[i + 1][0] == K.EOP["round32"]
-        cast = (lambda v: np.asarray(v, dtype=np.float32)) if f32 else (lambda v: v)
-        with np.errstate(all="ignore"):
-            if op == K.EOP["arg"]:
-                st.append(np.asarray(args[arg], dtype=np.float64))
-            elif op == K.EOP["const"]:
-                st.append(np.full(len(args[0]), consts[arg]))
-            elif op == K.EOP["un"]:
-                n = UN_NAMES[arg]
-                st[-1] = np.asarray(NP_UN.get(n, getattr(np, n, None))(cast(st[-1])), dtype=np.float64)
-            elif op in (K.EOP["bin"], K.EOP["cmp"]):
-                b = st.pop()
-                a = st.pop()
-                fn = NP_CMP[CMP_NAMES[arg]] if op == K.EOP["cmp"] else NP_BIN.get(BIN_NAMES[arg], getattr(np, BIN_NAMES[arg], None))
-                st.append(np.asarray(fn(cast(a), cast(b)), dtype=np.float64))
-            elif op == K.EOP["select"]:
-                b = st.pop()
-                a = st.pop()
-                c = st.pop()
-                st.append(np.where(c != 0, a, b))
-            elif op == K.EOP["round32"]:
-                st[-1] = st[-1].astype(np.float32).astype(np.float64)
-            else:
-                raise AssertionError(f"unknown code {op}")
-    assert len(st) == 1
-    return st[0]
-
 
 def values(rng, n=160):
     special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1.0, -1.0, 0.5, -0.5, 2.0, 1e-300, -3.5])
