@@ -130,14 +130,30 @@ typedef enum so_mapfn {
  *                     false except under SO_CMP_NE
  *   SO_EOP_SELECT     c, a, b -> c != 0 ? a : b, NumPy's `where`
  *   SO_EOP_ROUND32    x -> (double)(float)x
+ *   SO_EOP_INTERP k   x -> np.interp(x, xp, fp, left, right): a look-up table with linear interpolation
+ *                     (breakpoint envelopes, transfer curves, wavetables).  The table lies in the node's
+ *                     constants, k the index of its header: constants[k] = n (the number of knots, an
+ *                     integer value, 1 <= n <= 1048576), constants[k+1] = left, constants[k+2] = right
+ *                     (the values for x < xp[0] and x > xp[n-1]), then xp[0..n) -- strictly increasing,
+ *                     no NaN -- and fp[0..n).  The same layout in all three places a program can sit --
+ *                     SO_MAP_EXPR, SO_RAMP_EXPR and the `Signal(fn)` form (a SO_MAP_EXPR over a FUNC
+ *                     identity node) --: the table is part of p1 and the node's s0 states how many doubles
+ *                     p1 holds (a program without tables may leave s0 = 0).  The result is a Float64 and
+ *                     NumPy's value bit for bit: NaN -> NaN (n = 1: fp[0], as NumPy), x on a knot -> that
+ *                     knot's fp, otherwise slope * (x - xp[j]) + fp[j] with NumPy's fall-backs where that
+ *                     is NaN.  A NumPy `period=` is the host's job: it reduces and sorts xp, adds the two
+ *                     wrap-around knots and emits SO_BIN_REMAINDER in front of the look-up.  The plan
+ *                     copies every table once, at creation, into device memory of its own (counted in
+ *                     so_stats_t.scratch_bytes); an execute copies none.
  * A program must leave exactly one value; the planner rejects stack underflow, argument
- * indexes out of range and unknown codes with SO_ERR_INVALID.  Semantics follow NumPy's
+ * indexes out of range, unknown codes, and a table that is out of range of p1 (s0), has n < 1
+ * or an xp that does not increase, with SO_ERR_INVALID.  Semantics follow NumPy's
  * ufuncs: SO_BIN_MINIMUM / MAXIMUM propagate NaN, SO_BIN_FMIN / FMAX ignore it,
  * SO_BIN_REMAINDER has the sign of the divisor (Python `%`), SO_UN_RINT rounds half to even.
  */
 typedef struct so_eop {
     int32_t code; /* so_eop_code_t        */
-    int32_t arg;  /* argument / constant index or function id */
+    int32_t arg;  /* argument / constant index, function id or table header index */
 } so_eop_t;
 
 typedef enum so_eop_code {
@@ -147,7 +163,8 @@ typedef enum so_eop_code {
     SO_EOP_BIN = 3,
     SO_EOP_CMP = 4,
     SO_EOP_SELECT = 5,
-    SO_EOP_ROUND32 = 6
+    SO_EOP_ROUND32 = 6,
+    SO_EOP_INTERP = 7
 } so_eop_code_t;
 
 typedef enum so_un {
@@ -218,12 +235,13 @@ typedef enum so_rskind {
  *            (max(1,frames), src/ramps.jl:26); child 0 = the signal being ramped
  *            (gives length/nch/dtype); the node's VALUE is the gain
  *            SO_RAMP_EXPR: p0=const so_eop_t* program of one argument (the ramp position),
- *            i2=its length, p1=const double* constants; the gain is fn(x) inside the ramp
- *            and 1 outside it (src/ramps.jl:56-59)
+ *            i2=its length, p1=const double* constants, s0=their number (needed by SO_EOP_INTERP
+ *            only); the gain is fn(x) inside the ramp and 1 outside it (src/ramps.jl:56-59)
  *  MAP       i0=so_mapfn_t  i1=bychannel  i2=so_padkind_t of `padding`  d0=pad value
  *            i3=extra (see so_mapfn_t); children = x.signals (un-extended)
  *            SO_MAP_EXPR: p0=const so_eop_t* program (ARG k = child k), i3=its length,
- *            p1=const double* constants, i1=1 (bychannel; a bychannel=false closure is
+ *            p1=const double* constants, s0=their number (needed by SO_EOP_INTERP only),
+ *            i1=1 (bychannel; a bychannel=false closure is
  *            written as one program per output channel over GETCHAN children, joined by
  *            TUPLECAT); dtype = the closure's result type (Float32 / Float64)
  *  FILT_SOS  i0=nsections  p0=double[6*nsec] rows (b0,b1,b2,a0,a1,a2), a0==1

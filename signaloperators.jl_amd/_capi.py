@@ -17,7 +17,8 @@ RAMPFN = {"sinramp": 0, "identity": 1, "expr": 2}
 MAPFN = {"add": 0, "mul": 1, "sub": 2, "div": 3, "tuplecat": 4, "getchan": 5, "as1channel": 6,
          "asnchannels": 7, "toeltype": 8, "reversech": 9, "expr": 10}
 # expression programs (so_eop_t): opcodes and function ids
-EOP = {"arg": 0, "const": 1, "un": 2, "bin": 3, "cmp": 4, "select": 5, "round32": 6}
+EOP = {"arg": 0, "const": 1, "un": 2, "bin": 3, "cmp": 4, "select": 5, "round32": 6, "interp": 7}
+INTERP_MAX_KNOTS = 1 << 20  # SO_EOP_INTERP: a table's header is (n, left, right) in the constants, then xp[n], fp[n]
 UN = {name: i for i, name in enumerate((
     "neg", "abs", "sqrt", "cbrt", "square", "reciprocal", "exp", "exp2", "expm1", "log", "log2", "log10", "log1p",
     "sin", "cos", "tan", "arcsin", "arccos", "arctan", "sinh", "cosh", "tanh", "arcsinh", "arccosh", "arctanh",

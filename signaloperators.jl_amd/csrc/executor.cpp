@@ -173,6 +173,8 @@ void Plan::finalize() {
         HIPCHECK(hipMalloc(&d_leaves, leaves.size() * sizeof(DLeaf)));
         HIPCHECK(h2d_small(d_leaves, leaves.data(), leaves.size() * sizeof(DLeaf)));
     }
+    for (auto& T : tables)  // SO_EOP_INTERP: the only copy of a table the plan ever makes
+        HIPCHECK(h2d_small(bufs[T.buf].d, T.src, T.ndoubles * 8));
     for (auto& S : stages) {
         if (S.need <= 0) continue;
         if (S.kind == ST_SOS && S.qmat_buf >= 0)

@@ -137,13 +137,18 @@ static __device__ __attribute__((noinline)) double so_cmp_dispatch(int f, double
     }
 }
 
+// (the table look-up of SO_EOP_INTERP: out of line for the same reason -- a search loop per call site otherwise)
+static __device__ __attribute__((noinline)) double so_interp_dispatch(const void* table, double x) {
+    return so_interp((const double*)table, x);
+}
+
 // HEAVY == false drops the generator/ramp opcodes (the planner always hoists them into the
 // per-frame program), so the per-sample interpreter carries no transcendental code.
 // PAIR (E == 2, n[1] == n[0] + 1 for every lane, same parity of n[0] across the wave): array
 // leaves with unit frame stride are read with one 16-byte (fp64) / 8-byte (fp32) load per lane
 // when the pair is naturally aligned -- the widest, best-coalesced form of a streaming read.
 // MATH == true (k_pointwise's separate math instantiation, used only by steps that contain an expression-program
-// operation or a counter-based noise leaf): OP_UN / OP_BIN / OP_CMP / OP_SELECT and OP_FUNC's SO_FN_RANDN as well.  Every other instantiation compiles exactly as before.
+// operation or a counter-based noise leaf): OP_UN / OP_BIN / OP_CMP / OP_SELECT / OP_INTERP and OP_FUNC's SO_FN_RANDN as well.  Every other instantiation compiles exactly as before.
 template <int E, bool CV, int D, bool HEAVY, bool PAIR = false, bool MATH = false>
 __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc, int len,
                                             const DLeaf* __restrict__ leaves,
@@ -280,6 +285,10 @@ __device__ __forceinline__ void run_program(const DOp* __restrict__ ops, int pc,
                                                      : so_cmp_dispatch(op.arg, st[1][e], st[0][e]);
                         SO_POP1()
                     }
+                } else if (op.code == OP_INTERP) {
+                    const void* table = leaves[op.arg].base;  // (wave-uniform)
+#pragma unroll
+                    for (int e = 0; e < E; ++e) st[0][e] = so_interp_dispatch(table, st[0][e]);
                 } else if (op.code == OP_SELECT) {
                     if constexpr (D >= 3) {
 #pragma unroll

@@ -6,13 +6,14 @@
 
 namespace so {
 // Opcodes of the expression-program operations (include/sigops.h so_eop_t) in the fused pointwise programs, next to
-// sigops_internal.h's OpCode; arg = the so_un_t / so_bin_t / so_cmp_t function id.  Only k_pointwise's math
+// sigops_internal.h's OpCode; arg = the so_un_t / so_bin_t / so_cmp_t function id (OP_INTERP: a leaf).  Only k_pointwise's math
 // instantiation (launch_pointwise(..., math = true)) and the hipRTC kernels execute them.
 enum MathOpCode : int32_t {
     OP_UN = 13,     // x -> f(x)
     OP_BIN = 14,    // a, b -> f(a, b)
     OP_CMP = 15,    // a, b -> (a f b) ? 1 : 0
-    OP_SELECT = 16  // c, a, b -> c != 0 ? a : b
+    OP_SELECT = 16, // c, a, b -> c != 0 ? a : b
+    OP_INTERP = 17  // x -> np.interp(x, table); arg = the leaf whose `base` is the table in device memory (kmath.h so_interp)
 };
 void launch_pointwise(const DPiece* d_pieces, int npieces, int64_t nblocks, const DOp* d_ops,
                       const DLeaf* d_leaves, OutView out, bool deep, hipStream_t st, bool chain = false, bool il = false,

@@ -88,6 +88,85 @@ SO_MF so_c_eq(double a, double b) { return a == b ? 1.0 : 0.0; }
 SO_MF so_c_ne(double a, double b) { return a != b ? 1.0 : 0.0; }
 
 SO_MF so_select(double c, double a, double b) { return c != 0.0 ? a : b; }
+
+// SO_EOP_INTERP: NumPy's `np.interp(x, xp, fp, left, right)` over a table `t` in device memory, laid out as the C-ABI
+// lays it into a node's constants (include/sigops.h): t[0] = n, t[1] = left, t[2] = right, then xp[n] (strictly
+// increasing: the planner checks) and fp[n].  The values are NumPy's, operation for operation (arr_interp of
+// numpy/_core/src/multiarray/compiled_base.c): a NaN x is returned as it is (a table of ONE knot has no such rule in
+// NumPy: there a NaN x is neither left nor right of the knot and gives fp[0]); outside the table left / right; on a knot
+// that knot's fp; otherwise slope * (x - xp[j]) + fp[j] with the slope computed per sample, and NumPy's two fall-backs
+// where that is NaN (an infinite fp).
+// The search returns the one j with xp[j] <= x < xp[j + 1] for ANY strictly increasing xp.  It starts from the linear
+// guess (x - xp[0]) * (n - 1) / (xp[n - 1] - xp[0]) -- which only chooses where the search starts: every decision is a
+// comparison against xp --, gallops from there in doubling steps until x is bracketed, then bisects.  A uniform table
+// costs two reads of xp (the guess is the answer or next to it), any other at most ~2 log2 n.  All table reads are plain
+// loads; a table of up to a few megabytes stays in L2.
+SO_MF so_interp(const double* __restrict__ t, double x) {
+    const int n = (int)t[0];
+    const double* __restrict__ xp = t + 3;
+    const double* __restrict__ fp = xp + n;
+    const double x0 = xp[0];
+    if (n == 1) return x < x0 ? t[1] : x > x0 ? t[2] : fp[0];
+    if (x != x) return x;
+    const double xl = xp[n - 1];
+    if (x < x0) return t[1];
+    if (x > xl) return t[2];
+    if (x == xl) return fp[n - 1];
+    // here xp[0] <= x < xp[n - 1]
+    const double g = (x - x0) * (double)(n - 1) / (xl - x0);
+    int lo = g >= 0.0 && g < (double)(n - 1) ? (int)g : g >= (double)(n - 1) ? n - 2 : 0;  // (a NaN guess: 0)
+    int hi;
+    double xlo = xp[lo], xhi = xl;
+    if (xlo <= x) {  // the answer is at lo or above: gallop up until xp[hi] > x (xp[n - 1] is)
+        int step = 1;
+        hi = lo + 1;
+        while (hi < n - 1) {
+            const double v = xp[hi];
+            if (v > x) {
+                xhi = v;
+                break;
+            }
+            lo = hi;
+            xlo = v;
+            step += step;
+            hi = lo + step < n - 1 ? lo + step : n - 1;
+        }
+    } else {  // below lo: gallop down until xp[lo] <= x (xp[0] is)
+        int step = 1;
+        hi = lo;
+        xhi = xlo;
+        lo = hi - 1;
+        for (;;) {
+            xlo = xp[lo];
+            if (xlo <= x) break;
+            hi = lo;
+            xhi = xlo;
+            step += step;
+            lo = hi - step > 0 ? hi - step : 0;
+        }
+    }
+    while (hi - lo > 1) {  // xp[lo] <= x < xp[hi]
+        const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+        const double v = xp[mid];
+        if (v <= x) {
+            lo = mid;
+            xlo = v;
+        } else {
+            hi = mid;
+            xhi = v;
+        }
+    }
+    const double f0 = fp[lo];
+    if (x == xlo) return f0;
+    const double f1 = fp[lo + 1];
+    const double s = (f1 - f0) / (xhi - xlo);
+    double r = s * (x - xlo) + f0;
+    if (r != r) {
+        r = s * (x - xhi) + f1;
+        if (r != r && f0 == f1) r = f0;
+    }
+    return r;
+}
 #undef SO_MF
 
 }  // namespace so

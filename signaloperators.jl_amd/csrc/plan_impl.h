@@ -78,6 +78,7 @@ struct Expr {
     int dtype;
     int a = -1, b = -1, c = -1;  // operands (E_SELECT: a = the condition, b / c = the values)
     int fn = 0;
+    int table = -1;  // E_UN only: >= 0, the table look-up SO_EOP_INTERP of Plan::tables[table] (fn unused; leaf.buf = its device copy)
     DLeaf leaf{};
     int array_node = -1;  // E_LOAD of an ARRAY node (for so_plan_set_array)
     bool mono = true, heavy = false;
@@ -257,6 +258,14 @@ struct RsBatch {
 
 constexpr int kProfExecs = 256;  // executes a deferred-profiling plan keeps events for
 
+// A look-up table of SO_EOP_INTERP: header and knots as they lie in the node's constants (include/sigops.h), copied once
+// into a device buffer of the plan (finalize)
+struct InterpTable {
+    const double* src;  // the node's constants at the table's header
+    size_t ndoubles;    // 3 + 2 n
+    int buf;
+};
+
 struct HostLeaf {
     int node;
     const void* src;
@@ -283,6 +292,7 @@ struct Plan {
     std::vector<DLeaf> leaves;
     std::vector<int> leaf_array_node;  // per leaf: ARRAY node or -1
     std::vector<HostLeaf> host_leaves;
+    std::vector<InterpTable> tables;  // SO_EOP_INTERP tables, one per distinct (constants, header index)
     std::map<int, int> array_buf;  // ARRAY node -> buf id (host arrays: device copy)
     std::map<int, const void*> array_ptr;  // current data pointer per ARRAY node
     DPiece* d_pieces = nullptr;
@@ -375,6 +385,21 @@ struct Plan {
         e.mono = exprs[a].mono && (b < 0 || exprs[b].mono) && (c < 0 || exprs[c].mono);
         e.heavy = true;
         return add_expr(e);
+    }
+    // SO_EOP_INTERP: np.interp(a, table) -- a unary expression-program operation whose function is a table
+    int mk_interp(const double* src, int a) {
+        int ti = -1;
+        for (size_t i = 0; i < tables.size(); ++i)
+            if (tables[i].src == src) ti = (int)i;
+        if (ti < 0) {
+            const size_t nd = 3 + 2 * (size_t)src[0];
+            tables.push_back(InterpTable{src, nd, raw_buf(nd * 8)});
+            ti = (int)tables.size() - 1;
+        }
+        const int e = mk_math(E_UN, 0, a);
+        exprs[e].table = ti;
+        exprs[e].leaf.buf = tables[ti].buf;
+        return e;
     }
     bool has_math(int e) const {
         if (e < 0) return false;

@@ -48,6 +48,24 @@ static void check_program(int node, const so_node_t& nd, const void* p, int len,
             break;
         case SO_EOP_SELECT: need = 3; break;
         case SO_EOP_ROUND32: need = 1; break;
+        case SO_EOP_INTERP: {  // the table in the constants: header (n, left, right), xp[n], fp[n]
+            const double* t = (const double*)nd.p1;
+            const int64_t cap = nd.s0;  // doubles in p1
+            if (!t || o.arg < 0 || cap < 3 || o.arg > cap - 3)
+                fail(SO_ERR_INVALID, at + "table " + std::to_string(o.arg) + " out of range of the constant table (" + std::to_string(cap) + " constants)");
+            const double nn = t[o.arg];
+            if (!(nn >= 1.0)) fail(SO_ERR_INVALID, at + "a table needs at least one knot");
+            if (nn > 1048576.0 || nn != (double)(int64_t)nn) fail(SO_ERR_INVALID, at + "a table has an integer number of knots, 1048576 at most");
+            const int64_t tn = (int64_t)nn;
+            if (o.arg + 3 + 2 * tn > cap)
+                fail(SO_ERR_INVALID, at + "table " + std::to_string(o.arg) + " (" + std::to_string(tn) + " knots) out of range of the constant table (" + std::to_string(cap) + " constants)");
+            const double* xp = t + o.arg + 3;
+            if (xp[0] != xp[0]) fail(SO_ERR_INVALID, at + "NaN in the table's xp");
+            for (int64_t k = 0; k + 1 < tn; ++k)
+                if (!(xp[k] < xp[k + 1])) fail(SO_ERR_INVALID, at + "the table's xp is not strictly increasing (knot " + std::to_string(k + 1) + ")");
+            need = 1;
+            break;
+        }
         default: fail(SO_ERR_INVALID, at + "unknown code " + std::to_string(o.code));
         }
         if (sp < need) fail(SO_ERR_INVALID, at + "stack underflow");
@@ -473,6 +491,7 @@ int Plan::prog_expr(const so_node_t& nd, const so_eop_t* prog, int len, const st
                 st.back() = mk_bin(o.arg == SO_BIN_ADD ? E_ADD : o.arg == SO_BIN_SUB ? E_SUB : o.arg == SO_BIN_MUL ? E_MUL : E_DIV, a, b);
             else st.back() = mk_math(o.code == SO_EOP_BIN ? E_BIN : E_CMP, o.arg, a, b);
             break;
+        case SO_EOP_INTERP: st.back() = mk_interp(consts + o.arg, st.back()); break;
         case SO_EOP_SELECT:
             c = st.back();
             st.pop_back();
@@ -857,7 +876,8 @@ void Plan::gen(int ei, std::vector<DOp>& code, std::map<int, int>& hoisted,
         return;
     case E_UN:
         gen(e.a, code, hoisted, fcode, allow_hoist);
-        code.push_back(DOp{OP_UN, e.fn});
+        if (e.table >= 0) code.push_back(DOp{OP_INTERP, add_leaf(e)});  // (the leaf: the table's device copy)
+        else code.push_back(DOp{OP_UN, e.fn});
         return;
     case E_BIN:
     case E_CMP:

@@ -353,7 +353,8 @@ def lower(x, nframes_out=None, rng=None):
         code, consts = prog
         lw.keep.append(code)
         lw.keep.append(consts)
-        return dict(p0=code.ctypes.data, p1=consts.ctypes.data if consts.size else None), int(code.shape[0])
+        # (s0: how many constants p1 holds -- what the planner checks the tables of SO_EOP_INTERP against)
+        return dict(p0=code.ctypes.data, p1=consts.ctypes.data if consts.size else None, s0=int(consts.size)), int(code.shape[0])
 
     def expr_map(s, kids):
         """an `elementwise` MapSignal: one SO_MAP_EXPR node over the operands (bychannel), or one per output channel

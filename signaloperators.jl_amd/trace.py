@@ -10,6 +10,10 @@ device, once per sample.  The closure itself is never called per sample.
 Rules:
   * recorded: Python's `+ - * / ** %`, unary `-` / `+`, `abs`, `< <= > >= == !=`; the NumPy ufuncs of `UFUNCS`
     (through `__array_ufunc__`); `np.where` and `np.clip` (through `__array_function__`).
+  * recorded: `np.interp(x, xp, fp, left=None, right=None, period=None)` of a traced `x` over concrete tables `xp`, `fp`
+    (a breakpoint envelope, a transfer curve, a wavetable): one SO_EOP_INTERP, the table -- converted to Float64, `xp`
+    strictly increasing -- stored in the program's constants; the result is Float64 as NumPy's is.  `period=` is resolved
+    here as NumPy resolves it (xp reduced, sorted, two wrap-around knots): `remainder`, then the plain look-up.
   * every operation's result type is NumPy's own: the operation is applied to 0-d values of the operand types, with
     the closure's actual constants (so NumPy 2's weak Python scalars promote as on the host path).  A Float32 result
     is followed by an explicit ROUND32; constants enter in the type NumPy computes the operation in.
@@ -24,6 +28,7 @@ import numpy as np
 from . import _capi as K
 
 ARG, CONST, UN, BIN, CMP, SELECT, ROUND32 = (K.EOP[k] for k in ("arg", "const", "un", "bin", "cmp", "select", "round32"))
+INTERP = K.EOP["interp"]
 
 # ufunc -> (kind, function name in _capi's tables); "pos": no operation
 UFUNCS = {
@@ -100,7 +105,8 @@ def _name(f):
 
 class _Tracer:
     def __init__(self):
-        self.nodes = []  # (kind, fn, operands, dtype): kind arg / const / un / bin / cmp / select / pos
+        self.nodes = []  # (kind, fn, operands, dtype): kind arg / const / un / bin / cmp / select / pos / interp
+        self.tables = {}  # np.interp tables: bytes of (left, right, xp, fp) -> Float64 [n, left, right, xp..., fp...]
 
     def add(self, kind, fn, operands, dtype):
         self.nodes.append((kind, fn, tuple(operands), np.dtype(dtype)))
@@ -217,7 +223,16 @@ class Sym:
                 x = x if lo is None else _apply(np.maximum, (x, lo))
                 return x if hi is None else _apply(np.minimum, (x, hi))
             return _apply(np.minimum, (_apply(np.maximum, (x, lo)), hi))
-        _error(f"elementwise: np.{_name(func)} is not traceable (traced: the ufuncs of trace.UFUNCS, np.where, np.clip)")
+        if func is np.interp:
+            names = ("x", "xp", "fp", "left", "right", "period")
+            if len(args) > len(names) or any(k not in names[len(args):] for k in kwargs):
+                _error("elementwise: np.interp takes (x, xp, fp, left=None, right=None, period=None)")
+            a = dict(zip(names, args), **kwargs)
+            if not all(k in a for k in ("x", "xp", "fp")):
+                _error("elementwise: np.interp needs x, xp and fp")
+            return _interp(a["x"], a["xp"], a["fp"], a.get("left"), a.get("right"), a.get("period"))
+        _error(f"elementwise: np.{_name(func)} is not traceable (traced: the ufuncs of trace.UFUNCS, np.where, np.clip, "
+               "np.interp)")
 
     def __repr__(self):
         return f"<traced {self.dtype} value #{self._idx}>"
@@ -291,6 +306,71 @@ def _select(c, a, b):
     return tr.add("select", None, [_operand(tr, c, np.bool_), _operand(tr, a, dt), _operand(tr, b, dt)], dt)
 
 
+def _has_sym(v):
+    if isinstance(v, Sym):
+        return True
+    if isinstance(v, (list, tuple)):
+        return any(_has_sym(e) for e in v)
+    return isinstance(v, np.ndarray) and v.dtype == object and any(_has_sym(e) for e in v.ravel())
+
+
+def _interp(x, xp, fp, left, right, period):
+    """np.interp(x, xp, fp, left, right, period) of a traced x: the table as Float64 in the program's constants"""
+    if _has_sym(xp) or _has_sym(fp):
+        _error("elementwise: np.interp needs concrete tables: xp and fp may not be traced values (a table that is itself "
+               "a signal is not traceable)")
+    for name, v in (("left", left), ("right", right), ("period", period)):
+        if v is not None and not _is_const(v):
+            _error(f"elementwise: np.interp: {name} must be a number or None, not {type(v).__name__}")
+    if not isinstance(x, Sym):
+        _error("elementwise: np.interp: x must be a traced value or a number")
+    tr = x._tr
+    try:
+        xa, fa = np.asarray(xp), np.asarray(fp)
+    except Exception as e:  # noqa: BLE001
+        _error(f"elementwise: np.interp: xp / fp are not numeric sequences: {e}")
+    if np.iscomplexobj(fa):
+        _error("elementwise: np.interp with a complex fp is not traceable (the engine computes real samples)")
+    if xa.dtype.kind not in "fiub" or fa.dtype.kind not in "fiub":
+        _error(f"elementwise: np.interp: xp / fp must be real numbers (got {xa.dtype}, {fa.dtype})")
+    if xa.ndim != 1 or fa.ndim != 1:
+        _error("elementwise: np.interp: xp and fp must be one-dimensional sequences")
+    if xa.shape[0] != fa.shape[0]:
+        _error(f"elementwise: np.interp: xp and fp are not of the same length ({xa.shape[0]} and {fa.shape[0]})")
+    if xa.shape[0] == 0:
+        _error("elementwise: np.interp: the table is empty (n = 0)")
+    xa, fa = xa.astype(np.float64), fa.astype(np.float64)
+    if np.isnan(xa).any():
+        _error("elementwise: np.interp: NaN in xp")
+    if x.dtype.kind not in "fiub":
+        _error(f"elementwise: np.interp of a {x.dtype} value is not traceable")
+    if x.dtype != np.float64:  # NumPy converts x to Float64 first (exact for Float32, booleans and small integers)
+        x = tr.add("pos", None, [x._idx], np.float64)
+    if period is not None:  # NumPy's own normalisation of periodic boundaries (numpy.interp)
+        if period == 0:
+            _error("elementwise: np.interp: period must be a non-zero value")
+        period = abs(float(period))
+        left = right = None
+        x = _apply(np.remainder, (x, period))
+        xa = xa % period
+        order = np.argsort(xa)
+        xa, fa = xa[order], fa[order]
+        xa = np.concatenate((xa[-1:] - period, xa, xa[0:1] + period))
+        fa = np.concatenate((fa[-1:], fa, fa[0:1]))
+    n = xa.shape[0]
+    if n > K.INTERP_MAX_KNOTS:
+        _error(f"elementwise: np.interp: a table of {n} knots is too large (at most {K.INTERP_MAX_KNOTS})")
+    if n > 1 and not (xa[1:] > xa[:-1]).all():
+        _error("elementwise: np.interp: xp must be strictly increasing" + (" (after reduction by the period)" if period else "")
+               + ": a search over an unsorted table has no defined answer")
+    lv = np.float64(fa[0] if left is None else left)
+    rv = np.float64(fa[-1] if right is None else right)
+    table = np.concatenate((np.asarray([n, lv, rv], dtype=np.float64), xa, fa))
+    key = table.tobytes()  # (left / right are part of a table as it is stored)
+    tr.tables.setdefault(key, table)
+    return tr.add("interp", key, [x._idx], np.float64)
+
+
 def _operand(tr, v, cdt):
     """node index of an operand; a constant becomes a constant node of its value in the computing type"""
     if isinstance(v, Sym):
@@ -307,8 +387,10 @@ def _const_node(tr, v):
 
 
 def _emit(tr, out_idx):
-    """postfix program (int32 [n, 2]) and constant table (float64) of node `out_idx`"""
+    """postfix program (int32 [n, 2]) and constant table (float64) of node `out_idx`; the tables of np.interp follow the
+    scalar constants, each stored once (include/sigops.h SO_EOP_INTERP: header n, left, right, then xp[n], fp[n])"""
     code, consts, cidx = [], [], {}
+    tables = []  # keys in order of first use; an INTERP's arg is the table's number until the offsets are known
 
     def const(v):
         key = np.float64(v).tobytes()
@@ -335,12 +417,22 @@ def _emit(tr, out_idx):
             code.append((CMP, K.CMP[fn]))
         elif kind == "select":
             code.append((SELECT, 0))
+        elif kind == "interp":
+            if fn not in tables:
+                tables.append(fn)
+            code.append((INTERP, tables.index(fn)))
         # ("pos": a change of type only)
         if dt == np.float32 and kind != "cmp":
             code.append((ROUND32, 0))  # Float32 arithmetic: every operation rounds
 
     rec(out_idx)
-    return np.ascontiguousarray(np.asarray(code, dtype=np.int32).reshape(-1, 2)), np.asarray(consts, dtype=np.float64)
+    parts, offs, at = [np.asarray(consts, dtype=np.float64)], [], len(consts)
+    for key in tables:
+        offs.append(at)
+        parts.append(tr.tables[key])
+        at += tr.tables[key].size
+    code = [(c, offs[a]) if c == INTERP else (c, a) for c, a in code]
+    return np.ascontiguousarray(np.asarray(code, dtype=np.int32).reshape(-1, 2)), np.concatenate(parts)
 
 
 def _trace_once(fn, dtypes, bychannel, nch):

@@ -19,6 +19,14 @@ y = torch.randn((nch, n), dtype=TDT, device="cuda").t()
 z = torch.randn((nch, n // 2), dtype=TDT, device="cuda").t()
 X, Y, Z = so.Signal(x, fs), so.Signal(y, fs), so.Signal(z, fs)
 tone = so.Signal(so.sin, ω=1 * so.kHz)
+
+
+def INTERP_TABLE(kn, kind):
+    r = np.random.default_rng(kn)
+    xp = np.linspace(-4.0, 4.0, kn) if kind == "uniform" else np.sort(r.uniform(-4.0, 4.0, kn))
+    return xp, r.standard_normal(kn)
+
+
 cases = {
     "copy (Until)": lambda: X | so.Until(n * so.frames),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
@@ -55,6 +63,10 @@ cases = {
     "closure hypot(x, y)": lambda: so.OperateOn(so.elementwise(lambda a, b: np.hypot(a, b)), X, Y),
     "Amplify(closure exp(-t/2))": lambda: so.Amplify(X, so.Signal(so.elementwise(lambda t: np.exp(-0.5 * t)), fs)) | so.Until(n * so.frames),
     "RampOn 1 s closure u^2": lambda: X | so.RampOn(1 * so.s, so.elementwise(lambda u: u ** 2)),
+    # look-up tables (`np.interp` in a closure, include/sigops.h SO_EOP_INTERP): 17 / 1 024 / 65 536 knots over [-4, 4],
+    # uniform (the search's first guess is the answer) and random (gallop + bisection); the yardstick is the tanh row above
+    **{f"closure interp {kn} {kind}": (lambda t=INTERP_TABLE(kn, kind): so.OperateOn(so.elementwise(lambda a: np.interp(a, *t)), X))
+       for kn in (17, 1024, 65536) for kind in ("uniform", "random")},
     # counter-based device noise (`Signal(randn, rng=so.DeviceRNG(...))`, csrc/krand.h): the fill kernel, the same leaf as
     # an expression (hipRTC, K1's math instantiation: `case_env`), replicated to the channels, and the headline's tree
     # with the noise in place of its array leaf next to the array-leaf form (FRAMES=26.46e6 for the headline's own size)
