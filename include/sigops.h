@@ -81,7 +81,8 @@ typedef enum so_kind {
     SO_NODE_MAP = 8,      /* MapSignal / OperateOn           src/mapsignal.jl:8-30,131-272 */
     SO_NODE_FILT_SOS = 9, /* FilteredSignal, IIR DF2T SOS    src/filters.jl:98-262         */
     SO_NODE_RESAMPLE = 10,/* FilteredSignal{..ResamplerFn}   src/reformatting.jl:92-122    */
-    SO_NODE_NORMPOWER = 11/* NormedSignal                    src/filters.jl:266-314        */
+    SO_NODE_NORMPOWER = 11,/* NormedSignal                   src/filters.jl:266-314        */
+    SO_NODE_SAMPLEAT = 12 /* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -250,6 +251,14 @@ typedef enum so_rskind {
  *            p0=double[hlen] = resample_filter(ratio) taps   i2=hlen  i3=blocksize
  *            fs = NEW frame rate; child fs = old frame rate
  *  NORMPOWER child 0
+ *  SAMPLEAT  children = (x, pos): the table x -- finite, at least one frame, Float32 / Float64 -- read at the
+ *            positions pos gives (frames of x, 0-based; Float32 / Float64; 1 channel, broadcast, or x's count)
+ *            with linear interpolation.  i0: bit 0 = relative (the position of frame n is n + pos[n]), bit 1 =
+ *            wrap (positions are taken modulo nframes(x); d0 / d1 ignored)   d0=left d1=right (the values
+ *            before frame 0 and past the last frame of x).  The node has pos's length and frame rate, x's
+ *            channels, and is Float64: frame n, channel c is NumPy's np.interp(p, arange(N), x[:, c], left,
+ *            right) -- np.interp(p, arange(N), x[:, c], period=N) under wrap -- bit for bit (DESIGN.md,
+ *            "SampleAt").  One child or three, or a pos of another channel count, is SO_ERR_INVALID.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

@@ -69,6 +69,7 @@ void Plan::finalize() {
             if (car_has_arr2(c)) stage_host_array(c.array_node2);
         }
         stage_host_array(S.in_array_node);
+        stage_host_array(S.pos_array_node);
     }
     if (!out.is_device && out.nframes > 0) {
         Buf b;
@@ -257,8 +258,9 @@ void Plan::finalize() {
             continue;
         }
         if (S.pw_step >= 0) push_pw_step(S.pw_step);
+        if (S.pos_pw_step >= 0) push_pw_step(S.pos_pw_step);
         if (S.fused_away) continue;  // (runs inside its consumer's launch)
-        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : "k_sumsq";
+        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : "k_sumsq";
         Step st{1, sid, nm, 0};
         // algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a
         // Float64 map is 4 bytes a sample, whatever the node's promoted type) plus the samples it writes in the type of
@@ -273,6 +275,8 @@ void Plan::finalize() {
         if (S.kind == ST_SOS && S.rsos_src >= 0) st.bytes = (S.rs.n_in * src_esz(stages[S.rsos_src]) * (S.rs.arr2 ? 2 : 1) + S.rs.n_out * osz) * S.rs.nch;  // (arr2: a second array read)
         else if (S.kind == ST_SOS) st.bytes = (S.need - S.base) * S.sg.nch * (esz + osz);
         else if (S.kind == ST_RESAMPLE) st.bytes = (S.rg.n_in * (src_esz(S) + (S.rp.arr2 ? src_esz(S) : 0)) + S.rg.n_out * osz) * S.rg.nch;  // (arr2: a second array of the source's type read)
+        else if (S.kind == ST_SAMPLEAT)  // per frame: a position read, two table samples read where they lie, a Float64 written
+            st.bytes = (S.need - S.base) * ((int64_t)nodes[nodes[S.node].kids[1]].nch * 8 + (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8));
         else st.bytes = (S.need - S.base) * nodes[S.node].nch * esz;
         steps.push_back(st);
     }
@@ -347,6 +351,7 @@ void Plan::plan_lanes() {
         } else {
             const Stage& S = stages[st.idx];
             if (S.in_buf >= 0 && S.rsos_src < 0) rd[i].insert(S.in_buf);
+            if (S.pos_buf >= 0) rd[i].insert(S.pos_buf);
             carrier_reads(S.rsos_src >= 0 ? stages[S.rsos_src].carriers : S.carriers, rd[i]);
             if (S.win_off >= 0) wr[i].insert(-100 - st.idx);  // its own window of the result
             else wr[i].insert(st.idx == alias_stage ? kFinal : S.out_buf);
@@ -684,6 +689,61 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                     fail(SO_ERR_RUNTIME, "internal: no batched one-pass IIR instantiation for this geometry");
                 int nl = 1;
                 if (poison) nl += launch_rsos_fixup_batch((const RsFixup*)P->bufs[B.fix_buf].d, (int)nm, maxch, out_f32, st);
+                s.launches = nl;
+                launches += nl;
+            } else if (P->stages[s.idx].kind == ST_SAMPLEAT) {
+                const Stage& S = P->stages[s.idx];
+                const Node& N = P->nodes[S.node];
+                auto array_base = [&](int an) {
+                    return P->nodes[an].nd.i0 ? (const char*)P->array_ptr[an] : (const char*)P->bufs[P->array_buf[an]].d;
+                };
+                SampleAtArgs a{};
+                const int xdt = P->nodes[N.kids[0]].dtype;
+                if (S.in_array_node >= 0) {  // the table where it lies
+                    a.x = array_base(S.in_array_node) + (size_t)S.in_offset * dsize(xdt);
+                    a.xcs = N.nch == 1 ? 0 : S.in_pitch;
+                } else {
+                    const Buf& b = P->bufs[S.in_buf];
+                    a.x = (const char*)b.d + (size_t)(S.in_offset - b.frame0) * dsize(xdt);
+                    a.xcs = b.pitch;
+                }
+                a.xfs = S.x_fstride;
+                a.N = S.in_frames;
+                a.x_f32 = xdt == SO_F32;
+                if (S.pos_array_node >= 0) {
+                    a.pos = (const double*)array_base(S.pos_array_node) + S.pos_offset;
+                    a.pcs = S.pos_pitch;
+                } else {
+                    const Buf& b = P->bufs[S.pos_buf];
+                    a.pos = (const double*)b.d;
+                    a.pcs = S.pos_pitch == 0 ? 0 : b.pitch;
+                }
+                Buf ob = P->bufs[S.out_buf];
+                if ((int)s.idx == P->alias_stage) {  // write the sink buffer directly
+                    if (P->out.is_device) {
+                        ob.d = outp;
+                        ob.pitch = N.nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
+                    } else {
+                        ob.d = P->bufs[P->out_stage_buf].d;
+                        ob.pitch = P->bufs[P->out_stage_buf].pitch;
+                    }
+                    ob.d = (char*)ob.d - (size_t)P->alias_skip * 8;
+                } else if (S.win_off >= 0) {  // ... or its window of it
+                    const Buf& ab = P->bufs[P->out_alias_buf];
+                    ob.d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * 8;
+                    ob.pitch = ab.pitch;
+                }
+                a.y = (double*)ob.d;
+                a.ycs = ob.pitch;
+                a.base = S.base;
+                a.n = S.need - S.base;
+                a.left = N.nd.d0;
+                a.right = N.nd.d1;
+                a.nch = N.nch;
+                a.relative = N.nd.i0 & 1;
+                a.wrap = (N.nd.i0 >> 1) & 1;
+                const int nl = launch_sample_at(a, st);
+                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "SampleAt: more than 65535 channels or 2^39 frames are not lowered");
                 s.launches = nl;
                 launches += nl;
             } else {

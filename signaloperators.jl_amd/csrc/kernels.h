@@ -88,4 +88,19 @@ size_t rsos_lds_bytes(int ngroups, int ks, int rpitch, int nwaves, int cyc);
 size_t rsos_lds_budget();
 void launch_rms(const void* x, int dtype, int64_t n, int nch, int64_t pitch, double* partial,
                 int nparts, double* rms, hipStream_t st, const RmsPatch& patch = RmsPatch{});
+// SampleAt (k_sample_at.hip, -ffp-contract=off): y[i, c] = the table x read at pos[i, c] (+ base + i where `relative`),
+// i in [0, n) the frames of the stage's buffer, base the absolute frame of i = 0.  Strides in elements; pcs = 0: one row of
+// positions for every channel.  Returns the number of launches, -1 when the shape cannot be launched.
+struct SampleAtArgs {
+    const void* x;      // the table: N frames, element (j, c) at x[j * xfs + c * xcs]
+    int64_t xfs, xcs, N;
+    const double* pos;  // pos[i + c * pcs]
+    int64_t pcs;
+    double* y;          // y[i + c * ycs]
+    int64_t ycs;
+    int64_t base, n;
+    double left, right;
+    int32_t nch, x_f32, relative, wrap;
+};
+int launch_sample_at(const SampleAtArgs& a, hipStream_t st);
 }  // namespace so

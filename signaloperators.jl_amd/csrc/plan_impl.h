@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -127,6 +127,10 @@ struct Stage {
     int64_t in_offset = 0;  // elements (direct)
     int64_t in_pitch = 0, in_frames = 0;
     int pw_step = -1;  // pointwise step materialising the input
+    // SampleAt: the input above is the table x (all of it); this second one the positions of the frames [base, need)
+    int pos_buf = -1, pos_array_node = -1, pos_pw_step = -1;
+    int64_t pos_offset = 0, pos_pitch = 0;  // elements (an array read in place); pos_pitch 0: one row for every channel
+    int64_t x_fstride = 1;                  // the table's frame stride where it lies (an interleaved array is read in place too)
     std::vector<DCarrier> carriers;  // periodic resampler: input expressed as carriers
     int car_buf = -1;
     int ctl_buf = -1;  // device copy of the RsCtl control block
@@ -464,6 +468,7 @@ struct Plan {
     int dry = 0;  // > 0: lower() only looks for the errors evaluating those frames raises (no stages, no buffers)
     void check_frames(int ni, int64_t upto);
     void process_stage(int sid);
+    void process_sample_at(int sid);
     int emit_pointwise(const std::vector<Piece>& ps, int out_buf, int out_dtype);
     // a piece of the fill form: the noise leaf's expression, the constant factor's (or -1), kFillRound* flags
     struct RandnFill { int noise = -1, scale = -1, flags = 0; };

@@ -248,6 +248,24 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = float_of(c.dtype);
             break;
         }
+        case SO_NODE_SAMPLEAT: {  // x read at the positions pos gives (no reference counterpart; DESIGN.md "SampleAt")
+            const std::string where = "node " + std::to_string(i) + ": SampleAt ";
+            if (N.kids.size() != 2) fail(SO_ERR_INVALID, where + "takes two children, the table x and the positions pos (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            Node& pos = kid(1);
+            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a table x of known, finite length (use `Until`)");
+            if (x.len.n < 1) fail(SO_ERR_LENGTH, where + "needs a table x of at least one frame");
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 table x (integer sample types are not lowered)");
+            if (pos.dtype != SO_F32 && pos.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "takes Float32 or Float64 positions");
+            if (pos.nch != 1 && pos.nch != x.nch)
+                fail(SO_ERR_INVALID, where + "positions have " + std::to_string(pos.nch) + " channels: 1 or the table's " + std::to_string(x.nch) + " expected");
+            if (nd.i0 & ~3) fail(SO_ERR_INVALID, where + "unknown flags " + std::to_string(nd.i0));
+            N.len = pos.len;
+            N.nch = x.nch;
+            N.dtype = SO_F64;
+            if (pos.short_skip) N.short_skip = pos.short_skip;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -813,6 +831,31 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         out.push_back({r, le});
         return out;
     }
+    case SO_NODE_SAMPLEAT: {
+        // a stage: the table below it is materialised whole (or read in place), the positions over the frames anybody
+        // reads; the result is a plain buffer for whoever consumes it (process_sample_at, stages.cpp)
+        const Node& X = nodes[N.kids[0]];
+        if (dry) {
+            check_frames(N.kids[0], X.len.n);
+            check_frames(N.kids[1], m.sf ? r.b + m.df : m.df + 1);
+            out.push_back({r, mk_const(0.0, N.dtype)});
+            return out;
+        }
+        const int sid = stage_for(ni, ST_SAMPLEAT);
+        use_stage(stages[sid], r, m);
+        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
+        Expr e;
+        e.op = E_LOAD;
+        e.dtype = N.dtype;
+        e.leaf = mk_leafmap(m);
+        e.leaf.fstride = 1;
+        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
+        e.leaf.dtype = N.dtype;
+        e.leaf.buf = stages[sid].out_buf;
+        e.mono = (m.sc == 0);
+        out.push_back({r, add_expr(e)});
+        return out;
+    }
     }
     fail(SO_ERR_INVALID, "unknown node kind");
 }
@@ -1352,7 +1395,7 @@ void Plan::try_window_alias(std::vector<Piece>& rootp) {
         for (auto& L : leaves)
             if (L.buf == b) other = true;
         for (auto& S2 : stages) {
-            if (S2.in_buf == b) other = true;
+            if (S2.in_buf == b || S2.pos_buf == b) other = true;
             for (auto& c : S2.carriers)
                 if (c.buf == b) other = true;
         }
@@ -1482,7 +1525,7 @@ Plan* plan_create(const so_node_t* nodes, int32_t n_nodes, int32_t root, const s
                         if (L.buf == e.leaf.buf) P->alias_stage = -1;
                 if (P->alias_stage >= 0)
                     for (auto& S : P->stages)
-                        if (S.in_buf == e.leaf.buf) P->alias_stage = -1;
+                        if (S.in_buf == e.leaf.buf || S.pos_buf == e.leaf.buf) P->alias_stage = -1;
             }
         }
         const auto t_stg = std::chrono::steady_clock::now();

@@ -356,8 +356,75 @@ void Plan::sos_chunking(int sid, int64_t need, int nch, int dtype, const std::ve
     stages[sid].sg = g;
 }
 
+// SampleAt: the table x whole -- an array (any strides) or a stage buffer read where it lies, anything else materialised
+// by one pointwise step -- and the positions of the frames [base, need) anybody reads: a Float64 array with unit frame
+// stride read in place, anything else (a formula, a Float32 array, another stage's buffer) one pointwise step into a
+// Float64 buffer.  The kernel is pointwise in the frame, so a window computes its own range with absolute frame numbers.
+void Plan::process_sample_at(int sid) {
+    const int ni = stages[sid].node;
+    const int xk = nodes[ni].kids[0], pk = nodes[ni].kids[1];
+    const int nch = nodes[ni].nch, pch = nodes[pk].nch, xdt = nodes[xk].dtype;
+    const int64_t Nx = nodes[xk].len.n;
+    const int64_t need = stages[sid].need;
+    stages[sid].processed = true;
+    if (need <= 0) return;
+    const int64_t base = stages[sid].lo < need ? stages[sid].lo : 0;
+    stages[sid].base = stages[sid].in_base = base;
+    bufs[stages[sid].out_buf].frame0 = base;
+    if (base > 0) check_frames(pk, base);
+    auto plain = [&](const std::vector<Piece>& ps, int dtype, bool unit_stride) {
+        if (ps.size() != 1) return false;
+        const Expr& e = exprs[ps[0].e];
+        return e.op == E_LOAD && e.leaf.mode == LM_PLAIN && e.leaf.sf == 1 && e.leaf.sc == 1 && e.leaf.dtype == dtype && e.leaf.df >= 0 &&
+               e.leaf.dc >= 0 && (!unit_stride || e.leaf.fstride == 1) && e.leaf.fstride >= 1 &&
+               (e.leaf.cstride > 0 || (e.leaf.cstride == -1 && e.array_node < 0 && e.leaf.dc == 0) || ps[0].r.c1 - ps[0].r.c0 == 1);
+    };
+    {
+        const std::vector<Piece> ps = lower(xk, Rect{0, Nx, 0, nch}, Map{1, 0, 1, 0});
+        Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
+        S.in_frames = Nx;
+        if (plain(ps, xdt, false)) {
+            const Expr& e = exprs[ps[0].e];
+            S.in_array_node = e.array_node;
+            S.in_buf = e.array_node >= 0 ? -1 : e.leaf.buf;
+            S.x_fstride = e.leaf.fstride;
+            S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
+            S.in_offset = e.leaf.df * e.leaf.fstride + (e.array_node >= 0 ? e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0) : 0);
+            if (e.array_node >= 0) count_array(e.array_node);
+        } else {
+            const int b = new_buf(Nx, nch, xdt);
+            const int step = emit_pointwise(ps, b, xdt);
+            Stage& S2 = stages[sid];
+            S2.in_buf = b;
+            S2.in_pitch = -1;
+            S2.in_offset = 0;
+            S2.pw_step = step;
+        }
+    }
+    {
+        const std::vector<Piece> ps = lower(pk, Rect{0, need - base, 0, pch}, Map{1, base, 1, 0});
+        Stage& S = stages[sid];
+        if (plain(ps, SO_F64, true) && exprs[ps[0].e].array_node >= 0) {
+            const Expr& e = exprs[ps[0].e];
+            S.pos_array_node = e.array_node;
+            S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
+            S.pos_offset = e.leaf.df + e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0);
+            count_array(e.array_node);
+        } else {
+            const int b = new_buf(need - base, pch, SO_F64);
+            const int step = emit_pointwise(ps, b, SO_F64);
+            Stage& S2 = stages[sid];
+            S2.pos_buf = b;
+            S2.pos_pitch = pch == 1 ? 0 : -1;  // -1: pitch of pos_buf
+            S2.pos_offset = 0;
+            S2.pos_pw_step = step;
+        }
+    }
+}
+
 void Plan::process_stage(int sid) {
     // NOTE: `stages` may grow while lowering the child; re-take references after.
+    if (stages[sid].kind == ST_SAMPLEAT) return process_sample_at(sid);
     int ni = stages[sid].node;
     Node& N = nodes[ni];
     const so_node_t& nd = N.nd;

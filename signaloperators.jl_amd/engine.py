@@ -418,6 +418,9 @@ def _streamable(x):
                 "stream does not know yet; not streamable")
     if isinstance(x, S.PaddedSignal) and any(x.pad is p for p in (S.lastframe, S.cycle, S.mirror)):  # (identity: a pad may be an ndarray)
         S.error("BlockStream: lastframe / cycle / mirror padding indexes the end of the input; not streamable")
+    if isinstance(x, S.SampleAtSignal):
+        S.error("BlockStream: SampleAt reads its table at any position, and a stream keeps only a tail of its input "
+                "resident; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -253,6 +253,10 @@ def _demand(x, n, out, skip=0):
         _demand(x.signal, capped(x.signal, m), out, 0)
     elif isinstance(x, S.NormedSignal):
         _demand(x.signal, S.nframes(x.signal), out, 0)
+    elif isinstance(x, S.SampleAtSignal):
+        # the table whole (any frame of it may be read), the positions for the frames the sink reaches
+        _demand(x.signal, S.nframes(x.signal), out, 0)
+        _demand(x.pos, capped(x.pos, n), out, skip)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -534,6 +538,11 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_NORMPOWER)
             r.update(children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.SampleAtSignal):
+            kids = (rec(s.signal), rec(s.pos))
+            r = common(s, K.NODE_SAMPLEAT)
+            r.update(i0=(1 if s.relative else 0) | (2 if s.wrap else 0), d0=s.left, d1=s.right, children=kids)
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

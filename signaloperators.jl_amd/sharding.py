@@ -28,8 +28,17 @@ def block_range(n, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def _refuse_sample_at(x, what):
+    """a tree with a SampleAt node is not sharded: every rank would need the whole table, and that is not built"""
+    if isinstance(x, S.SampleAtSignal):
+        raise S.ErrorException(f"{what}: sharding a tree that contains SampleAt over several GPUs is not built")
+    for c in getattr(x, "children", ()) or ():
+        _refuse_sample_at(c, what)
+
+
 def shard_append(x, rank, world):
     """-> (sub-signal for this rank or None, first output frame, number of frames)"""
+    _refuse_sample_at(x, "shard_append")
     if not isinstance(x, S.AppendSignals):
         raise S.ErrorException("shard_append needs an Append(...) root")
     kids = x.signals
@@ -51,6 +60,7 @@ def shard_time(x, rank, world, align=1):
     from .units import frames
 
     x = S._assignal(x)
+    _refuse_sample_at(x, "shard_time")
     n = S.nframes(x)
     if n is None or S.isknowninf(n):
         raise S.ErrorException("shard_time needs a signal of known, finite length")
@@ -67,6 +77,7 @@ def shard_time(x, rank, world, align=1):
 def shard_channels(x, rank, world):
     """channel slab [c0,c1) of a signal whose channels are independent"""
     x = S._assignal(x)
+    _refuse_sample_at(x, "shard_channels")
     c0, c1 = block_range(x.nch, rank, world)
     if c1 <= c0:
         return None, c0, c1

@@ -508,6 +508,32 @@ class FilteredSignal(WrappedSignal):
         return self.signal.duration()
 
 
+class SampleAtSignal(AbstractSignal):
+    """`SampleAt(x, pos)`: the table `x` read at the positions the signal `pos` gives, with linear interpolation (no
+    reference counterpart; include/sigops.h SO_NODE_SAMPLEAT, DESIGN.md "SampleAt").  It has the length and frame rate
+    of `pos`, the channels of `x`, and is Float64 like `np.interp`."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x, pos, left=0.0, right=0.0, relative=False, wrap=False):
+        self.signal = x
+        self.pos = pos
+        self.children = (x, pos)
+        self.left = float(left)
+        self.right = float(right)
+        self.relative = bool(relative)
+        self.wrap = bool(wrap)
+        self.fs = pos.fs
+        self.nch = x.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.pos.nframes_helper()
+
+    def duration(self):
+        return self.pos.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -865,6 +891,12 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known and x.fs != x.signal.fs:
             return _resample(x.signal, fs, bs)
         return FilteredSignal(ToFramerate(x.signal, fs, bs), x.fn, x.blocksize, fs)
+    if isinstance(x, SampleAtSignal):
+        # a rate the positions do not have yet is theirs to take (never the table's: it is a table of frames, its own
+        # rate is not consulted); a result that has a rate is resampled like any computed signal
+        if known:
+            return _resample(x, fs, bs)
+        return SampleAtSignal(x.signal, ToFramerate(x.pos, fs, bs), x.left, x.right, x.relative, x.wrap)
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -971,6 +1003,85 @@ def SelectChannel(x, n=None):  # src/mapsignal.jl:388-391
         return Curried(lambda y: SelectChannel(y, k))
     x = _assignal(x)
     return _OperateOn(GETCHAN, [x], bychannel=False, extra=int(n))
+
+
+# --------------------------------------------------------------------------
+# SampleAt / Delay: a signal read at computed positions (no reference counterpart)
+def _real_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _SampleAt(x, pos, left=0.0, right=0.0, relative=False, wrap=False):
+    x = _assignal(x)
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error("SampleAt: the table x must have a known, finite length (use `Until`)")
+    if n < 1:
+        error("SampleAt: the table x must have at least one frame")
+    if x.dtype not in (F32, F64):
+        error("SampleAt: the table x must be Float32 or Float64 (use `ToEltype`)")
+    for name, v in (("left", left), ("right", right)):
+        if not _real_number(v):
+            error(f"SampleAt: {name} must be a number, not {v!r}")
+    if _real_number(pos):
+        pos = NumberSig(float(pos))
+    pos = _assignal(pos)
+    if pos.dtype not in (F32, F64):
+        error("SampleAt: the positions must be Float32 or Float64 (use `ToEltype`)")
+    if pos.nch not in (1, x.nch):
+        error(f"SampleAt: the positions have {pos.nch} channels; 1 or the table's {x.nch} expected")
+    return SampleAtSignal(x, pos, left, right, relative, wrap)
+
+
+def SampleAt(*args, left=0.0, right=0.0, relative=False, wrap=False):
+    """`SampleAt(x, pos)`, curried `x | SampleAt(pos)`: frame n, channel c of the result is
+    `np.interp(p, arange(N), x[:, c], left, right)` -- `np.interp(p, arange(N), x[:, c], period=N)` with `wrap` -- at
+    `p = pos[n, c]` (`n + pos[n, c]` with `relative`): positions count the frames of `x` from 0."""
+    kw = dict(left=left, right=right, relative=relative, wrap=wrap)
+    if len(args) == 1:
+        pos = args[0]
+        return Curried(lambda x: _SampleAt(x, pos, **kw))
+    if len(args) != 2:
+        error("SampleAt(x, pos) expected")
+    return _SampleAt(args[0], args[1], **kw)
+
+
+def _Delay(x, d):
+    from .units import frames
+
+    x = _assignal(x)
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error("Delay: SampleAt needs a signal x of known, finite length (use `Until`)")
+    if isinstance(d, Quantity):
+        if U.is_time(d):
+            if x.fs is None:
+                error("Delay: a delay given as a time needs the frame rate of x")
+            d = U.inseconds_raw(d) * x.fs
+        elif U.is_frames(d):
+            d = d.value
+        else:
+            error(f"Delay: {d} is neither a time nor a number of frames")
+    if _real_number(d):
+        pos = NumberSig(-float(d), x.fs)
+    else:
+        d = _assignal(d)
+        if x.fs is not None:
+            d = ToFramerate(d, x.fs)
+        pos = _OperateOn(SUB, [d])
+    y = _SampleAt(x, pos, relative=True)
+    return _Until(_Pad(y, zero), n * frames)
+
+
+def Delay(*args):
+    """`Delay(x, d)`, curried `x | Delay(d)`: `x` delayed by `d` frames (a number or a signal; a time quantity is
+    converted with the rate of `x`), zeros before its first frame: `SampleAt(x, -d, relative=True)` over the frames of `x`."""
+    if len(args) == 1:
+        d = args[0]
+        return Curried(lambda x: _Delay(x, d))
+    if len(args) != 2:
+        error("Delay(x, d) expected")
+    return _Delay(args[0], args[1])
 
 
 # --------------------------------------------------------------------------

@@ -27,6 +27,22 @@ def INTERP_TABLE(kn, kind):
     return xp, r.standard_normal(kn)
 
 
+def POS(kind):
+    """device-resident Float64 positions for the `sampleat` rows, n x nch (one row of positions per channel, so that a row
+    streams what `Mix(x, y)` streams: two reads and one write per sample)"""
+    p = torch.empty((nch, n), dtype=torch.float64, device="cuda")
+    t = torch.arange(n, dtype=torch.float64, device="cuda")
+    if kind == "identity":  # relative, a zero offset: every lane reads its own frame
+        p.zero_()
+    elif kind == "vibrato":  # relative: a delay of 1 .. 9 frames that moves at 0.5 Hz
+        p[:] = -(5.0 + 4.0 * torch.sin(t * (2.0 * np.pi * 0.5 / 44100.0)))
+    elif kind == "random":  # uniform over the whole table
+        p.uniform_(0.0, float(n - 1))
+    else:  # a wavetable of 2048 frames read at 1.37 frames per frame, a different phase per channel
+        p[:] = t * 1.37 + 17.0 * torch.arange(nch, dtype=torch.float64, device="cuda").reshape(-1, 1)
+    return so.Signal(p.t(), fs)
+
+
 cases = {
     "copy (Until)": lambda: X | so.Until(n * so.frames),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
@@ -67,6 +83,12 @@ cases = {
     # uniform (the search's first guess is the answer) and random (gallop + bisection); the yardstick is the tanh row above
     **{f"closure interp {kn} {kind}": (lambda t=INTERP_TABLE(kn, kind): so.OperateOn(so.elementwise(lambda a: np.interp(a, *t)), X))
        for kn in (17, 1024, 65536) for kind in ("uniform", "random")},
+    # `SampleAt(x, pos)` (include/sigops.h SO_NODE_SAMPLEAT, csrc/k_sample_at.hip): the table read at device-resident
+    # positions; the yardstick is the `Mix(x, y)` row above, which streams the same bytes
+    "sampleat identity": lambda: so.SampleAt(X, POS("identity"), relative=True),
+    "sampleat vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True),
+    "sampleat random": lambda: so.SampleAt(X, POS("random")),
+    "sampleat wrap 2048": lambda: so.SampleAt(so.Signal(x[:2048], fs), POS("wavetable"), wrap=True),
     # counter-based device noise (`Signal(randn, rng=so.DeviceRNG(...))`, csrc/krand.h): the fill kernel, the same leaf as
     # an expression (hipRTC, K1's math instantiation: `case_env`), replicated to the channels, and the headline's tree
     # with the noise in place of its array leaf next to the array-leaf form (FRAMES=26.46e6 for the headline's own size)
