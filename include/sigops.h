@@ -82,7 +82,8 @@ typedef enum so_kind {
     SO_NODE_FILT_SOS = 9, /* FilteredSignal, IIR DF2T SOS    src/filters.jl:98-262         */
     SO_NODE_RESAMPLE = 10,/* FilteredSignal{..ResamplerFn}   src/reformatting.jl:92-122    */
     SO_NODE_NORMPOWER = 11,/* NormedSignal                   src/filters.jl:266-314        */
-    SO_NODE_SAMPLEAT = 12 /* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
+    SO_NODE_SAMPLEAT = 12,/* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
+    SO_NODE_COMB = 13     /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -259,6 +260,16 @@ typedef enum so_rskind {
  *            channels, and is Float64: frame n, channel c is NumPy's np.interp(p, arange(N), x[:, c], left,
  *            right) -- np.interp(p, arange(N), x[:, c], period=N) under wrap -- bit for bit (DESIGN.md,
  *            "SampleAt").  One child or three, or a pos of another channel count, is SO_ERR_INVALID.
+ *  COMB      child 0 = x (finite, Float32 / Float64)   l0 = D >= 1, the delay in frames   d0=b0 d1=bD d2=a (finite).
+ *            Per channel, with xd = x[n-D] and yd = y[n-D] where n >= D and +0.0 before that,
+ *                y[n] = (b0 * x[n] + bD * xd) + a * yd
+ *            every product and every sum rounded on its own in Float64 (a Float32 x is widened on load, exactly); a
+ *            term whose coefficient is exactly 0.0 is left out -- neither multiplied nor added -- so bD == 0 gives
+ *            b0 * x[n] + a * yd, a == 0 gives b0 * x[n] + bD * xd, both give b0 * x[n].  The node has x's length, frame
+ *            rate and channels and is Float64; the result equals a sequential loop bit for bit ("Comb").
+ *            Comb(x, d, g): b0 = direct (1), bD = feedforward (0), a = g.  Allpass(x, d, g): b0 = -g, bD = 1, a = g.
+ *            Not exactly one child, l0 < 1 or a non-finite coefficient is SO_ERR_INVALID; an infinite child
+ *            SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

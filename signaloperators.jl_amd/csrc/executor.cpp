@@ -260,7 +260,7 @@ void Plan::finalize() {
         if (S.pw_step >= 0) push_pw_step(S.pw_step);
         if (S.pos_pw_step >= 0) push_pw_step(S.pos_pw_step);
         if (S.fused_away) continue;  // (runs inside its consumer's launch)
-        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : "k_sumsq";
+        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : S.kind == ST_COMB ? "k_comb" : "k_sumsq";
         Step st{1, sid, nm, 0};
         // algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a
         // Float64 map is 4 bytes a sample, whatever the node's promoted type) plus the samples it writes in the type of
@@ -277,6 +277,8 @@ void Plan::finalize() {
         else if (S.kind == ST_RESAMPLE) st.bytes = (S.rg.n_in * (src_esz(S) + (S.rp.arr2 ? src_esz(S) : 0)) + S.rg.n_out * osz) * S.rg.nch;  // (arr2: a second array of the source's type read)
         else if (S.kind == ST_SAMPLEAT)  // per frame: a position read, two table samples read where they lie, a Float64 written
             st.bytes = (S.need - S.base) * ((int64_t)nodes[nodes[S.node].kids[1]].nch * 8 + (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8));
+        else if (S.kind == ST_COMB)  // per sample: one read where x lies, one Float64 written
+            st.bytes = S.need * (int64_t)nodes[S.node].nch * ((int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8);
         else st.bytes = (S.need - S.base) * nodes[S.node].nch * esz;
         steps.push_back(st);
     }
@@ -461,6 +463,45 @@ static bool kernel_gave_up(Plan* P, std::string& err) {
     *(volatile uint32_t*)P->kerr = 0;
     err = std::string(who == 2 ? "k_resample_arb" : "k_rsos") + ": a wait between its waves did not end (this plan's last result is invalid)";
     return true;
+}
+
+// ---------------------------------------------------------------------------
+// Where the stages that take one plain input and write one Float64 buffer (SampleAt's table, Comb's x) read and write.
+static const char* array_base(Plan* P, int an) {
+    return P->nodes[an].nd.i0 ? (const char*)P->array_ptr[an] : (const char*)P->bufs[P->array_buf[an]].d;
+}
+// the input set up by Plan::stage_input: an array where it lies, or a buffer; -> its first element, `cs` its channel stride
+static const void* stage_input_view(Plan* P, const Stage& S, int nch, int dtype, int64_t& cs) {
+    if (S.in_array_node >= 0) {
+        cs = nch == 1 ? 0 : S.in_pitch;
+        return array_base(P, S.in_array_node) + (size_t)S.in_offset * dsize(dtype);
+    }
+    const Buf& b = P->bufs[S.in_buf];
+    cs = b.pitch;
+    return (const char*)b.d + (size_t)(S.in_offset - b.frame0) * dsize(dtype);
+}
+// the Float64 rows stage `sid` writes: its own buffer, the sink's result where the stage is aliased to it (from the
+// stage's local frame alias_skip on), or its window of the result; `cs` = the channel stride
+static double* stage_output_view(Plan* P, int sid, void* outp, int64_t& cs) {
+    const Stage& S = P->stages[sid];
+    const Buf& ob = P->bufs[S.out_buf];
+    void* d = ob.d;
+    cs = ob.pitch;
+    if (sid == P->alias_stage) {
+        if (P->out.is_device) {
+            d = outp;
+            cs = P->nodes[S.node].nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
+        } else {
+            d = P->bufs[P->out_stage_buf].d;
+            cs = P->bufs[P->out_stage_buf].pitch;
+        }
+        d = (char*)d - (size_t)P->alias_skip * 8;
+    } else if (S.win_off >= 0) {
+        const Buf& ab = P->bufs[P->out_alias_buf];
+        d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * 8;
+        cs = ab.pitch;
+    }
+    return (double*)d;
 }
 
 static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& err) {
@@ -694,47 +735,21 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
             } else if (P->stages[s.idx].kind == ST_SAMPLEAT) {
                 const Stage& S = P->stages[s.idx];
                 const Node& N = P->nodes[S.node];
-                auto array_base = [&](int an) {
-                    return P->nodes[an].nd.i0 ? (const char*)P->array_ptr[an] : (const char*)P->bufs[P->array_buf[an]].d;
-                };
                 SampleAtArgs a{};
                 const int xdt = P->nodes[N.kids[0]].dtype;
-                if (S.in_array_node >= 0) {  // the table where it lies
-                    a.x = array_base(S.in_array_node) + (size_t)S.in_offset * dsize(xdt);
-                    a.xcs = N.nch == 1 ? 0 : S.in_pitch;
-                } else {
-                    const Buf& b = P->bufs[S.in_buf];
-                    a.x = (const char*)b.d + (size_t)(S.in_offset - b.frame0) * dsize(xdt);
-                    a.xcs = b.pitch;
-                }
+                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
                 a.xfs = S.x_fstride;
                 a.N = S.in_frames;
                 a.x_f32 = xdt == SO_F32;
                 if (S.pos_array_node >= 0) {
-                    a.pos = (const double*)array_base(S.pos_array_node) + S.pos_offset;
+                    a.pos = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
                     a.pcs = S.pos_pitch;
                 } else {
                     const Buf& b = P->bufs[S.pos_buf];
                     a.pos = (const double*)b.d;
                     a.pcs = S.pos_pitch == 0 ? 0 : b.pitch;
                 }
-                Buf ob = P->bufs[S.out_buf];
-                if ((int)s.idx == P->alias_stage) {  // write the sink buffer directly
-                    if (P->out.is_device) {
-                        ob.d = outp;
-                        ob.pitch = N.nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
-                    } else {
-                        ob.d = P->bufs[P->out_stage_buf].d;
-                        ob.pitch = P->bufs[P->out_stage_buf].pitch;
-                    }
-                    ob.d = (char*)ob.d - (size_t)P->alias_skip * 8;
-                } else if (S.win_off >= 0) {  // ... or its window of it
-                    const Buf& ab = P->bufs[P->out_alias_buf];
-                    ob.d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * 8;
-                    ob.pitch = ab.pitch;
-                }
-                a.y = (double*)ob.d;
-                a.ycs = ob.pitch;
+                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
                 a.base = S.base;
                 a.n = S.need - S.base;
                 a.left = N.nd.d0;
@@ -744,6 +759,27 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 a.wrap = (N.nd.i0 >> 1) & 1;
                 const int nl = launch_sample_at(a, st);
                 if (nl < 0) fail(SO_ERR_UNSUPPORTED, "SampleAt: more than 65535 channels or 2^39 frames are not lowered");
+                s.launches = nl;
+                launches += nl;
+            } else if (P->stages[s.idx].kind == ST_COMB) {
+                const Stage& S = P->stages[s.idx];
+                const Node& N = P->nodes[S.node];
+                CombArgs a{};
+                const int xdt = P->nodes[N.kids[0]].dtype;
+                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
+                a.xfs = S.x_fstride;
+                a.x_f32 = xdt == SO_F32;
+                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
+                a.n = S.need;
+                a.D = N.nd.l0;
+                a.b0 = N.nd.d0;
+                a.bD = N.nd.d1;
+                a.a = N.nd.d2;
+                a.nch = N.nch;
+                if (a.D < 1) fail(SO_ERR_INVALID, "Comb: a delay of less than one frame");  // (the planner has refused it)
+                const int nl = launch_comb(a, st);
+                // (one lane per frame mod D: min(D, frames) lanes a channel, in blocks of kBlock, must fit grid.x)
+                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Comb: more than 65535 channels, or a delay AND a signal of 2^39 frames and more, are not lowered");
                 s.launches = nl;
                 launches += nl;
             } else {

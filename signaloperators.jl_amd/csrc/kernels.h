@@ -103,4 +103,19 @@ struct SampleAtArgs {
     int32_t nch, x_f32, relative, wrap;
 };
 int launch_sample_at(const SampleAtArgs& a, hipStream_t st);
+// Comb / Allpass (k_comb.hip, -ffp-contract=off): per channel y[n] = (b0 * x[n] + bD * x[n - D]) + a * y[n - D], n in [0, n),
+// x and y before frame 0 taken as +0.0, every product and sum rounded on its own; a term whose coefficient is exactly 0.0
+// is left out.  One lane per (residue n mod D, channel) walks its class in order.  Strides in elements.  Returns the
+// number of launches, -1 when the shape cannot be launched.
+constexpr int kCombUnroll = 16;  // steps of a lane whose loads are issued before the arithmetic that depends on them
+struct CombArgs {
+    const void* x;  // element (n, c) at x[n * xfs + c * xcs]
+    int64_t xfs, xcs;
+    double* y;      // y[n + c * ycs]
+    int64_t ycs;
+    int64_t n, D;
+    double b0, bD, a;
+    int32_t nch, x_f32;
+};
+int launch_comb(const CombArgs& a, hipStream_t st);
 }  // namespace so

@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -469,6 +469,9 @@ struct Plan {
     void check_frames(int ni, int64_t upto);
     void process_stage(int sid);
     void process_sample_at(int sid);
+    void process_comb(int sid);
+    bool plain_read(const std::vector<Piece>& ps, int dtype, bool unit_stride) const;
+    void stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype);
     int emit_pointwise(const std::vector<Piece>& ps, int out_buf, int out_dtype);
     // a piece of the fill form: the noise leaf's expression, the constant factor's (or -1), kFillRound* flags
     struct RandnFill { int noise = -1, scale = -1, flags = 0; };

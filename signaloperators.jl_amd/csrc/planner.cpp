@@ -266,6 +266,19 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             if (pos.short_skip) N.short_skip = pos.short_skip;
             break;
         }
+        case SO_NODE_COMB: {  // a feedback delay line of l0 frames (no reference counterpart; DESIGN.md "Comb")
+            const std::string where = "node " + std::to_string(i) + ": Comb ";
+            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            if (nd.l0 < 1) fail(SO_ERR_INVALID, where + "needs a delay of at least one frame (" + std::to_string(nd.l0) + " given)");
+            if (!std::isfinite(nd.d0) || !std::isfinite(nd.d1) || !std::isfinite(nd.d2)) fail(SO_ERR_INVALID, where + "takes finite coefficients b0, bD and a");
+            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a signal x of known, finite length (use `Until`)");
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            N.len = x.len;
+            N.nch = x.nch;
+            N.dtype = SO_F64;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -842,6 +855,29 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             return out;
         }
         const int sid = stage_for(ni, ST_SAMPLEAT);
+        use_stage(stages[sid], r, m);
+        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
+        Expr e;
+        e.op = E_LOAD;
+        e.dtype = N.dtype;
+        e.leaf = mk_leafmap(m);
+        e.leaf.fstride = 1;
+        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
+        e.leaf.dtype = N.dtype;
+        e.leaf.buf = stages[sid].out_buf;
+        e.mono = (m.sc == 0);
+        out.push_back({r, add_expr(e)});
+        return out;
+    }
+    case SO_NODE_COMB: {
+        // a stage: the recurrence starts at frame 0, so the stage computes the frames [0, need) whoever reads it and a
+        // window reads its slice of that buffer (process_comb, stages.cpp)
+        if (dry) {
+            check_frames(N.kids[0], m.sf ? r.b + m.df : m.df + 1);
+            out.push_back({r, mk_const(0.0, N.dtype)});
+            return out;
+        }
+        const int sid = stage_for(ni, ST_COMB);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

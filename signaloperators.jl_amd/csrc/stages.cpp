@@ -356,6 +356,40 @@ void Plan::sos_chunking(int sid, int64_t need, int nch, int dtype, const std::ve
     stages[sid].sg = g;
 }
 
+// Is this lowering of a stage's input one plain read -- an array leaf of any strides, or another stage's buffer -- that a
+// kernel can take where it lies?  (`unit_stride`: only with frame stride 1.)  SampleAt's table and positions and Comb's x.
+bool Plan::plain_read(const std::vector<Piece>& ps, int dtype, bool unit_stride) const {
+    if (ps.size() != 1) return false;
+    const Expr& e = exprs[ps[0].e];
+    return e.op == E_LOAD && e.leaf.mode == LM_PLAIN && e.leaf.sf == 1 && e.leaf.sc == 1 && e.leaf.dtype == dtype && e.leaf.df >= 0 &&
+           e.leaf.dc >= 0 && (!unit_stride || e.leaf.fstride == 1) && e.leaf.fstride >= 1 &&
+           (e.leaf.cstride > 0 || (e.leaf.cstride == -1 && e.array_node < 0 && e.leaf.dc == 0) || ps[0].r.c1 - ps[0].r.c0 == 1);
+}
+
+// The input of stage `sid`, `frames` x `nch` of `dtype`, lowered to `ps`: read where it lies when it is plain, materialised by
+// one pointwise step otherwise (Stage::in_array_node / in_buf / x_fstride / in_pitch / in_offset / pw_step).
+void Plan::stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype) {
+    Stage& S = stages[sid];
+    S.in_frames = frames;
+    if (plain_read(ps, dtype, false)) {
+        const Expr& e = exprs[ps[0].e];
+        S.in_array_node = e.array_node;
+        S.in_buf = e.array_node >= 0 ? -1 : e.leaf.buf;
+        S.x_fstride = e.leaf.fstride;
+        S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
+        S.in_offset = e.leaf.df * e.leaf.fstride + (e.array_node >= 0 ? e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0) : 0);
+        if (e.array_node >= 0) count_array(e.array_node);
+        return;
+    }
+    const int b = new_buf(frames, nch, dtype);
+    const int step = emit_pointwise(ps, b, dtype);
+    Stage& S2 = stages[sid];  // (re-taken: the vectors may have grown)
+    S2.in_buf = b;
+    S2.in_pitch = -1;
+    S2.in_offset = 0;
+    S2.pw_step = step;
+}
+
 // SampleAt: the table x whole -- an array (any strides) or a stage buffer read where it lies, anything else materialised
 // by one pointwise step -- and the positions of the frames [base, need) anybody reads: a Float64 array with unit frame
 // stride read in place, anything else (a formula, a Float32 array, another stage's buffer) one pointwise step into a
@@ -372,39 +406,11 @@ void Plan::process_sample_at(int sid) {
     stages[sid].base = stages[sid].in_base = base;
     bufs[stages[sid].out_buf].frame0 = base;
     if (base > 0) check_frames(pk, base);
-    auto plain = [&](const std::vector<Piece>& ps, int dtype, bool unit_stride) {
-        if (ps.size() != 1) return false;
-        const Expr& e = exprs[ps[0].e];
-        return e.op == E_LOAD && e.leaf.mode == LM_PLAIN && e.leaf.sf == 1 && e.leaf.sc == 1 && e.leaf.dtype == dtype && e.leaf.df >= 0 &&
-               e.leaf.dc >= 0 && (!unit_stride || e.leaf.fstride == 1) && e.leaf.fstride >= 1 &&
-               (e.leaf.cstride > 0 || (e.leaf.cstride == -1 && e.array_node < 0 && e.leaf.dc == 0) || ps[0].r.c1 - ps[0].r.c0 == 1);
-    };
-    {
-        const std::vector<Piece> ps = lower(xk, Rect{0, Nx, 0, nch}, Map{1, 0, 1, 0});
-        Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
-        S.in_frames = Nx;
-        if (plain(ps, xdt, false)) {
-            const Expr& e = exprs[ps[0].e];
-            S.in_array_node = e.array_node;
-            S.in_buf = e.array_node >= 0 ? -1 : e.leaf.buf;
-            S.x_fstride = e.leaf.fstride;
-            S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
-            S.in_offset = e.leaf.df * e.leaf.fstride + (e.array_node >= 0 ? e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0) : 0);
-            if (e.array_node >= 0) count_array(e.array_node);
-        } else {
-            const int b = new_buf(Nx, nch, xdt);
-            const int step = emit_pointwise(ps, b, xdt);
-            Stage& S2 = stages[sid];
-            S2.in_buf = b;
-            S2.in_pitch = -1;
-            S2.in_offset = 0;
-            S2.pw_step = step;
-        }
-    }
+    stage_input(sid, lower(xk, Rect{0, Nx, 0, nch}, Map{1, 0, 1, 0}), Nx, nch, xdt);
     {
         const std::vector<Piece> ps = lower(pk, Rect{0, need - base, 0, pch}, Map{1, base, 1, 0});
-        Stage& S = stages[sid];
-        if (plain(ps, SO_F64, true) && exprs[ps[0].e].array_node >= 0) {
+        Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
+        if (plain_read(ps, SO_F64, true) && exprs[ps[0].e].array_node >= 0) {
             const Expr& e = exprs[ps[0].e];
             S.pos_array_node = e.array_node;
             S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
@@ -422,9 +428,27 @@ void Plan::process_sample_at(int sid) {
     }
 }
 
+// Comb: the recurrence starts at frame 0, so the stage computes the frames [0, need) of its buffer (base = 0) whatever
+// window reads it.  The child is demanded over the same frames and taken like SampleAt's table (stage_input).
+void Plan::process_comb(int sid) {
+    const int ni = stages[sid].node;
+    const int xk = nodes[ni].kids[0];
+    const int nch = nodes[ni].nch;
+    const int64_t need = stages[sid].need;
+    stages[sid].processed = true;
+    if (need <= 0) return;
+    stages[sid].base = stages[sid].in_base = 0;
+    bufs[stages[sid].out_buf].frame0 = 0;
+    stage_input(sid, lower(xk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[xk].dtype);
+    if (std::getenv("SIGOPS_DEBUG_PLAN"))
+        std::fprintf(stderr, "[sigops] Comb stage %d: D=%lld frames [0,%lld) x %d channels, x %s\n", sid, (long long)nodes[ni].nd.l0, (long long)need,
+                     nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+}
+
 void Plan::process_stage(int sid) {
     // NOTE: `stages` may grow while lowering the child; re-take references after.
     if (stages[sid].kind == ST_SAMPLEAT) return process_sample_at(sid);
+    if (stages[sid].kind == ST_COMB) return process_comb(sid);
     int ni = stages[sid].node;
     Node& N = nodes[ni];
     const so_node_t& nd = N.nd;

@@ -421,6 +421,9 @@ def _streamable(x):
     if isinstance(x, S.SampleAtSignal):
         S.error("BlockStream: SampleAt reads its table at any position, and a stream keeps only a tail of its input "
                 "resident; not streamable")
+    if isinstance(x, S.CombSignal):
+        S.error("BlockStream: Comb / Allpass would have to carry the D frames of its delay line from one push to the "
+                "next, and that is not built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

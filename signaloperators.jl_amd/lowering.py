@@ -257,6 +257,9 @@ def _demand(x, n, out, skip=0):
         # the table whole (any frame of it may be read), the positions for the frames the sink reaches
         _demand(x.signal, S.nframes(x.signal), out, 0)
         _demand(x.pos, capped(x.pos, n), out, skip)
+    elif isinstance(x, S.CombSignal):
+        # the recurrence starts at frame 0: the frames before a window are computed too
+        _demand(x.signal, capped(x.signal, n), out, 0)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -543,6 +546,11 @@ def lower(x, nframes_out=None, rng=None):
             kids = (rec(s.signal), rec(s.pos))
             r = common(s, K.NODE_SAMPLEAT)
             r.update(i0=(1 if s.relative else 0) | (2 if s.wrap else 0), d0=s.left, d1=s.right, children=kids)
+            idx = lw.add(**r)
+        elif isinstance(s, S.CombSignal):
+            c = rec(s.signal)
+            r = common(s, K.NODE_COMB)
+            r.update(l0=s.delay, d0=s.b0, d1=s.bD, d2=s.a, children=(c,))
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

@@ -534,6 +534,31 @@ class SampleAtSignal(AbstractSignal):
         return self.pos.duration()
 
 
+class CombSignal(AbstractSignal):
+    """`Comb(x, d, g)` / `Allpass(x, d, g)`: a feedback delay line of `delay` frames over `x`,
+    `y[n] = (b0 x[n] + bD x[n - D]) + a y[n - D]` (no reference counterpart; include/sigops.h SO_NODE_COMB, DESIGN.md
+    "Comb").  It has the length, frame rate and channels of `x` and is Float64."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x, delay, b0, bD, a):
+        self.signal = x
+        self.children = (x,)
+        self.delay = int(delay)
+        self.b0 = float(b0)
+        self.bD = float(bD)
+        self.a = float(a)
+        self.fs = x.fs
+        self.nch = x.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -897,6 +922,12 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return SampleAtSignal(x.signal, ToFramerate(x.pos, fs, bs), x.left, x.right, x.relative, x.wrap)
+    if isinstance(x, CombSignal):
+        # the delay is a number of frames (a time was converted with the rate x had): a missing rate goes to x, a
+        # result that has a rate is resampled like any computed signal
+        if known:
+            return _resample(x, fs, bs)
+        return CombSignal(ToFramerate(x.signal, fs, bs), x.delay, x.b0, x.bD, x.a)
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1082,6 +1113,72 @@ def Delay(*args):
     if len(args) != 2:
         error("Delay(x, d) expected")
     return _Delay(args[0], args[1])
+
+
+# --------------------------------------------------------------------------
+# Comb / Allpass: feedback delay lines (no reference counterpart)
+def _comb_delay(what, x, d):
+    """the delay in frames: a number of frames, a `frames` quantity, or a time converted with the rate of x"""
+    if isinstance(d, Quantity):
+        if U.is_time(d):
+            if x.fs is None:
+                error(f"{what}: a delay given as a time needs the frame rate of x")
+            return U.inframes_int(d, x.fs)
+        if not U.is_frames(d):
+            error(f"{what}: the delay {d} is neither a time nor a number of frames")
+        d = d.value
+    if not _real_number(d) or not math.isfinite(d) or d != math.floor(d):
+        error(f"{what}: the delay must be a whole number of frames, not {d!r} (`Delay` interpolates; a delay line does not)")
+    return int(d)
+
+
+def _Comb(what, x, d, b0, bD, a):
+    """`what` names the construct in a refusal: "Comb", or "Allpass (Comb)" for the wrapper"""
+    x = _assignal(x)
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal x must have a known, finite length (use `Until`): the recurrence starts at frame 0")
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    for name, v in (("g", a), ("feedforward", bD), ("direct", b0)):
+        if not _real_number(v) or not math.isfinite(v):
+            error(f"{what}: {name} must be a finite number, not {v!r}")
+    D = _comb_delay(what, x, d)
+    if D < 1:
+        error(f"{what}: the delay must be at least one frame ({D} given)")
+    return CombSignal(x, D, b0, bD, a)
+
+
+def Comb(*args, feedforward=0.0, direct=1.0):
+    """`Comb(x, d, g)`, curried `x | Comb(d, g)`: a comb filter, `y[n] = (direct x[n] + feedforward x[n - D]) + g y[n - D]`
+    per channel, frames before the first taken as +0.0, every product and sum rounded on its own in Float64 and a term
+    whose coefficient is exactly 0 left out.  The default is the feedback comb `y[n] = x[n] + g y[n - D]`, an echo with
+    repeats.  `d` is a whole number of frames (a number or a `frames` quantity) or a time, converted with the rate of `x`.
+    The result has the length of `x`; an echo's tail is the caller's to ask for: `x | Pad(zero) | Until(t) | Comb(d, g)`.
+    `x` must have a known, finite length.  `stream` over the node works, but the recurrence starts at frame 0, so
+    every block recomputes the frames before it (quadratic in the length, as `stream` over `Normpower` re-reads its
+    input).  Blocks and windows agree with the whole sink bit for bit where `x` gives the same bits whatever number of
+    frames is asked of it (arrays, formulas, maps, `SampleAt`, nested `Comb`s); a `Filt` below the node rounds by how it
+    chunks its input, and the comb carries that: agreement within the Float64 contract.  `BlockStream` and multi-GPU
+    shards refuse the node."""
+    if len(args) == 2:
+        d, g = args
+        return Curried(lambda x: _Comb("Comb", x, d, direct, feedforward, g))
+    if len(args) != 3:
+        error("Comb(x, d, g) expected")
+    return _Comb("Comb", args[0], args[1], direct, feedforward, args[2])
+
+
+def Allpass(*args):
+    """`Allpass(x, d, g)`, curried `x | Allpass(d, g)`: Schroeder's allpass, `y[n] = (-g x[n] + x[n - D]) + g y[n - D]`:
+    `Comb(x, d, g, feedforward=1, direct=-g)`."""
+    if len(args) == 2:
+        d, g = args
+        return Curried(lambda x: _Comb("Allpass (Comb)", x, d, -g if _real_number(g) else g, 1.0, g))
+    if len(args) != 3:
+        error("Allpass(x, d, g) expected: Comb with direct = -g, feedforward = 1")
+    g = args[2]
+    return _Comb("Allpass (Comb)", args[0], args[1], -g if _real_number(g) else g, 1.0, g)
 
 
 # --------------------------------------------------------------------------

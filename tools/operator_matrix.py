@@ -89,6 +89,12 @@ cases = {
     "sampleat vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True),
     "sampleat random": lambda: so.SampleAt(X, POS("random")),
     "sampleat wrap 2048": lambda: so.SampleAt(so.Signal(x[:2048], fs), POS("wavetable"), wrap=True),
+    # `Comb(x, d, g)` / `Allpass(x, d, g)` (include/sigops.h SO_NODE_COMB, csrc/k_comb.hip): a lane per (frame mod D,
+    # channel) -- an echo of 4800 frames fills the chip, a delay of 48 frames is 48 lanes a channel (the documented slow
+    # corner); the yardstick is the `copy (Until)` row at the top, one read and one write per sample
+    "comb 4800": lambda: so.Comb(X, 4800, 0.7),
+    "comb 48": lambda: so.Comb(X, 48, 0.7),
+    "allpass 347": lambda: so.Allpass(X, 347, 0.7),
     # counter-based device noise (`Signal(randn, rng=so.DeviceRNG(...))`, csrc/krand.h): the fill kernel, the same leaf as
     # an expression (hipRTC, K1's math instantiation: `case_env`), replicated to the channels, and the headline's tree
     # with the noise in place of its array leaf next to the array-leaf form (FRAMES=26.46e6 for the headline's own size)
@@ -106,9 +112,14 @@ case_env = {
     "noise expr K1 math (mono)": {"SIGOPS_RANDN_NOFILL": "1", "SIGOPS_RTC": "0"},
 }
 only = os.environ.get("ONLY")
+# ONLY_ANY="copy (Until);comb": the rows whose name contains one of the pieces between semicolons (no row name has one), so
+# that a row and its yardstick are timed in one process; ONLY keeps its meaning, one substring
+only_any = [o for o in os.environ.get("ONLY_ANY", "").split(";") if o]
 WARM, REPS = int(os.environ.get("WARM", "20")), int(os.environ.get("REPS", "30"))
 for name, mk in cases.items():
     if only and only not in name:
+        continue
+    if only_any and not any(o in name for o in only_any):
         continue
     try:
         tree = mk()
@@ -154,7 +165,7 @@ for name, mk in cases.items():
 # generator (drawn on the host and uploaded).  Inside the timer: building the tree, `so.sink(tree, "torch")` -- lowering,
 # plan creation, the result's allocation, the execute, the plan's check -- and a device synchronise.  SINKS sinks in a
 # row in this process; the first pays the one-time costs (code object load).
-if not only or only in "whole sink of noise":
+if (not only or only in "whole sink of noise") and (not only_any or any(o in "whole sink of noise" for o in only_any)):
     import time
 
     secs, SINKS = float(os.environ.get("NOISE_SECONDS", "60")), int(os.environ.get("SINKS", "5"))
