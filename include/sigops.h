@@ -83,7 +83,8 @@ typedef enum so_kind {
     SO_NODE_RESAMPLE = 10,/* FilteredSignal{..ResamplerFn}   src/reformatting.jl:92-122    */
     SO_NODE_NORMPOWER = 11,/* NormedSignal                   src/filters.jl:266-314        */
     SO_NODE_SAMPLEAT = 12,/* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
-    SO_NODE_COMB = 13     /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
+    SO_NODE_COMB = 13,    /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
+    SO_NODE_CUMSUM = 14   /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -269,6 +270,15 @@ typedef enum so_rskind {
  *            rate and channels and is Float64; the result equals a sequential loop bit for bit ("Comb").
  *            Comb(x, d, g): b0 = direct (1), bD = feedforward (0), a = g.  Allpass(x, d, g): b0 = -g, bD = 1, a = g.
  *            Not exactly one child, l0 < 1 or a non-finite coefficient is SO_ERR_INVALID; an infinite child
+ *            SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
+ *  CUMSUM    child 0 = x (finite, Float32 / Float64)   no parameters.
+ *            Per channel y[n] = x[0] + ... + x[n] in Float64 (a Float32 x is widened on load, exactly), summed over one
+ *            tree that depends on the frame index only, never on how many frames are asked for: runs of 16 frames left
+ *            to right from the first sample itself, an inclusive Kogge-Stone scan over the 64 run totals of a tile of
+ *            1024 frames, a sequential carry over the 16 tiles of a chunk and a sequential carry over the chunks of
+ *            16384 frames, every + one rounded addition ("Cumsum"; tests/cumsum_ref.py is the definition).
+ *            The node has x's length, frame rate and channels.  Integrate(x) is a MAP that multiplies the node by the
+ *            Float64 constant 1 / framerate.  Not exactly one child is SO_ERR_INVALID; an infinite child
  *            SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {

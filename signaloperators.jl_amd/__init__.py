@@ -10,7 +10,7 @@ from .signals import (  # noqa: F401
     ToFramerate, ToChannels, ToEltype, Format, Uniform,
     ArraySig, NumberSig, FuncSig, CutApply, PaddedSignal, AppendSignals, RampSignal,
     MapSignal, FilteredSignal, NormedSignal, FilterFn, RawFilterFn, RawFirFn, ResamplerFn, digitalfilter, ZeroPoleGain, SecondOrderSections, Biquad,
-    PolynomialRatio, SampleAt, Delay, SampleAtSignal, Comb, Allpass, CombSignal,
+    PolynomialRatio, SampleAt, Delay, SampleAtSignal, Comb, Allpass, CombSignal, Cumsum, Integrate, CumsumSignal,
 )
 from numpy import sin, cos  # noqa: F401  (Signal(sin), Signal(cos))
 from .engine import sink, sink_into, stream, BlockStream, Plan, Array, process_sink_params, _eager, filt, filt_into  # noqa: F401

@@ -260,7 +260,7 @@ void Plan::finalize() {
         if (S.pw_step >= 0) push_pw_step(S.pw_step);
         if (S.pos_pw_step >= 0) push_pw_step(S.pos_pw_step);
         if (S.fused_away) continue;  // (runs inside its consumer's launch)
-        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : S.kind == ST_COMB ? "k_comb" : "k_sumsq";
+        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : S.kind == ST_COMB ? "k_comb" : S.kind == ST_CUMSUM ? "k_cumsum" : "k_sumsq";
         Step st{1, sid, nm, 0};
         // algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a
         // Float64 map is 4 bytes a sample, whatever the node's promoted type) plus the samples it writes in the type of
@@ -279,6 +279,8 @@ void Plan::finalize() {
             st.bytes = (S.need - S.base) * ((int64_t)nodes[nodes[S.node].kids[1]].nch * 8 + (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8));
         else if (S.kind == ST_COMB)  // per sample: one read where x lies, one Float64 written
             st.bytes = S.need * (int64_t)nodes[S.node].nch * ((int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8);
+        else if (S.kind == ST_CUMSUM)  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
+            st.bytes = S.need * (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8);
         else st.bytes = (S.need - S.base) * nodes[S.node].nch * esz;
         steps.push_back(st);
     }
@@ -780,6 +782,24 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 const int nl = launch_comb(a, st);
                 // (one lane per frame mod D: min(D, frames) lanes a channel, in blocks of kBlock, must fit grid.x)
                 if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Comb: more than 65535 channels, or a delay AND a signal of 2^39 frames and more, are not lowered");
+                s.launches = nl;
+                launches += nl;
+            } else if (P->stages[s.idx].kind == ST_CUMSUM) {
+                const Stage& S = P->stages[s.idx];
+                const Node& N = P->nodes[S.node];
+                CumsumArgs a{};
+                const int xdt = P->nodes[N.kids[0]].dtype;
+                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
+                a.xfs = S.x_fstride;
+                a.x_f32 = xdt == SO_F32;
+                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
+                a.n = S.need;
+                a.nch = N.nch;
+                a.tot_pitch = cumsum_totals(S.need);
+                a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
+                const int nl = launch_cumsum(a, st);
+                // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
+                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Cumsum: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
                 s.launches = nl;
                 launches += nl;
             } else {

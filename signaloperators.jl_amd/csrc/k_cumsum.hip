@@ -1,0 +1,272 @@
+// k_cumsum: `Cumsum(x)` (signals.py; SO_NODE_CUMSUM of include/sigops.h) -- per channel y[n] = x[0] + ... + x[n] in Float64
+// over ONE summation tree that depends on the frame index only (DESIGN.md "Cumsum"; tests/cumsum_ref.py is the
+// definition), so a window, a stream block and the whole sink give the same bits:
+//   run    j of a tile: the frames [16 j, 16 j + 16) summed left to right from the first sample itself -> r, total R[j]
+//   tile   (64 runs): an inclusive Kogge-Stone scan v over R, d = 1 .. 32, a lane without a source keeps its value;
+//          t = r in run 0, v[j - 1] + r in run j >= 1
+//   chunk  (kCumsumTiles tiles): tile 0 is t, tile k >= 1 is c + t with c the last value of tile k - 1
+//   signal chunk 0 is its chunk-local u, chunk k >= 1 is C + u with C the running sum of the chunks' last u
+// Every + is one rounded Float64 addition; nothing is ever added to a zero that the tree does not have, so -0.0 survives.
+//
+// Reduce-then-scan, no workgroup waits for another (a look-back scan would sum whichever predecessors have published,
+// which is another tree each time):
+//   k_cumsum_totals  one workgroup per (chunk, channel), every chunk but the last: the chunk-local last value -> tot
+//   k_cumsum_carry   one workgroup per channel: tot -> its running sum, in place (lane 0 adds, out of LDS)
+//   k_cumsum_scan    one workgroup per (chunk, channel): the chunk-local scan again, + tot[chunk - 1], stored
+// A signal of one chunk is the third launch alone.
+//
+// A workgroup is kCumsumWaves waves; a wave takes kCumsumTiles / kCumsumWaves consecutive tiles, one after the other, a
+// lane one run of each and keeps its 16 values in registers until the tile carries are known (one barrier).  A lane's run
+// is 128 contiguous bytes, so x is not loaded in run order: a full tile of a unit-stride, 16-byte aligned row is loaded 16
+// bytes a lane, neighbouring lanes on neighbouring words (VL), written to the wave's own LDS image [64 runs][16 + 2 pad]
+// and read back a run a lane with ds_read_b128 (the pad of 16 bytes puts the 16 lanes of a read group on 16 different
+// slots); pass 2 stores the same way back (VS).  Everything else -- a frame stride, an unaligned row, the ragged last
+// tile -- goes one element a lane, lanes on neighbouring frames, every frame index clamped into [0, n) BEFORE an address
+// is formed and every store under a guard (k_comb.hip and k_sample_at.hip do the same).  The LDS image belongs to one
+// wave; its writes and reads are ordered by a wavefront-scope fence.  Frame arithmetic is 64-bit.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace so {
+
+constexpr int kCumsumWaves = 4;
+constexpr int kCumsumPerWave = kCumsumTiles / kCumsumWaves;  // tiles a wave carries in registers
+constexpr int kCumsumPitch = kCumsumRun + 2;                 // doubles per run of the LDS image
+constexpr int kCumsumImage = 64 * kCumsumPitch;              // doubles per wave
+static_assert(kCumsumRun == 16 && kCumsumTiles % kCumsumWaves == 0, "the loaders below are written for runs of 16 frames");
+
+typedef double cs_v2d __attribute__((ext_vector_type(2)));
+typedef float cs_v4f __attribute__((ext_vector_type(4)));
+
+// the LDS image is one wave's: order its accesses among the lanes of the wave
+__device__ __forceinline__ void cs_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// element e of a tile lies at this double of the image
+__device__ __forceinline__ int cs_at(int e) { return (e >> 4) * kCumsumPitch + (e & 15); }
+
+// the tile that starts at frame f0 of the row xr (n frames, frame stride xfs) -> the lane's run in r[0 .. 16)
+template <typename TX, bool VL>
+__device__ __forceinline__ void cs_load_tile(const TX* __restrict__ xr, int64_t xfs, int64_t f0, int64_t n, double* img, int lane,
+                                             double (&r)[kCumsumRun]) {
+    if (VL && f0 + kCumsumTile <= n) {
+        if (sizeof(TX) == 8) {
+#pragma unroll
+            for (int i = 0; i < kCumsumTile / 128; ++i) {
+                const int e = 128 * i + 2 * lane;
+                *reinterpret_cast<cs_v2d*>(img + cs_at(e)) = *reinterpret_cast<const cs_v2d*>(xr + f0 + e);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < kCumsumTile / 256; ++i) {
+                const int e = 256 * i + 4 * lane;
+                const cs_v4f w = *reinterpret_cast<const cs_v4f*>(xr + f0 + e);
+                cs_v2d lo, hi;
+                lo.x = (double)w.x, lo.y = (double)w.y, hi.x = (double)w.z, hi.y = (double)w.w;
+                *reinterpret_cast<cs_v2d*>(img + cs_at(e)) = lo;
+                *reinterpret_cast<cs_v2d*>(img + cs_at(e) + 2) = hi;
+            }
+        }
+    } else {
+        const int64_t last = n - 1;
+        TX w[kCumsumRun];
+#pragma unroll
+        for (int m = 0; m < kCumsumRun; ++m) {
+            const int64_t f = f0 + 64 * m + lane;
+            w[m] = xr[(f <= last ? f : last) * xfs];  // (past the end: a copy of the last frame, read by nothing that exists)
+        }
+#pragma unroll
+        for (int m = 0; m < kCumsumRun; ++m) img[cs_at(64 * m + lane)] = (double)w[m];
+    }
+    cs_wave_sync();
+#pragma unroll
+    for (int q = 0; q < kCumsumRun / 2; ++q) {
+        const cs_v2d w = *reinterpret_cast<const cs_v2d*>(img + lane * kCumsumPitch + 2 * q);
+        r[2 * q] = w.x, r[2 * q + 1] = w.y;
+    }
+    cs_wave_sync();  // (the image is written again: by the next tile, or by cs_store_tile)
+}
+
+// r: the lane's run -> its tile-local values t; returns the last of them (lane 63: the tile's last value, v[62] + R[63] --
+// the value the next tile carries, which is not the scan's v[63])
+__device__ __forceinline__ double cs_tile_scan(double (&r)[kCumsumRun], int lane) {
+#pragma unroll
+    for (int m = 1; m < kCumsumRun; ++m) r[m] = r[m - 1] + r[m];
+    double v = r[kCumsumRun - 1];
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        const double s = __shfl_up(v, d, 64);
+        if (lane >= d) v = s + v;
+    }
+    const double before = __shfl_up(v, 1, 64);
+    if (lane >= 1) {
+#pragma unroll
+        for (int m = 0; m < kCumsumRun; ++m) r[m] = before + r[m];
+    }
+    return r[kCumsumRun - 1];
+}
+
+// the lane's run r -> the frames [f0, f0 + 1024) of the row yr that exist
+template <bool VS>
+__device__ __forceinline__ void cs_store_tile(double* __restrict__ yr, int64_t f0, int64_t n, double* img, int lane,
+                                              const double (&r)[kCumsumRun]) {
+#pragma unroll
+    for (int q = 0; q < kCumsumRun / 2; ++q) {
+        cs_v2d w;
+        w.x = r[2 * q], w.y = r[2 * q + 1];
+        *reinterpret_cast<cs_v2d*>(img + lane * kCumsumPitch + 2 * q) = w;
+    }
+    cs_wave_sync();
+    if (VS && f0 + kCumsumTile <= n) {
+#pragma unroll
+        for (int i = 0; i < kCumsumTile / 128; ++i) {
+            const int e = 128 * i + 2 * lane;
+            *reinterpret_cast<cs_v2d*>(yr + f0 + e) = *reinterpret_cast<const cs_v2d*>(img + cs_at(e));
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < kCumsumRun; ++m) {
+            const int64_t f = f0 + 64 * m + lane;
+            if (f < n) yr[f] = img[cs_at(64 * m + lane)];
+        }
+    }
+    cs_wave_sync();
+}
+
+// Pass 1: the chunk-local last value of chunk blockIdx.x (a whole chunk: the last chunk of a row has no total).
+template <typename TX, bool VL>
+__global__ __launch_bounds__(64 * kCumsumWaves) void k_cumsum_totals(CumsumArgs a) {
+    __shared__ __attribute__((aligned(16))) double image[kCumsumWaves * kCumsumImage];
+    __shared__ double total[kCumsumTiles];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t chunk = blockIdx.x;
+    const int c = blockIdx.y;
+    const TX* __restrict__ xr = (const TX*)a.x + (int64_t)c * a.xcs;
+    double* img = image + wave * kCumsumImage;
+#pragma unroll 1
+    for (int i = 0; i < kCumsumPerWave; ++i) {
+        const int tile = wave * kCumsumPerWave + i;
+        double r[kCumsumRun];
+        cs_load_tile<TX, VL>(xr, a.xfs, chunk * kCumsumChunk + (int64_t)tile * kCumsumTile, a.n, img, lane, r);
+        const double v = cs_tile_scan(r, lane);
+        if (lane == 63) total[tile] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = total[0];
+#pragma unroll
+        for (int k = 1; k < kCumsumTiles; ++k) s = s + total[k];
+        a.tot[(int64_t)c * a.tot_pitch + chunk] = s;
+    }
+}
+
+// The carries: tot[k] <- tot[0] + ... + tot[k], summed in that order, per channel (blockIdx.x), in place.  The totals go
+// through LDS kBlock at a time; lane 0 reads 16 of them, adds, writes 16.
+__global__ __launch_bounds__(kBlock) void k_cumsum_carry(double* tot, int64_t pitch, int64_t count) {
+    __shared__ double in[kBlock], out[kBlock];
+    double* row = tot + (int64_t)blockIdx.x * pitch;
+    double s = 0.0;  // (lane 0's; replaced, not added to, by the first total)
+    for (int64_t k0 = 0; k0 < count; k0 += kBlock) {
+        const int64_t k = k0 + threadIdx.x;
+        if (k < count) in[threadIdx.x] = row[k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = (int)(count - k0 < kBlock ? count - k0 : kBlock);  // (the entries past m are not read back)
+            for (int j0 = 0; j0 < m; j0 += 16) {
+                double w[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) w[j] = in[j0 + j];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    s = (k0 == 0 && j0 == 0 && j == 0) ? w[0] : s + w[j];
+                    out[j0 + j] = s;
+                }
+            }
+        }
+        __syncthreads();
+        if (k < count) row[k] = out[threadIdx.x];
+    }
+}
+
+// Pass 2: chunk blockIdx.x of channel blockIdx.y, stored.
+template <typename TX, bool VL, bool VS>
+__global__ __launch_bounds__(64 * kCumsumWaves) void k_cumsum_scan(CumsumArgs a) {
+    __shared__ __attribute__((aligned(16))) double image[kCumsumWaves * kCumsumImage];
+    __shared__ double total[kCumsumTiles];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t chunk = blockIdx.x;
+    const int c = blockIdx.y;
+    const TX* __restrict__ xr = (const TX*)a.x + (int64_t)c * a.xcs;
+    double* __restrict__ yr = a.y + (int64_t)c * a.ycs;
+    double* img = image + wave * kCumsumImage;
+    const int64_t f00 = chunk * kCumsumChunk + (int64_t)wave * kCumsumPerWave * kCumsumTile;  // the wave's first frame
+    double r[kCumsumPerWave][kCumsumRun];
+#pragma unroll
+    for (int i = 0; i < kCumsumPerWave; ++i) {
+        const int64_t f0 = f00 + (int64_t)i * kCumsumTile;
+        if (f0 < a.n) {  // (a tile past the end: nothing reads its total)
+            cs_load_tile<TX, VL>(xr, a.xfs, f0, a.n, img, lane, r[i]);
+            const double v = cs_tile_scan(r[i], lane);
+            if (lane == 63) total[wave * kCumsumPerWave + i] = v;
+        }
+    }
+    __syncthreads();
+    // the carry into the wave's first tile: the last value of the tile before it, summed tile after tile
+    double cy = 0.0;
+    for (int k = 0; k < wave * kCumsumPerWave; ++k) cy = k == 0 ? total[0] : cy + total[k];
+    const bool chunks_before = chunk > 0;
+    const double C = chunks_before ? a.tot[(int64_t)c * a.tot_pitch + chunk - 1] : 0.0;
+#pragma unroll
+    for (int i = 0; i < kCumsumPerWave; ++i) {
+        const int64_t f0 = f00 + (int64_t)i * kCumsumTile;
+        if (f0 >= a.n) break;
+        const int tile = wave * kCumsumPerWave + i;
+        if (tile > 0) {
+#pragma unroll
+            for (int m = 0; m < kCumsumRun; ++m) r[i][m] = cy + r[i][m];
+        }
+        if (chunks_before) {
+#pragma unroll
+            for (int m = 0; m < kCumsumRun; ++m) r[i][m] = C + r[i][m];
+        }
+        cs_store_tile<VS>(yr, f0, a.n, img, lane, r[i]);
+        cy = tile == 0 ? total[0] : cy + total[tile];  // the last value of this tile, chunk-local
+    }
+}
+
+static bool cs_aligned(const void* p, int64_t cs, int nch, size_t esz) {
+    return (uintptr_t)p % 16 == 0 && (nch == 1 || (cs * (int64_t)esz) % 16 == 0);
+}
+
+template <typename TX>
+static void launch_cumsum_t(const CumsumArgs& a, int64_t nchunks, hipStream_t st) {
+    const bool vl = a.xfs == 1 && cs_aligned(a.x, a.xcs, a.nch, sizeof(TX)), vs = cs_aligned(a.y, a.ycs, a.nch, 8);
+    const dim3 block(64 * kCumsumWaves);
+    if (nchunks > 1) {
+        const dim3 grid((unsigned)(nchunks - 1), (unsigned)a.nch);
+        if (vl) hipLaunchKernelGGL((k_cumsum_totals<TX, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_cumsum_totals<TX, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_cumsum_carry, dim3((unsigned)a.nch), dim3(kBlock), 0, st, a.tot, a.tot_pitch, nchunks - 1);
+    }
+    const dim3 grid((unsigned)nchunks, (unsigned)a.nch);
+    if (vl && vs) hipLaunchKernelGGL((k_cumsum_scan<TX, true, true>), grid, block, 0, st, a);
+    else if (vl) hipLaunchKernelGGL((k_cumsum_scan<TX, true, false>), grid, block, 0, st, a);
+    else if (vs) hipLaunchKernelGGL((k_cumsum_scan<TX, false, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_cumsum_scan<TX, false, false>), grid, block, 0, st, a);
+}
+
+int launch_cumsum(const CumsumArgs& a, hipStream_t st) {
+    if (a.n <= 0 || a.nch <= 0) return 0;
+    const int64_t nchunks = (a.n + kCumsumChunk - 1) / kCumsumChunk;
+    if (a.nch > 65535 || nchunks >= ((int64_t)1 << 31)) return -1;
+    if (nchunks > 1 && (a.tot == nullptr || a.tot_pitch < nchunks - 1)) return -1;
+    if (a.x_f32) launch_cumsum_t<float>(a, nchunks, st);
+    else launch_cumsum_t<double>(a, nchunks, st);
+    return nchunks > 1 ? 3 : 1;
+}
+
+}  // namespace so

@@ -118,4 +118,27 @@ struct CombArgs {
     int32_t nch, x_f32;
 };
 int launch_comb(const CombArgs& a, hipStream_t st);
+// Cumsum (k_cumsum.hip, -ffp-contract=off): per channel y[n] = x[0] + ... + x[n] in Float64 over ONE summation tree that
+// depends on the frame index only (DESIGN.md "Cumsum"): runs of kCumsumRun frames summed left to right, an inclusive
+// Kogge-Stone scan over the 64 run totals of a tile, a sequential carry over the kCumsumTiles tiles of a chunk and a
+// sequential carry over the chunks.  Reduce-then-scan, no workgroup waits for another: k_cumsum_totals (the chunk-local
+// last value of every chunk but the last -> tot), k_cumsum_carry (tot -> the running sum of tot, in place, one workgroup
+// per channel), k_cumsum_scan (recomputes the chunk, adds the carry, stores).  A signal of one chunk is one launch.
+// Strides in elements.  Returns the number of launches, -1 when the shape cannot be launched.
+constexpr int kCumsumRun = 16;    // L: frames a lane sums left to right
+constexpr int kCumsumTiles = 16;  // G: tiles (64 runs each) a workgroup carries through sequentially
+constexpr int kCumsumTile = 64 * kCumsumRun, kCumsumChunk = kCumsumTile * kCumsumTiles;
+struct CumsumArgs {
+    const void* x;  // element (n, c) at x[n * xfs + c * xcs]
+    int64_t xfs, xcs;
+    double* y;      // y[n + c * ycs]
+    int64_t ycs;
+    double* tot;    // [nch][tot_pitch] scratch, tot_pitch >= cumsum_totals(n)
+    int64_t tot_pitch;
+    int64_t n;
+    int32_t nch, x_f32;
+};
+// the chunk totals a channel of n frames needs: one for every chunk that has a chunk behind it
+constexpr int64_t cumsum_totals(int64_t n) { return n <= kCumsumChunk ? 0 : (n - 1) / kCumsumChunk; }
+int launch_cumsum(const CumsumArgs& a, hipStream_t st);
 }  // namespace so

@@ -279,6 +279,17 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = SO_F64;
             break;
         }
+        case SO_NODE_CUMSUM: {  // the running sum over one fixed summation tree (no reference counterpart; DESIGN.md "Cumsum")
+            const std::string where = "node " + std::to_string(i) + ": Cumsum ";
+            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a signal x of known, finite length (use `Until`)");
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            N.len = x.len;
+            N.nch = x.nch;
+            N.dtype = SO_F64;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -869,15 +880,16 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         out.push_back({r, add_expr(e)});
         return out;
     }
-    case SO_NODE_COMB: {
-        // a stage: the recurrence starts at frame 0, so the stage computes the frames [0, need) whoever reads it and a
-        // window reads its slice of that buffer (process_comb, stages.cpp)
+    case SO_NODE_COMB:
+    case SO_NODE_CUMSUM: {
+        // a stage: the recurrence (the sum) starts at frame 0, so the stage computes the frames [0, need) whoever reads it
+        // and a window reads its slice of that buffer (process_comb, stages.cpp)
         if (dry) {
             check_frames(N.kids[0], m.sf ? r.b + m.df : m.df + 1);
             out.push_back({r, mk_const(0.0, N.dtype)});
             return out;
         }
-        const int sid = stage_for(ni, ST_COMB);
+        const int sid = stage_for(ni, N.nd.kind == SO_NODE_CUMSUM ? ST_CUMSUM : ST_COMB);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

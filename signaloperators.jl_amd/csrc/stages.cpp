@@ -428,8 +428,10 @@ void Plan::process_sample_at(int sid) {
     }
 }
 
-// Comb: the recurrence starts at frame 0, so the stage computes the frames [0, need) of its buffer (base = 0) whatever
-// window reads it.  The child is demanded over the same frames and taken like SampleAt's table (stage_input).
+// Comb and Cumsum: the recurrence (the sum) starts at frame 0, so the stage computes the frames [0, need) of its buffer
+// (base = 0) whatever window reads it.  The child is demanded over the same frames and taken like SampleAt's table
+// (stage_input).  Cumsum owns one Float64 per (chunk that has a chunk behind it, channel) besides: the chunk totals, every
+// entry written by the execute that reads it (k_cumsum.hip), so nothing clears them.
 void Plan::process_comb(int sid) {
     const int ni = stages[sid].node;
     const int xk = nodes[ni].kids[0];
@@ -440,15 +442,20 @@ void Plan::process_comb(int sid) {
     stages[sid].base = stages[sid].in_base = 0;
     bufs[stages[sid].out_buf].frame0 = 0;
     stage_input(sid, lower(xk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[xk].dtype);
+    const bool cumsum = stages[sid].kind == ST_CUMSUM;
+    if (cumsum && cumsum_totals(need) > 0) {
+        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 8);
+        stages[sid].aux_buf = b;
+    }
     if (std::getenv("SIGOPS_DEBUG_PLAN"))
-        std::fprintf(stderr, "[sigops] Comb stage %d: D=%lld frames [0,%lld) x %d channels, x %s\n", sid, (long long)nodes[ni].nd.l0, (long long)need,
-                     nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+        std::fprintf(stderr, "[sigops] %s stage %d: %s%lld, frames [0,%lld) x %d channels, x %s\n", cumsum ? "Cumsum" : "Comb", sid, cumsum ? "chunk totals a channel " : "D=",
+                     (long long)(cumsum ? cumsum_totals(need) : nodes[ni].nd.l0), (long long)need, nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
 }
 
 void Plan::process_stage(int sid) {
     // NOTE: `stages` may grow while lowering the child; re-take references after.
     if (stages[sid].kind == ST_SAMPLEAT) return process_sample_at(sid);
-    if (stages[sid].kind == ST_COMB) return process_comb(sid);
+    if (stages[sid].kind == ST_COMB || stages[sid].kind == ST_CUMSUM) return process_comb(sid);
     int ni = stages[sid].node;
     Node& N = nodes[ni];
     const so_node_t& nd = N.nd;

@@ -424,6 +424,9 @@ def _streamable(x):
     if isinstance(x, S.CombSignal):
         S.error("BlockStream: Comb / Allpass would have to carry the D frames of its delay line from one push to the "
                 "next, and that is not built; not streamable")
+    if isinstance(x, S.CumsumSignal):
+        S.error("BlockStream: Cumsum / Integrate would have to carry its running sum (and its place in the summation "
+                "tree) from one push to the next, and that is not built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -257,8 +257,8 @@ def _demand(x, n, out, skip=0):
         # the table whole (any frame of it may be read), the positions for the frames the sink reaches
         _demand(x.signal, S.nframes(x.signal), out, 0)
         _demand(x.pos, capped(x.pos, n), out, skip)
-    elif isinstance(x, S.CombSignal):
-        # the recurrence starts at frame 0: the frames before a window are computed too
+    elif isinstance(x, (S.CombSignal, S.CumsumSignal)):
+        # the recurrence (the sum) starts at frame 0: the frames before a window are computed too
         _demand(x.signal, capped(x.signal, n), out, 0)
     elif isinstance(x, S.RampSignal):
         return
@@ -551,6 +551,11 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_COMB)
             r.update(l0=s.delay, d0=s.b0, d1=s.bD, d2=s.a, children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.CumsumSignal):
+            c = rec(s.signal)
+            r = common(s, K.NODE_CUMSUM)
+            r.update(children=(c,))
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

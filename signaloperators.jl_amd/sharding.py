@@ -36,18 +36,23 @@ def _refuse_sample_at(x, what):
         _refuse_sample_at(c, what)
 
 
-def _refuse_comb(x, what):
-    """a tree with a Comb node is not sharded: a rank's frames depend on every frame before them, and that is not built"""
-    if isinstance(x, S.CombSignal):
-        raise S.ErrorException(f"{what}: sharding a tree that contains Comb / Allpass over several GPUs is not built")
+# nodes whose frames depend on every frame before them: a rank cannot start in the middle, and handing the state on is not built
+_FROM_FRAME_0 = ((S.CombSignal, "Comb / Allpass"), (S.CumsumSignal, "Cumsum / Integrate"))
+
+
+def _refuse_from_frame_0(x, what):
+    """a tree with a Comb or a Cumsum node is not sharded: a rank's frames depend on every frame before them"""
+    for cls, name in _FROM_FRAME_0:
+        if isinstance(x, cls):
+            raise S.ErrorException(f"{what}: sharding a tree that contains {name} over several GPUs is not built")
     for c in getattr(x, "children", ()) or ():
-        _refuse_comb(c, what)
+        _refuse_from_frame_0(c, what)
 
 
 def shard_append(x, rank, world):
     """-> (sub-signal for this rank or None, first output frame, number of frames)"""
     _refuse_sample_at(x, "shard_append")
-    _refuse_comb(x, "shard_append")
+    _refuse_from_frame_0(x, "shard_append")
     if not isinstance(x, S.AppendSignals):
         raise S.ErrorException("shard_append needs an Append(...) root")
     kids = x.signals
@@ -70,7 +75,7 @@ def shard_time(x, rank, world, align=1):
 
     x = S._assignal(x)
     _refuse_sample_at(x, "shard_time")
-    _refuse_comb(x, "shard_time")
+    _refuse_from_frame_0(x, "shard_time")
     n = S.nframes(x)
     if n is None or S.isknowninf(n):
         raise S.ErrorException("shard_time needs a signal of known, finite length")
@@ -88,7 +93,7 @@ def shard_channels(x, rank, world):
     """channel slab [c0,c1) of a signal whose channels are independent"""
     x = S._assignal(x)
     _refuse_sample_at(x, "shard_channels")
-    _refuse_comb(x, "shard_channels")
+    _refuse_from_frame_0(x, "shard_channels")
     c0, c1 = block_range(x.nch, rank, world)
     if c1 <= c0:
         return None, c0, c1

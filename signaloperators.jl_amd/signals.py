@@ -559,6 +559,27 @@ class CombSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class CumsumSignal(AbstractSignal):
+    """`Cumsum(x)`: the running sum of `x` per channel, summed over one fixed tree (no reference counterpart;
+    include/sigops.h SO_NODE_CUMSUM, DESIGN.md "Cumsum").  It has the length, frame rate and channels of `x` and is
+    Float64."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x):
+        self.signal = x
+        self.children = (x,)
+        self.fs = x.fs
+        self.nch = x.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -928,6 +949,10 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return CombSignal(ToFramerate(x.signal, fs, bs), x.delay, x.b0, x.bD, x.a)
+    if isinstance(x, CumsumSignal):  # Comb's two rules: the sum runs over frames, whatever rate they have
+        if known:
+            return _resample(x, fs, bs)
+        return CumsumSignal(ToFramerate(x.signal, fs, bs))
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1179,6 +1204,42 @@ def Allpass(*args):
         error("Allpass(x, d, g) expected: Comb with direct = -g, feedforward = 1")
     g = args[2]
     return _Comb("Allpass (Comb)", args[0], args[1], -g if _real_number(g) else g, 1.0, g)
+
+
+# --------------------------------------------------------------------------
+# Cumsum / Integrate: running sums (no reference counterpart)
+def _Cumsum(x, what="Cumsum"):
+    """`what` names the construct in a refusal: "Cumsum", or "Integrate (Cumsum)" for the wrapper"""
+    x = _assignal(x)
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal x must have a known, finite length (use `Until`): the sum starts at frame 0")
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    return CumsumSignal(x)
+
+
+Cumsum = Curried(_Cumsum)
+Cumsum.__doc__ = """`Cumsum(x)`, piped `x | Cumsum`: the running sum, frame n of a channel is `x[0] + ... + x[n]` in Float64 -- the phase
+of an oscillator whose frequency `x` gives, brown noise from white.  A parallel sum rounds differently from a loop, so
+the node fixes ONE summation tree that depends on the frame index only (runs of 16 frames left to right, a Kogge-Stone
+scan over the 64 runs of a tile, sequential carries over the 16 tiles of a chunk and over the chunks; DESIGN.md
+"Cumsum", tests/cumsum_ref.py): a window, a `stream` block and the whole sink give the same bits, and the error of
+frame n stays within about (40 + chunks) * 2**-53 * sum(|x[:n + 1]|).  `x` must have a known, finite length.  `stream` over
+the node recomputes the frames before every block (quadratic in the length, as over `Comb`): stream what follows the
+node.  `BlockStream` and multi-GPU shards refuse the node."""
+
+
+def _Integrate(x):
+    x = _assignal(x)
+    if x.fs is None:
+        error("Integrate (Cumsum): the signal x needs a frame rate: the integral is the running sum times 1 / framerate (use `Cumsum`, or `ToFramerate`)")
+    return _OperateOn(MUL, [_Cumsum(x, "Integrate (Cumsum)"), NumberSig(1.0 / x.fs)])
+
+
+Integrate = Curried(_Integrate)
+Integrate.__doc__ = """`Integrate(x)`, piped `x | Integrate`: the integral of `x` over time, `Cumsum(x)` times the Float64 constant
+`1.0 / framerate(x)` (one more rounding a sample, through the map path)."""
 
 
 # --------------------------------------------------------------------------

@@ -45,6 +45,11 @@ def POS(kind):
 
 cases = {
     "copy (Until)": lambda: X | so.Until(n * so.frames),
+    # `Cumsum(x)` (include/sigops.h SO_NODE_CUMSUM, csrc/k_cumsum.hip): reduce-then-scan, two reads and one write per sample
+    # -- 1.5 x the bytes of the copy row above, its yardstick; `vco`: a 2048-frame wavetable read at the running sum of a
+    # per-frame increment (1.37 frames +- 20 %, a different trajectory per channel), `SampleAt` over `Cumsum`
+    "cumsum": lambda: so.Cumsum(X),
+    "vco": lambda: so.SampleAt(so.Signal(x[:2048], fs), so.Cumsum(so.Signal((1.37 + 0.2 * x.t().clamp(-1.0, 1.0).to(torch.float64)).t(), fs)), wrap=True),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
     "Amplify(sin)": lambda: X | so.Amplify(tone) | so.Until(n * so.frames),
     "Mix(x, y)": lambda: so.Mix(X, Y),
