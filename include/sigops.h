@@ -398,8 +398,16 @@ typedef enum so_counter {
     SO_COUNTER_GRAPH_REPLAYS = 0,   /* executes replayed from the captured launch graph            */
     SO_COUNTER_GRAPH_CAPTURES = 1,  /* times the launch sequence was captured                      */
     SO_COUNTER_DIRECT_EXECUTES = 2, /* executes issued launch by launch                            */
-    SO_COUNTER_FUSED_MFMAS_PER_BLOCK = 3 /* fp64 MFMAs the fused resampler + IIR kernel issues per block of 16 outputs x 16
-                                          * rows (0: the plan has no such launch): what a matrix-pipe roofline is priced with */
+    SO_COUNTER_FUSED_MFMAS_PER_BLOCK = 3, /* fp64 MFMAs the fused resampler + IIR kernel issues per block of 16 outputs x 16
+                                           * rows (0: the plan has no such launch): what a matrix-pipe roofline is priced with */
+    SO_COUNTER_WPROJ = 4, /* 1: the fused resampler + IIR kernel takes the state at the end of a range's warm-up from one
+                           * matrix product wherever the warm-up lies inside the array, instead of walking it (0: it walks) */
+    /* geometry of the plan's first fused resampler + IIR launch (0 where there is none), for tests that place samples: */
+    SO_COUNTER_RSOS_RANGE_PERIODS = 5,  /* periods per time range                                                    */
+    SO_COUNTER_RSOS_WARMUP_PERIODS = 6, /* warm-up periods in front of every range                                   */
+    SO_COUNTER_RSOS_PERIOD_INPUTS = 7,  /* input frames per period                                                   */
+    SO_COUNTER_WPROJ_FRAMES = 8,        /* frames a projected warm-up reads                                          */
+    SO_COUNTER_WPROJ_FIRST = 9          /* the first of them, counted from the warm-up's first period (may be < 0)   */
 } so_counter_t;
 int64_t so_plan_counter(const so_plan_t* plan, int32_t which);
 
@@ -528,6 +536,16 @@ int32_t so_design_resample_arbitrary(double rate, int32_t nphi, double* h, int32
 int32_t so_resample_positions(double fs_in, double fs_out, double rate, int32_t nphi, const double* h,
                               int32_t hlen, int64_t n_out, int64_t* j, int32_t* p, double* alpha,
                               int64_t* nfix, int64_t* nbaked);
+
+/* Diagnostic, host only: the matrix V of the fused resampler + IIR kernel's projected warm-up -- the state the cascade
+ * `sos` ([nsec][6] rows b0 b1 b2 1 a1 a2, times `gain`) is left in by `wp` periods of the kernel's block walk from rest
+ * (blocks of 16 outputs; block g of a period resamples with taps tab[g][kk][16] over the kw frames that end at frame
+ * jend[g] of the period, M input frames per period) is V . in.  v: [12][capacity] row-major, row d = state d of the DF2T
+ * cascade (rows from 2 nsec on are zero); *k columns are used, column o is frame *j0 + o counted from the first input of
+ * the first period.  SO_ERR_INVALID if capacity is too small (*k says what is needed). */
+int32_t so_rsos_wproj_matrix(const double* sos, int32_t nsec, double gain, const double* tab, const int32_t* jend,
+                             int32_t ngroups, int32_t kw, int64_t m, int32_t wp, double* v, int32_t capacity,
+                             int32_t* j0, int32_t* k);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

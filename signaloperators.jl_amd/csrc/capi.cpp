@@ -230,4 +230,25 @@ int32_t so_resample_positions(double fs_in, double fs_out, double rate, int32_t 
     return so::resample_positions(fs_in, fs_out, rate, nphi, h, hlen, n_out, j, p, alpha, nfix, nbaked);
 }
 
+int32_t so_rsos_wproj_matrix(const double* sos, int32_t nsec, double gain, const double* tab, const int32_t* jend,
+                             int32_t ngroups, int32_t kw, int64_t m, int32_t wp, double* v, int32_t capacity,
+                             int32_t* j0, int32_t* k) {
+    if (!sos || !tab || !jend || !v || !j0 || !k || nsec < 1 || nsec > 6 || ngroups < 1 || kw < 1 || m < 1 || wp < 1)
+        return set_err(SO_ERR_INVALID, "so_rsos_wproj_matrix: bad arguments");
+    // (sizes the kernel can have: at most 256 blocks per period, windows of a few thousand frames -- and a span that stays an int)
+    if (ngroups > 256 || kw > 4096 || capacity < 0 || m > (1 << 20) || wp > (1 << 20) || (int64_t)wp * m + kw > (1 << 22))
+        return set_err(SO_ERR_INVALID, "so_rsos_wproj_matrix: period, window or warm-up too long");
+    for (int g = 0; g < ngroups; ++g)
+        if (jend[g] < -(1 << 22) || jend[g] > (1 << 22)) return set_err(SO_ERR_INVALID, "so_rsos_wproj_matrix: window end out of range");
+    std::vector<double> V;
+    int jj = 0, K = 0;
+    so::rsos_wproj_matrix_sos(sos, nsec, gain, tab, jend, ngroups, kw, m, wp, V, jj, K);
+    *j0 = jj;
+    *k = K;
+    if (K > capacity) return set_err(SO_ERR_INVALID, "so_rsos_wproj_matrix: capacity too small");
+    for (int d = 0; d < 12; ++d)
+        for (int o = 0; o < K; ++o) v[(size_t)d * capacity + o] = V[(size_t)d * K + o];
+    return SO_OK;
+}
+
 }  // extern "C"

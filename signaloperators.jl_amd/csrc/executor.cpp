@@ -1366,6 +1366,21 @@ int64_t plan_counter(const Plan* P, int which) {
             if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.ks + 14;
         return 0;
     }
+    case SO_COUNTER_WPROJ: {  // k_rsos: the warm-up of a range as one product where it lies inside the array (RsSos::wproj)
+        for (const Stage& S : P->stages)
+            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.wproj;
+        return 0;
+    }
+    case SO_COUNTER_RSOS_RANGE_PERIODS:
+    case SO_COUNTER_RSOS_WARMUP_PERIODS:
+    case SO_COUNTER_RSOS_PERIOD_INPUTS:
+    case SO_COUNTER_WPROJ_FRAMES:
+    case SO_COUNTER_WPROJ_FIRST:
+        for (const Stage& S : P->stages)
+            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0)
+                return which == SO_COUNTER_RSOS_RANGE_PERIODS ? S.rs.pr : which == SO_COUNTER_RSOS_WARMUP_PERIODS ? S.rs.wp
+                     : which == SO_COUNTER_RSOS_PERIOD_INPUTS ? S.rs.M : which == SO_COUNTER_WPROJ_FRAMES ? S.rs.wk : S.rs.wj0;
+        return 0;
     default: return -1;
     }
 }

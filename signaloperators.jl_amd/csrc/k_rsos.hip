@@ -25,6 +25,8 @@
 // (single writer each), never through barriers: the chain wave must not wait for anybody but its x block.
 // A range starts wp periods before its first output from zero state (||A^(wp L)|| < 2^-70: the planner's warm
 // start) and stores nothing there.
+// Where a group's warm-ups lie wholly inside the array they are not walked: the state at their end is one product with a
+// host-built matrix (rsos_wproj_* below).
 #include "kcommon.h"
 #include "kstage.h"
 
@@ -292,6 +294,7 @@ __device__ __forceinline__ void rsos_widen(uint32_t slot, uint32_t row_bytes, in
 }
 
 constexpr int kRsosFlagLdp = 0, kRsosFlagYrd = 4, kRsosFlagXseq = 16, kRsosFlagSseq = 48, kRsosFlagXh = 49, kRsosFlagLnd = 52, kRsosFlags = 56;
+constexpr int kRsosFlagWp = 37;  // (37 .. 46: a y wave's share of a projected warm-up is in its slot -- rsos_wproj_y)
 // Helper geometry (RsSos::help; 12 waves, taps in registers): the y waves of residues kRsosHres[0..2] -- one on each of SIMDs 1 .. 3 --
 // hand the y wave that shares the chain's SIMD (residue kRsosHelper) their X block instead of computing D . X themselves:
 // 68 / 68 / 68 / 66 MFMAs per round of ten blocks on the four SIMDs instead of 72 / 72 / 72 / 54.  (Not the chain wave: its
@@ -314,6 +317,9 @@ struct RsosShared {
     int flags[kRsosFlags];
     int jend[kRsosMaxGroups];
     RsCtl ctl;
+    // per sequence group (rsos_body, between its two barriers): the warm-up periods this group WALKS -- g.wp, or 0 where the
+    // state at their end comes from the projection (RsSos::wproj, rsos_wproj_*) -- every role takes its geometry from this one
+    int wpe, proj;
 };
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -403,7 +409,7 @@ __device__ __forceinline__ RsosGroup rsos_group(const SO_LDS RsosShared* sh, int
     const int ct = uni(g.ct), rgs = uni(g.rgs);
     const int64_t ncg = uni(g.nch) / ct;
     const int64_t pr = rfl64(g.pr), M = rfl64(g.M), L = rfl64(g.L);
-    const int wp = uni(g.wp), ulo = uni(g.ulo);
+    const int wp = uni(sh->wpe), ulo = uni(g.ulo);
     RsosGroup q;
     q.cg = (int)(G % ncg);
     const int64_t r0 = (G / ncg) * rgs;
@@ -432,7 +438,7 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
     const SO_LDS RsSos& g = sh->g;
     const int ngroups = uni(g.ngroups);
     const RsosLds l = rsos_carve(dyn, uni(g.cyc) > 0 ? 0 : ngroups * uni(g.ks) * 64, uni(g.rpitch), NX, rsos_nss(NY));
-    const int NB = (uni(g.wp) + (int)rfl64(g.pr)) * ngroups;
+    const int NB = (uni(sh->wpe) + (int)rfl64(g.pr)) * ngroups;
     const double SO_GLB* mats = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats);
     long long* trace = (long long*)rfl64((int64_t)(uintptr_t)g.trace);
     const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
@@ -465,6 +471,9 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
     //                         Addresses, the counter's readfirstlane and the counter value therefore go into the gap
     //                         in front of the first MFMA; under it are scalar and LDS instructions only.
     v4d sA = v4d{0.0, 0.0, 0.0, 0.0}, sB = v4d{0.0, 0.0, 0.0, 0.0};  // state entering the even / odd block
+    // (the state entering block 0 is what state slot 0 holds: zeros -- rsos_body --, or the projected warm-up's, rsos_wproj_chain)
+#pragma unroll
+    for (int v = 0; v < NK; ++v) sA[v] = l.ss[v * 64 + lane];
     // D . x of the even / odd block, each in the four register pairs an MFMA takes as its C operand (rows 12 .. 15 of the
     // state do not exist: the fourth pair is never read back and may hold anything -- it is never written either)
     v4d dA = v4d{0.0, 0.0, 0.0, 0.0}, dB = v4d{0.0, 0.0, 0.0, 0.0};
@@ -644,7 +653,7 @@ __device__ __attribute__((noinline)) void rsos_loader(RsosShared* sh_, double* d
     const RsosLds l = rsos_carve(dyn, uni(g.cyc) > 0 ? 0 : ngroups * uni(g.ks) * 64, rpitch, NX, rsos_nss(NY));
     const int ct = uni(g.ct);
     const int M = (int)rfl64(g.M);
-    const int NP = uni(g.wp) + (int)rfl64(g.pr);
+    const int NP = uni(sh->wpe) + (int)rfl64(g.pr);
     const int ulo = uni(g.ulo);
     const int64_t n_in = rfl64(g.n_in);
     long long* trace = (long long*)rfl64((int64_t)(uintptr_t)g.trace);
@@ -1161,6 +1170,153 @@ __device__ __attribute__((noinline)) void rsos_loader(RsosShared* sh_, double* d
     }
 }
 
+// =========================== the warm-up as one product ===========================
+// A range starts wp periods early from rest, and of those periods nothing is kept but the state at their end -- a linear
+// function of the frames their windows read: s_0 = V . in (stages.cpp, rsos_wproj_matrix: the very map of the walk; V behind the
+// block matrices in RsSos::mats, as A operands).  Where all of a group's warm-ups lie inside the array on the loader's fast
+// path the group does not walk them (RsosShared::wpe = 0: loader, y waves and chain start at the first stored period):
+//     y waves   each a contiguous slice of V's k-steps; B operands straight from the array (row n16, two adjacent frames per
+//               lane and load: k-steps 2 c and 2 c + 1 take frames 8 c + 2 (lane >> 4) and + 1), one accumulator tile, left in
+//               state slot 1 + yi (nobody writes the state slots before the chain runs) behind a single-writer counter;
+//     chain     sums the tiles, adds the fused sine's share (cos a_r (V . sin) + sin a_r (V . cos), a_r the phase at the row's
+//               first frame), and leaves s_0 in state slot 0, where its recurrence starts from.
+// A non-finite frame in the span makes s_0 non-finite, the recurrence keeps it so, and the range is noted as one whose walk
+// ended non-finite.  Frames past the span (the k-step padding) are never loaded: their operand is 0.0.
+typedef double v2d_a8 __attribute__((ext_vector_type(2), aligned(8)));
+
+// this group projects its warm-ups (one thread, once per group; wave-uniform for everybody through RsosShared::proj)
+__device__ __forceinline__ bool rsos_wproj_group(const RsosShared& sh, int64_t G) {
+    const RsSos& g = sh.g;
+    const DCarrier& C0 = sh.ctl.car[0];
+    if (!g.wproj || g.src32 || g.arr2 || g.fuse < -1 || g.ct < 8) return false;
+    if (!(C0.base != nullptr && C0.vec_ok && C0.dtype == SO_F64) || (C0.df & 1)) return false;  // (the loader's `single`)
+    const int64_t ncg = g.nch / g.ct;
+    const int64_t r0 = (G / ncg) * g.rgs, r1 = r0 + g.rgs - 1;
+    if (r1 >= g.nranges || r0 * g.pr < g.wp) return false;  // (rows without a range; outputs below output 0)
+    if (g.store_lo > r0 * g.pr * g.L) return false;         // (a window that begins inside the group's first stored blocks)
+    const int64_t lo_ok = C0.a > 0 ? C0.a : 0, hi_ok = C0.b < g.n_in ? C0.b : g.n_in;
+    const int64_t f0 = (r0 * g.pr - g.wp) * g.M + g.wj0, f1 = (r1 * g.pr - g.wp) * g.M + g.wj0 + g.wk;
+    return f0 >= lo_ok && f1 <= hi_ok;
+}
+
+template <int NY>
+__device__ __attribute__((noinline)) void rsos_wproj_y(RsosShared* sh_, double* dyn, int64_t G_, int yi_) {
+    constexpr int NX = 2 * NY + 1;
+    const int lane = threadIdx.x & 63;
+    SO_LDS RsosShared* const sh = (SO_LDS RsosShared*)rsos_lds_ptr(sh_);
+    const int64_t G = rfl64(G_);
+    const int yi = uni(yi_);
+    const SO_LDS RsSos& g = sh->g;
+    const RsosLds l = rsos_carve(dyn, uni(g.cyc) > 0 ? 0 : uni(g.ngroups) * uni(g.ks) * 64, uni(g.rpitch), NX, rsos_nss(NY));
+    const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
+    const int ct = uni(g.ct), K = uni(g.wk);
+    const int npairs = (K + 7) >> 3;
+    const int c0 = (int)((int64_t)yi * npairs / NY), c1 = (int)((int64_t)(yi + 1) * npairs / NY);
+    const double SO_GLB* const V = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats) + 14 * 64 + lane;
+    const SO_LDS DCarrier& C0 = sh->ctl.car[0];
+    const int64_t ncg = uni(g.nch) / ct;
+    const int gq = lane >> 4, n16 = lane & 15;
+    // this lane's row: channel n16 % ct of range r0 + n16 / ct, from the first frame its warm-up reads
+    const int64_t r = (G / ncg) * uni(g.rgs) + n16 / ct;
+    const int64_t f0 = (r * rfl64(g.pr) - uni(g.wp)) * rfl64(g.M) + uni(g.wj0);
+    const double SO_GLB* const row = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)C0.base) +
+                                     ((int64_t)((int)(G % ncg) * ct + n16 % ct) * rfl64(C0.cstride) + rfl64(C0.df) + f0 + 2 * gq);
+    // eight pairs of k-steps per batch, two batches in flight; whole batches inside the span without a predicate, what is
+    // left of the slice -- and of the span: its last pair may be a part of one -- in one batch with them
+    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+    auto mm = [&](const double (&a)[16], const v2d (&b)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[2 * i], b[i][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[2 * i + 1], b[i][1], acc, 0, 0, 0);
+        }
+    };
+    auto load = [&](int c, double (&a)[16], v2d (&b)[8]) __attribute__((always_inline)) {
+        const double SO_GLB* const vp = V + (size_t)c * 128;
+        const double SO_GLB* const rp = row + (size_t)c * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            a[2 * i] = vp[i * 128];
+            a[2 * i + 1] = vp[i * 128 + 64];
+            b[i] = *(const v2d_a8 SO_GLB*)(rp + 8 * i);
+        }
+    };
+    double aA[16], aB[16];
+    v2d bA[8], bB[8];
+    const int c1f = min(c1, K >> 3);  // (pairs below this one lie wholly inside the span)
+    const int nfull = c1f > c0 ? (c1f - c0) >> 3 : 0;
+    if (nfull > 0) {
+        load(c0, aA, bA);
+        for (int n = 0; n < nfull; n += 2) {
+            const int c = c0 + 8 * n;
+            if (n + 1 < nfull) load(c + 8, aB, bB);
+            mm(aA, bA);
+            if (n + 2 < nfull) load(c + 16, aA, bA);
+            if (n + 1 < nfull) mm(aB, bB);
+        }
+    }
+    {
+        const int c = c0 + 8 * nfull;  // (c1 - c <= 8)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int cc = c + i;
+            aA[2 * i] = aA[2 * i + 1] = 0.0;
+            bA[i] = v2d{0.0, 0.0};
+            if (cc < c1) {  // (wave-uniform)
+                aA[2 * i] = V[(size_t)(2 * cc) * 64];
+                aA[2 * i + 1] = V[(size_t)(2 * cc + 1) * 64];
+                const int f = 8 * cc + 2 * gq;
+                if (f + 1 < K) bA[i] = *(const v2d_a8 SO_GLB*)(row + 8 * cc);
+                else if (f < K) bA[i][0] = row[8 * cc];  // (never a frame past the span: it may lie outside the array)
+            }
+        }
+        mm(aA, bA);
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) l.ss[(1 + yi) * 192 + v * 64 + lane] = acc[v];
+    flag_st(fl_base + 4 * (kRsosFlagWp + yi), 1);
+}
+
+template <int NY>
+__device__ __attribute__((noinline)) void rsos_wproj_chain(RsosShared* sh_, double* dyn, int64_t G_) {
+    constexpr int NX = 2 * NY + 1;
+    const int lane = threadIdx.x & 63;
+    SO_LDS RsosShared* const sh = (SO_LDS RsosShared*)rsos_lds_ptr(sh_);
+    const int64_t G = rfl64(G_);
+    const SO_LDS RsSos& g = sh->g;
+    const RsosLds l = rsos_carve(dyn, uni(g.cyc) > 0 ? 0 : uni(g.ngroups) * uni(g.ks) * 64, uni(g.rpitch), NX, rsos_nss(NY));
+    const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
+    const int ct = uni(g.ct), fuse = uni(g.fuse);
+    const int gq = lane >> 4, n16 = lane & 15;
+    double s[3] = {0.0, 0.0, 0.0};
+    if (fuse >= 0) {  // the sine's share: what does not wait for the y waves first
+        const SO_LDS DCarrier& C0 = sh->ctl.car[0];
+        const DLeaf leaf0 = leaf_uniform(sh_->ctl.leaves[min(kCtlLeaves - 1, max(0, uni(C0.slot_leaf[0])))]);
+        const int64_t ncg = uni(g.nch) / ct;
+        const int64_t r = (G / ncg) * uni(g.rgs) + n16 / ct;
+        const int64_t f0 = (r * rfl64(g.pr) - uni(g.wp)) * rfl64(g.M) + uni(g.wj0);
+        const double2 sc = rsos_sine_at(f0 + leaf0.df + 1, leaf0.v0, leaf0.v1, leaf0.v2, leaf0.flag);
+        const double SO_GLB* const W = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats) + 14 * 64 + (size_t)((uni(g.wk) + 7) >> 3) * 128;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const double t = fma(sc.y, W[gq + 4 * v], sc.x * W[16 + gq + 4 * v]);
+            s[v] = fuse == 2 ? -t : t;
+        }
+    }
+    int spins = 0;
+    for (;;) {
+        const int f = lane < NY ? flag_ld(fl_base + 4 * (kRsosFlagWp + lane)) : 1;
+        if (wave_min(f, NY) >= 1) break;
+        SO_SPIN_PAUSE(spins, 1, 1 << 22);
+    }
+#pragma unroll
+    for (int yi = 0; yi < NY; ++yi)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) s[v] += l.ss[(1 + yi) * 192 + v * 64 + lane];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) l.ss[v * 64 + lane] = s[v];
+}
+
 // =========================== helper wave ===========================
 // (16-wave geometry with RsSos::help: wave 12, the fourth wave of the chain's SIMD.)  D . X of the blocks whose y waves
 // hand over X itself -- residues kRsosHres0/1/2 of every round of NY blocks, in block order: four MFMAs that depend on
@@ -1173,7 +1329,7 @@ __device__ __attribute__((noinline)) void rsos_helper(RsosShared* sh_, double* d
     SO_LDS RsosShared* const sh = (SO_LDS RsosShared*)rsos_lds_ptr(sh_);
     const SO_LDS RsSos& g = sh->g;
     const RsosLds l = rsos_carve(dyn, 0, uni(g.rpitch), NX, rsos_nss(NY));
-    const int NB = (uni(g.wp) + (int)rfl64(g.pr)) * uni(g.ngroups);
+    const int NB = (uni(sh->wpe) + (int)rfl64(g.pr)) * uni(g.ngroups);
     const double SO_GLB* mats = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats);
     const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
     const int debug = uni(g.debug);
@@ -1231,7 +1387,7 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
     const SO_LDS RsSos& g = sh->g;
     const int ngroups = uni(g.ngroups), rpitch = uni(g.rpitch), RING = uni(g.ring);
     const RsosLds l = rsos_carve(dyn, CYC > 0 ? 0 : ngroups * KS * 64, rpitch, NX, rsos_nss(NY));
-    const int ct = uni(g.ct), wp = uni(g.wp), debug = uni(g.debug);
+    const int ct = uni(g.ct), wp = uni(sh->wpe), debug = uni(g.debug);
     const int M = (int)rfl64(g.M);
     const int NB = (wp + (int)rfl64(g.pr)) * ngroups;
     constexpr int kw = 4 * KS;
@@ -1728,9 +1884,19 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
         __syncthreads();  // (the previous group's LDS traffic is over; the first time: the tables are in place)
         if (threadIdx.x < kRsosFlags) sh.flags[threadIdx.x] = 0;
         if (threadIdx.x < 192) ss[threadIdx.x] = 0.0;  // s_0 = 0
+        if (threadIdx.x == 0) {
+            // (a group that projects its warm-ups walks none: the state entering block 0 is not there until the chain wave has
+            //  made it -- the state counter says "before block 0" and the y wave of block 0 waits like any other)
+            const bool pj = NW != 16 && NW != 17 && rsos_wproj_group(sh, G);  // (the twelve- and eight-wave geometries)
+            sh.proj = pj ? 1 : 0;
+            sh.wpe = pj ? 0 : g.wp;
+            if (pj) sh.flags[kRsosFlagSseq] = -1;
+        }
         __syncthreads();
+        const bool proj = sh.proj != 0;
         if (wave == 0) {
             if (!(g.debug & 64)) {
+                if (proj) rsos_wproj_chain<NY>(&sh, lds_raw, G);
                 const int nk = (g.debug & 131072) ? 3 : (2 * g.nsec + 3) / 4;
                 if (nk <= 1) rsos_chain<NY, 1>(&sh, lds_raw, G);
                 else if (nk == 2) rsos_chain<NY, 2>(&sh, lds_raw, G);
@@ -1809,6 +1975,7 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
             //  SIMDs -- residues 0 3 7 | 1 4 8 | 2 5 9 on SIMDs 1 | 2 | 3, 6 next to the chain.  Three consecutive residues on one
             //  SIMD, tried for the helper geometry, cost the plain 12-wave form 4 %: the chain takes the blocks in order.)
             const int yi = NW == 16 ? (wave < 4 ? wave - 1 : wave < 8 ? wave - 2 : wave < 12 ? wave - 3 : 9) : wave - (wave > 4 ? 2 : 1);
+            if (proj) rsos_wproj_y<NY>(&sh, lds_raw, G, yi);
             if constexpr (sizeof(TO) == 4 && CYC > 0) {
                 if (g.f32m) {
                     rsos_ywave<KS, NY, NL, TO, CYC, true, HW>(&sh, lds_raw, G, yi);

@@ -21,6 +21,9 @@ int tf_zero_input(const double* b, int nb, const double* a, int na, const double
 int design_resample_rational(int64_t num, int64_t den, std::vector<double>& h, std::string& err);
 int design_resample_arbitrary(double rate, int nphi, std::vector<double>& h, std::string& err);
 
+// (stages.cpp) the fused resampler + IIR kernel's warm-up as a matrix: V[12][K], see there
+void rsos_wproj_matrix_sos(const double* sos, int nsec, double gain, const double* tab, const int* jend, int ngroups, int kw, int64_t M, int wp,
+                           std::vector<double>& V, int& j0, int& K);
 int resample_positions(double fs_in, double fs_out, double rate, int nphi, const double* h, int hlen,
                        int64_t n_out, int64_t* j, int32_t* p, double* alpha, int64_t* nfix, int64_t* nbaked);
 

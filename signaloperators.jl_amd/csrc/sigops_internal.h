@@ -409,11 +409,15 @@ struct RsSos {
     int32_t debug;        // ablation bits (SIGOPS_RSOS_DEBUG): 1 no stores, 2 no gain, 4 chain does not wait for x, 8 y waves not for states, 16 nor for input, 32 loader not for ring space
     int32_t cyc;          // > 0: a y wave's blocks cycle through cyc phase groups whose taps it keeps in registers; 0: tap table in LDS
     int32_t arr2;         // the fast path's step takes a SECOND array as its operand (DCarrier::base2): the loader's A2 instantiation
-    int32_t pad_;
+    int32_t wproj;        // a range's warm-up is not walked where the whole of it lies inside the array: its end state is V . in, a
+                          // [2 nsec x wk] matrix (behind the 14 operands of `mats`) times the wk frames the warm-up blocks read
+    int32_t wk;           // ... frames the warm-up's windows span (V's columns; the table is padded to a multiple of 8)
+    int32_t wj0;          // ... the first of them, relative to the first input of the range's first warm-up period
     int64_t out_pitch;
     int64_t store_lo;     // outputs below this one are not stored (a window's warm-up: the kernel's output 0 is where the
                           // resampler stage's warm start begins, the result where the window does)
     const double* mats;   // [14][64] MFMA operands: D k-steps 0..3, A^16 k-steps 0..2, T^T k-steps 0..3, C^T k-steps 0..2
+                          // wproj: + [wk8 / 4][64] V as A operands (k-step 2 c + e, lane l: V[l & 15][8 c + 2 (l >> 4) + e]) + [2][16] V . sin, V . cos
     int32_t* bad;         // per channel: first range that ended in a non-finite state, or null
     long long* trace;     // SIGOPS_RSOS_TRACE: [16 waves][kRsosTraceIters][8] cycle stamps of workgroup 0, or null
     uint32_t* err;        // host-mapped word of the plan: a wait between the kernel's waves that did not end writes 1 here and the

@@ -1721,10 +1721,13 @@ void Plan::batch_sos_stages() {
 // Values: the resampled samples are K3's (same products, same order); the IIR's differ from the sequential
 // recurrence by the rounding of a different association, ~1e-14 norm-wise for cascades that pass the planner's
 // conditioning probes (the others never get here: they run k_sos_exact).
-static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
+// columns of [T C; D A^16]: the DF2T recurrence over one block from a unit input / a unit state
+static void rsos_block_columns(const SosCoefs& cf, std::vector<double>& Tm, std::vector<double>& Cm, std::vector<double>& Dm, std::vector<double>& Am) {
     const int ns = cf.nsec, D = 2 * ns, B = 16;
-    // columns of [T C; D A^16]: the DF2T recurrence over one block from a unit input / a unit state
-    std::vector<double> Tm(B * B, 0.0), Cm(B * 12, 0.0), Dm(12 * B, 0.0), Am(12 * 12, 0.0);
+    Tm.assign(B * B, 0.0);
+    Cm.assign(B * 12, 0.0);
+    Dm.assign(12 * B, 0.0);
+    Am.assign(12 * 12, 0.0);
     for (int col = 0; col < B + D; ++col) {
         std::vector<double> st(D, 0.0);
         if (col >= B) st[col - B] = 1.0;
@@ -1745,6 +1748,12 @@ static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
             else Am[d * 12 + (col - B)] = st[d];
         }
     }
+}
+
+static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
+    const int B = 16;
+    std::vector<double> Tm, Cm, Dm, Am;
+    rsos_block_columns(cf, Tm, Cm, Dm, Am);
     // MFMA operand form: every matrix as Mat[lane & 15][4 v + (lane >> 4)] per k-step v
     mats.assign((size_t)14 * 64, 0.0);
     for (int lane = 0; lane < 64; ++lane) {
@@ -1759,6 +1768,68 @@ static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
             }
         }
     }
+}
+
+// The state a range's warm-up leaves, as a matrix (k_rsos.hip, rsos_wproj_*).  The kernel walks the wp warm-up periods of a
+// range block by block from rest -- S' = D . X_b + A^16 . S with X_b = Tap_g(b)^T . Win_b -- and keeps nothing of them but the
+// state at their end, which is linear in the frames the windows read:
+//     s_0 = sum_b (A^16)^(NB - 1 - b) . D . Tap_g(b)^T . Win_b = V . in,      NB = wp ngroups blocks,
+// the very map of that walk: same block matrices, same (trimmed) tap table, same truncation at wp periods.  V[12][K], row d =
+// state d (rows from 2 nsec on: zero), column o = frame j0 + o relative to the first input of the first warm-up period; K is
+// the span the windows reach, nothing more.  Accumulated in long double (a column sums up to wp ngroups terms).
+static void rsos_wproj_matrix(const SosCoefs& cf, const double* tab, const int* jend, int ngroups, int kw, int64_t M, int wp, std::vector<double>& V,
+                       int& j0, int& K) {
+    std::vector<double> Tm, Cm, Dm, Am;
+    rsos_block_columns(cf, Tm, Cm, Dm, Am);
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    for (int p = 0; p < wp; p += std::max(1, wp - 1))
+        for (int gi = 0; gi < ngroups; ++gi) {
+            const int64_t o = (int64_t)p * M + jend[gi] - (kw - 1);
+            lo = std::min(lo, o);
+            hi = std::max(hi, o + kw - 1);
+        }
+    j0 = (int)lo;
+    K = (int)(hi - lo + 1);
+    std::vector<long double> acc((size_t)12 * K, 0.0L), P(12 * 16), Q(12 * 16);
+    for (int i = 0; i < 12 * 16; ++i) P[i] = Dm[i];
+    for (int64_t b = (int64_t)wp * ngroups - 1; b >= 0; --b) {  // P = (A^16)^(NB - 1 - b) . D
+        const int gi = (int)(b % ngroups);
+        const int64_t o0 = (b / ngroups) * M + jend[gi] - (kw - 1) - lo;
+        for (int kk = 0; kk < kw; ++kk) {
+            const double* tp = tab + ((size_t)gi * kw + kk) * 16;
+            for (int d = 0; d < 12; ++d) {
+                long double a = 0.0L;
+                for (int t = 0; t < 16; ++t) a += P[d * 16 + t] * (long double)tp[t];
+                acc[(size_t)d * K + o0 + kk] += a;
+            }
+        }
+        if (b == 0) break;
+        for (int d = 0; d < 12; ++d)
+            for (int t = 0; t < 16; ++t) {
+                long double a = 0.0L;
+                for (int e = 0; e < 12; ++e) a += (long double)Am[d * 12 + e] * P[e * 16 + t];
+                Q[d * 16 + t] = a;
+            }
+        P.swap(Q);
+    }
+    V.resize(acc.size());
+    for (size_t i = 0; i < acc.size(); ++i) V[i] = (double)acc[i];
+}
+
+// (the C-ABI's diagnostic: sections as [nsec][6] rows b0 b1 b2 1 a1 a2)
+void rsos_wproj_matrix_sos(const double* sos, int nsec, double gain, const double* tab, const int* jend, int ngroups, int kw, int64_t M, int wp,
+                           std::vector<double>& V, int& j0, int& K) {
+    SosCoefs cf{};
+    cf.nsec = nsec;
+    cf.gain = gain;
+    for (int f = 0; f < nsec; ++f) {
+        cf.b0[f] = sos[6 * f + 0];
+        cf.b1[f] = sos[6 * f + 1];
+        cf.b2[f] = sos[6 * f + 2];
+        cf.a1[f] = sos[6 * f + 4];
+        cf.a2[f] = sos[6 * f + 5];
+    }
+    rsos_wproj_matrix(cf, tab, jend, ngroups, kw, M, wp, V, j0, K);
 }
 
 void Plan::fuse_resample_sos() {
@@ -2026,7 +2097,20 @@ void Plan::fuse_resample_sos() {
             // (round 6, measured with the step waves and without the spilled store offsets: 4 ch 1.04 / 0.98 with / without a fused
             //  step against 0.95 for 8 ch; 2 ch 1.06 / 1.06)
             const double unit_cost = ct >= 8 ? 1.0 : ct == 4 ? 1.1 : ct == 2 ? 1.15 : 3.2;
-            const double t_fused = (double)((ngrp + cus - 1) / cus) * (double)((pr + wp) * ngp) * 0.30 * unit_cost * (ks + 14) / 28.0 + 15.0;
+            // (a plan that projects its warm-ups -- the form decided for good further down, from the same facts -- walks pr periods
+            //  and pays the product instead: fetch-bound, 41 - 46 us for the headline's 3 290 frames, 13 ns per frame of the span;
+            //  measured, profiles/r07/wproj_bench.jsonl)
+            bool wpj = !std::getenv("SIGOPS_RSOS_NOWPROJ") && !std::getenv("SIGOPS_RSOS_NWAVES") && nodes[S2.node].dtype == SO_F64 && !two_arrays && !was_ga &&
+                       ct >= 8 && wp * Mp + kwp <= 16384;
+            if (wpj && plain_src) wpj = S3.in_array_node >= 0 && nodes[nodes[S3.node].kids[0]].dtype != SO_F32;
+            else if (wpj) {
+                const DCarrier& c0 = S3.carriers[0];
+                const bool sine = c0.nsteps == 1 && (c0.arg[0] & 0x2ff) == 0 && c0.nslots >= 1 && (c0.op[0] == OP_ADD || (c0.op[0] == OP_SUB && !(c0.arg[0] & 0x100))) &&
+                                  c0.slot_kind[0] == OP_FUNC && leaves[c0.slot_leaf[0]].mode == SO_FN_SIN && leaves[c0.slot_leaf[0]].sf == 1;
+                wpj = c0.dtype == SO_F64 && c0.array_node >= 0 && (c0.nsteps == 0 || sine);
+            }
+            const double t_pro = wpj ? 0.013 * (double)(wp * Mp + kwp) : 0.0;
+            const double t_fused = (double)((ngrp + cus - 1) / cus) * ((double)((pr + (wpj ? 0 : wp)) * ngp) * 0.30 * unit_cost * (ks + 14) / 28.0 + t_pro) + 15.0;
             const double t_two = 8.0e-6 * (double)need * nch + 95.0;
             if (std::getenv("SIGOPS_DEBUG_PLAN"))
                 std::fprintf(stderr, "[sigops] k_rsos estimate: fused %.0f us (%lld groups, %lld + %lld periods), two kernels %.0f us\n", t_fused,
@@ -2186,6 +2270,60 @@ void Plan::fuse_resample_sos() {
         }
         S2.rsos_grid = (int)std::min<int64_t>(ngrp, cus);
         rsos_block_matrices(cf, S2.rsos_mats_host);
+        // The warm-up of a range as ONE product (rsos_wproj_matrix above; k_rsos.hip, rsos_wproj_*) instead of wp periods of the
+        // block walk: a Float64 ARRAY on the loader's fast path (not a stage buffer: what K1 materialised for this kernel takes the
+        // path the two-array form of the same tree takes -- their results are compared bit for bit), plain or `v +- one sine`, groups of 8 or 16 channels, the
+        // twelve- and eight-wave geometries.  The sine's share of the state is V . sin(w k + a_r) = cos a_r (V . sin w k) +
+        // sin a_r (V . cos w k): two vectors behind V, the phase a_r of the row's first frame is the kernel's to evaluate.
+        // A group whose warm-up is not wholly inside the array (the signal's first ranges, windows) walks as before.
+        // SIGOPS_RSOS_NOWPROJ=1: every group walks.
+        {
+            const std::vector<double>& tb = own_tab ? S2.rsos_tab_host : S3.tab_host;
+            const std::vector<int>& je = own_tab ? S2.rsos_jend_host : S3.jend_host;
+            const DCarrier& c0 = S3.carriers[0];
+            const bool form = g.fuse == -1 || ((g.fuse == 1 || g.fuse == 2) && g.fuse_sine);
+            S2.rs.wproj = 0;
+            if (!std::getenv("SIGOPS_RSOS_NOWPROJ") && nodes[S2.node].dtype == SO_F64 && !two_arrays && !g.src32 && !g.ring32 && !g.f32m &&
+                !g.gsplit && !g.help && (g.nwaves == 12 || g.nwaves == 8) && ct >= 8 && form && c0.dtype == SO_F64 && c0.array_node >= 0 &&
+                tb.size() == (size_t)ngp * kwp * 16 && (int)je.size() >= ngp && wp * Mp + kwp <= 16384) {
+                std::vector<double> V;
+                int j0 = 0, K = 0;
+                rsos_wproj_matrix(cf, tb.data(), je.data(), ngp, kwp, Mp, (int)wp, V, j0, K);
+                const int K8 = (K + 7) / 8 * 8;
+                std::vector<double>& mt = S2.rsos_mats_host;
+                mt.resize((size_t)14 * 64 + (size_t)K8 / 4 * 64 + 32, 0.0);
+                for (int ksx = 0; ksx < K8 / 4; ++ksx)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int i = lane & 15, f = 8 * (ksx >> 1) + 2 * (lane >> 4) + (ksx & 1);
+                        mt[(size_t)14 * 64 + (size_t)ksx * 64 + lane] = i < 12 && f < K ? V[(size_t)i * K + f] : 0.0;
+                    }
+                if (g.fuse >= 0) {
+                    const DLeaf& L0 = leaves[c0.slot_leaf[0]];
+                    const long double wc = L0.flag ? (long double)L0.v0 / (long double)L0.v2 : 1.0L / (long double)L0.v2;  // cycles per frame
+                    long double vs[12] = {}, vc[12] = {};
+                    for (int f = 0; f < K; ++f) {  // (the phase is the frame's: one sine and cosine per frame, for all twelve rows)
+                        long double ph = wc * f;
+                        ph -= floorl(ph);
+                        const long double sn = sinl(2.0L * 3.141592653589793238462643383279502884L * ph);
+                        const long double cs = cosl(2.0L * 3.141592653589793238462643383279502884L * ph);
+                        for (int i = 0; i < 12; ++i) {
+                            vs[i] += (long double)V[(size_t)i * K + f] * sn;
+                            vc[i] += (long double)V[(size_t)i * K + f] * cs;
+                        }
+                    }
+                    for (int i = 0; i < 12; ++i) {
+                        mt[(size_t)14 * 64 + (size_t)K8 / 4 * 64 + i] = (double)vs[i];
+                        mt[(size_t)14 * 64 + (size_t)K8 / 4 * 64 + 16 + i] = (double)vc[i];
+                    }
+                }
+                S2.rs.wproj = 1;
+                S2.rs.wk = K;
+                S2.rs.wj0 = j0;
+                if (std::getenv("SIGOPS_DEBUG_PLAN"))
+                    std::fprintf(stderr, "[sigops] k_rsos: warm-up as one product: %d frames from %d (%d k-steps instead of %lld blocks)\n", K, j0, K8 / 4,
+                                 (long long)(wp * ngp));
+            }
+        }
         S2.rsos_mats_buf = raw_buf(S2.rsos_mats_host.size() * 8);
         if (S2.bad_buf < 0) S2.bad_buf = raw_buf((size_t)nch * 4);  // first range per channel that ended in a non-finite state
         S3.fused_away = true;

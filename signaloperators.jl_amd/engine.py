@@ -132,7 +132,14 @@ class Plan:
         """so_plan_counter: how the executes so far were issued (graph replays / captures / direct)"""
         L = K.lib()
         return {"graph_replays": L.so_plan_counter(self.handle, 0), "graph_captures": L.so_plan_counter(self.handle, 1),
-                "direct_executes": L.so_plan_counter(self.handle, 2), "fused_mfmas_per_block": L.so_plan_counter(self.handle, 3)}
+                "direct_executes": L.so_plan_counter(self.handle, 2), "fused_mfmas_per_block": L.so_plan_counter(self.handle, 3),
+                "wproj": L.so_plan_counter(self.handle, 4)}
+
+    def rsos_geometry(self):
+        """the first fused resampler + IIR launch's ranges (so_plan_counter 5 .. 9): periods per range, warm-up periods, input
+        frames per period, frames a projected warm-up reads and the first of them relative to the warm-up's first input"""
+        L = K.lib()
+        return {k: L.so_plan_counter(self.handle, i) for i, k in enumerate(("pr", "wp", "M", "wproj_frames", "wproj_first"), 5)}
 
     def steps(self):
         """per-step statistics of the last (profiled) execute: so_plan_step_info"""
