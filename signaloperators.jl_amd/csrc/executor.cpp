@@ -29,6 +29,111 @@ static hipError_t h2d_small(void* dst, const void* src, size_t bytes) {
     return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// finalize's tables: the pointwise steps' pieces, programs and leaves, the look-up tables, and per stage what its kernels
+// read -- straight from the stages' *_host vectors (std::vector<Stage> moves while the planner adds stages: no pointers kept).
+static void upload_tables(Plan* P) {
+    std::vector<Buf>& bufs = P->bufs;
+    auto up = [&](int buf, const auto& v, size_t at = 0) {  // vector v into plan buffer `buf`, from byte `at` on
+        HIPCHECK(h2d_small((char*)bufs[buf].d + at, v.data(), v.size() * sizeof(*v.data())));
+    };
+    auto alloc_up = [](auto*& d, const auto& v) {  // a table with an allocation of its own, where there is one
+        if (v.empty()) return;
+        HIPCHECK(hipMalloc(&d, v.size() * sizeof(*v.data())));
+        HIPCHECK(h2d_small(d, v.data(), v.size() * sizeof(*v.data())));
+    };
+    alloc_up(P->d_pieces, P->pieces);
+    alloc_up(P->d_ops, P->ops);
+    alloc_up(P->d_leaves, P->leaves);
+    for (auto& T : P->tables)  // SO_EOP_INTERP: the only copy of a table the plan ever makes
+        HIPCHECK(h2d_small(bufs[T.buf].d, T.src, T.ndoubles * 8));
+    for (auto& S : P->stages) {
+        if (S.need <= 0) continue;
+        if (S.kind == ST_SOS && S.qmat_buf >= 0) up(S.qmat_buf, S.qmat_host);
+        if (S.kind == ST_SOS && S.rsos_src >= 0) {
+            up(S.rsos_mats_buf, S.rsos_mats_host);
+            if (S.rsos_jrel_buf >= 0) up(S.rsos_jrel_buf, S.rsos_jrel_host);
+            if (S.rsos_tab_buf >= 0) {
+                up(S.rsos_tab_buf, S.rsos_tab_host);
+                up(S.rsos_jend_buf, S.rsos_jend_host);
+            }
+        }
+        if (S.kind == ST_SOS && S.onepass) up(S.one_tabs_buf, S.one_tabs_host);
+        if (S.kind == ST_RESAMPLE && S.rs_jrel_buf >= 0 && S.rs_nf_buf >= 0) {
+            up(S.rs_jrel_buf, S.rs_jrel_host);
+            HIPCHECK(hipMemset(bufs[S.rs_nf_buf].d, 0, 64));  // (the list's count: k_rs_fixup leaves it at zero again)
+        }
+        if (S.kind == ST_RESAMPLE) {
+            up(S.pfb_buf, S.pfb_host);
+            up(S.dpfb_buf, S.dpfb_host);
+            if (S.wtab_buf >= 0) up(S.wtab_buf, S.wtab_host);
+            if (S.tiled) {
+                up(S.pfbt_buf, S.pfbt_host);
+                up(S.dpfbt_buf, S.dpfbt_host);
+            }
+            if (S.fix_buf >= 0) up(S.fix_buf, S.fix_host);
+            if (S.periodic || S.rows) {
+                up(S.tab_buf, S.tab_host);
+                up(S.jend_buf, S.jend_host);
+            }
+            if (S.rows && !S.mtab_host.empty()) {
+                up(S.mtab_buf, S.mtab_host);
+                up(S.mjend_buf, S.mjend_host);
+            }
+        } else if (S.kind == ST_SOS && S.mpow_buf >= 0) {
+            for (size_t gi = 0; gi < S.xs_mats_host.size() && S.xs_mats_buf >= 0; ++gi) up(S.xs_mats_buf, S.xs_mats_host[gi], gi * 2 * 16 * 16 * 8);
+            for (size_t gi = 0; gi < S.mpow_host.size(); ++gi) up(S.mpow_buf, S.mpow_host[gi], gi * S.mpow_stride() * 8);
+        }
+    }
+}
+
+// The name a stage's step goes by in so_plan_step_info: the kernel that does its work.
+static const char* stage_step_name(const Stage& S) {
+    switch (S.kind) {
+    case ST_SOS: return S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos";
+    case ST_RESAMPLE:
+        if (S.periodic) return "k_resample_periodic";
+        if (S.rows) return "k_resample_rows";
+        if (S.tiled) return S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled";
+        return "k_resample";
+    case ST_SAMPLEAT: return "k_sample_at";
+    case ST_COMB: return "k_comb";
+    case ST_CUMSUM: return "k_cumsum";
+    default: return "k_sumsq";
+    }
+}
+
+// Algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a Float64
+// map is 4 bytes a sample, whatever the node's promoted type) plus the samples it writes in the type of the buffer they go
+// to (a Float64 stage that rounds into the Float32 result itself writes 4).
+static int64_t stage_step_bytes(const Plan* P, int sid) {
+    const Stage& S = P->stages[sid];
+    const Node& N = P->nodes[S.node];
+    const int64_t esz = (int64_t)dsize(N.dtype);
+    const int64_t osz = (sid == P->alias_stage && P->alias_narrow) ? (int64_t)dsize(P->out.dtype) : esz;
+    auto src_esz = [&](const Stage& R) -> int64_t {  // a resampler's source: carrier 0's array / buffer, else its child
+        if (!R.carriers.empty()) return (int64_t)dsize(R.carriers[0].dtype);
+        const std::vector<int>& kids = P->nodes[R.node].kids;
+        return !kids.empty() && kids[0] >= 0 ? (int64_t)dsize(P->nodes[kids[0]].dtype) : esz;
+    };
+    auto kid_esz = [&](int k) { return (int64_t)dsize(P->nodes[N.kids[k]].dtype); };
+    switch (S.kind) {
+    case ST_SOS:
+        if (S.rsos_src >= 0)  // (arr2: a second array read)
+            return (S.rs.n_in * src_esz(P->stages[S.rsos_src]) * (S.rs.arr2 ? 2 : 1) + S.rs.n_out * osz) * S.rs.nch;
+        return (S.need - S.base) * S.sg.nch * (esz + osz);
+    case ST_RESAMPLE:  // (arr2: a second array of the source's type read)
+        return (S.rg.n_in * (src_esz(S) + (S.rp.arr2 ? src_esz(S) : 0)) + S.rg.n_out * osz) * S.rg.nch;
+    case ST_SAMPLEAT:  // per frame: a position read, two table samples read where they lie, a Float64 written
+        return (S.need - S.base) * ((int64_t)P->nodes[N.kids[1]].nch * 8 + (int64_t)N.nch * (2 * kid_esz(0) + 8));
+    case ST_COMB:  // per sample: one read where x lies, one Float64 written
+        return S.need * (int64_t)N.nch * (kid_esz(0) + 8);
+    case ST_CUMSUM:  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
+        return S.need * (int64_t)N.nch * (2 * kid_esz(0) + 8);
+    default: return (S.need - S.base) * N.nch * esz;
+    }
+}
+
 void Plan::finalize() {
     // size stage output buffers now that every need is known
     for (size_t si = 0; si < stages.size(); ++si) {
@@ -161,69 +266,7 @@ void Plan::finalize() {
     if (dbg_t)
         std::fprintf(stderr, "[sigops] finalize: leaves and carriers patched, carrier blocks uploaded: %.3f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf0).count());
-    // upload tables
-    if (!pieces.empty()) {
-        HIPCHECK(hipMalloc(&d_pieces, pieces.size() * sizeof(DPiece)));
-        HIPCHECK(h2d_small(d_pieces, pieces.data(), pieces.size() * sizeof(DPiece)));
-    }
-    if (!ops.empty()) {
-        HIPCHECK(hipMalloc(&d_ops, ops.size() * sizeof(DOp)));
-        HIPCHECK(h2d_small(d_ops, ops.data(), ops.size() * sizeof(DOp)));
-    }
-    if (!leaves.empty()) {
-        HIPCHECK(hipMalloc(&d_leaves, leaves.size() * sizeof(DLeaf)));
-        HIPCHECK(h2d_small(d_leaves, leaves.data(), leaves.size() * sizeof(DLeaf)));
-    }
-    for (auto& T : tables)  // SO_EOP_INTERP: the only copy of a table the plan ever makes
-        HIPCHECK(h2d_small(bufs[T.buf].d, T.src, T.ndoubles * 8));
-    for (auto& S : stages) {
-        if (S.need <= 0) continue;
-        if (S.kind == ST_SOS && S.qmat_buf >= 0)
-            HIPCHECK(h2d_small(bufs[S.qmat_buf].d, S.qmat_host.data(), S.qmat_host.size() * 8));
-        if (S.kind == ST_SOS && S.rsos_src >= 0) {
-            HIPCHECK(h2d_small(bufs[S.rsos_mats_buf].d, S.rsos_mats_host.data(), S.rsos_mats_host.size() * 8));
-            if (S.rsos_jrel_buf >= 0) HIPCHECK(h2d_small(bufs[S.rsos_jrel_buf].d, S.rsos_jrel_host.data(), S.rsos_jrel_host.size() * 4));
-            if (S.rsos_tab_buf >= 0) {
-                HIPCHECK(h2d_small(bufs[S.rsos_tab_buf].d, S.rsos_tab_host.data(), S.rsos_tab_host.size() * 8));
-                HIPCHECK(h2d_small(bufs[S.rsos_jend_buf].d, S.rsos_jend_host.data(), S.rsos_jend_host.size() * 4));
-            }
-        }
-        if (S.kind == ST_SOS && S.onepass)
-            HIPCHECK(h2d_small(bufs[S.one_tabs_buf].d, S.one_tabs_host.data(), S.one_tabs_host.size() * 8));
-        if (S.kind == ST_RESAMPLE && S.rs_jrel_buf >= 0 && S.rs_nf_buf >= 0) {
-            HIPCHECK(h2d_small(bufs[S.rs_jrel_buf].d, S.rs_jrel_host.data(), S.rs_jrel_host.size() * 4));
-            HIPCHECK(hipMemset(bufs[S.rs_nf_buf].d, 0, 64));  // (the list's count: k_rs_fixup leaves it at zero again)
-        }
-        if (S.kind == ST_RESAMPLE) {
-            HIPCHECK(h2d_small(bufs[S.pfb_buf].d, S.pfb_host.data(), S.pfb_host.size() * 8));
-            HIPCHECK(h2d_small(bufs[S.dpfb_buf].d, S.dpfb_host.data(), S.dpfb_host.size() * 8));
-            if (S.wtab_buf >= 0)
-                HIPCHECK(h2d_small(bufs[S.wtab_buf].d, S.wtab_host.data(), S.wtab_host.size() * 8));
-            if (S.tiled) {
-                HIPCHECK(h2d_small(bufs[S.pfbt_buf].d, S.pfbt_host.data(), S.pfbt_host.size() * 8));
-                HIPCHECK(h2d_small(bufs[S.dpfbt_buf].d, S.dpfbt_host.data(), S.dpfbt_host.size() * 8));
-            }
-            if (S.fix_buf >= 0)
-                HIPCHECK(h2d_small(bufs[S.fix_buf].d, S.fix_host.data(), S.fix_host.size() * sizeof(RsFix)));
-            if (S.periodic || S.rows) {
-                HIPCHECK(h2d_small(bufs[S.tab_buf].d, S.tab_host.data(), S.tab_host.size() * 8));
-                HIPCHECK(h2d_small(bufs[S.jend_buf].d, S.jend_host.data(), S.jend_host.size() * 4));
-            }
-            if (S.rows && !S.mtab_host.empty()) {
-                HIPCHECK(h2d_small(bufs[S.mtab_buf].d, S.mtab_host.data(), S.mtab_host.size() * 8));
-                HIPCHECK(h2d_small(bufs[S.mjend_buf].d, S.mjend_host.data(), S.mjend_host.size() * 4));
-            }
-        } else if (S.kind == ST_SOS && S.mpow_buf >= 0) {
-            for (size_t gi = 0; gi < S.xs_mats_host.size() && S.xs_mats_buf >= 0; ++gi)
-                HIPCHECK(h2d_small((char*)bufs[S.xs_mats_buf].d + gi * 2 * 16 * 16 * 8, S.xs_mats_host[gi].data(),
-                                   S.xs_mats_host[gi].size() * 8));
-            size_t msz = 0;
-            for (auto& v : S.mpow_host) msz = std::max(msz, v.size());
-            for (size_t gi = 0; gi < S.mpow_host.size(); ++gi)
-                HIPCHECK(h2d_small((char*)bufs[S.mpow_buf].d + gi * msz * 8, S.mpow_host[gi].data(),
-                                   S.mpow_host[gi].size() * 8));
-        }
-    }
+    upload_tables(this);
     if (dbg_t)
         std::fprintf(stderr, "[sigops] finalize: tables uploaded: %.3f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf0).count());
@@ -260,28 +303,8 @@ void Plan::finalize() {
         if (S.pw_step >= 0) push_pw_step(S.pw_step);
         if (S.pos_pw_step >= 0) push_pw_step(S.pos_pw_step);
         if (S.fused_away) continue;  // (runs inside its consumer's launch)
-        const char* nm = S.kind == ST_SOS ? (S.rsos_src >= 0 ? "k_rsos" : S.sg.exact ? "k_sos_exact" : "k_sos") : S.kind == ST_RESAMPLE ? (S.periodic ? "k_resample_periodic" : S.rows ? "k_resample_rows" : S.tiled ? (S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled") : "k_resample") : S.kind == ST_SAMPLEAT ? "k_sample_at" : S.kind == ST_COMB ? "k_comb" : S.kind == ST_CUMSUM ? "k_cumsum" : "k_sumsq";
-        Step st{1, sid, nm, 0};
-        // algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a
-        // Float64 map is 4 bytes a sample, whatever the node's promoted type) plus the samples it writes in the type of
-        // the buffer they go to (a Float64 stage that rounds into the Float32 result itself writes 4)
-        const int64_t esz = (int64_t)dsize(nodes[S.node].dtype);
-        const int64_t osz = (sid == alias_stage && alias_narrow) ? (int64_t)dsize(out.dtype) : esz;
-        auto src_esz = [&](const Stage& R) -> int64_t {  // a resampler's source: carrier 0's array / buffer, else its child
-            if (!R.carriers.empty()) return (int64_t)dsize(R.carriers[0].dtype);
-            const std::vector<int>& kids = nodes[R.node].kids;
-            return !kids.empty() && kids[0] >= 0 ? (int64_t)dsize(nodes[kids[0]].dtype) : esz;
-        };
-        if (S.kind == ST_SOS && S.rsos_src >= 0) st.bytes = (S.rs.n_in * src_esz(stages[S.rsos_src]) * (S.rs.arr2 ? 2 : 1) + S.rs.n_out * osz) * S.rs.nch;  // (arr2: a second array read)
-        else if (S.kind == ST_SOS) st.bytes = (S.need - S.base) * S.sg.nch * (esz + osz);
-        else if (S.kind == ST_RESAMPLE) st.bytes = (S.rg.n_in * (src_esz(S) + (S.rp.arr2 ? src_esz(S) : 0)) + S.rg.n_out * osz) * S.rg.nch;  // (arr2: a second array of the source's type read)
-        else if (S.kind == ST_SAMPLEAT)  // per frame: a position read, two table samples read where they lie, a Float64 written
-            st.bytes = (S.need - S.base) * ((int64_t)nodes[nodes[S.node].kids[1]].nch * 8 + (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8));
-        else if (S.kind == ST_COMB)  // per sample: one read where x lies, one Float64 written
-            st.bytes = S.need * (int64_t)nodes[S.node].nch * ((int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8);
-        else if (S.kind == ST_CUMSUM)  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
-            st.bytes = S.need * (int64_t)nodes[S.node].nch * (2 * (int64_t)dsize(nodes[nodes[S.node].kids[0]].dtype) + 8);
-        else st.bytes = (S.need - S.base) * nodes[S.node].nch * esz;
+        Step st{1, sid, stage_step_name(S), 0};
+        st.bytes = stage_step_bytes(this, sid);
         steps.push_back(st);
     }
     stats.n_stages = (int)order.size() + 1;
@@ -468,42 +491,595 @@ static bool kernel_gave_up(Plan* P, std::string& err) {
 }
 
 // ---------------------------------------------------------------------------
-// Where the stages that take one plain input and write one Float64 buffer (SampleAt's table, Comb's x) read and write.
+// Where a stage reads and writes: the first element and the channel pitch in elements.
+struct View {
+    char* d;
+    int64_t pitch;
+};
 static const char* array_base(Plan* P, int an) {
     return P->nodes[an].nd.i0 ? (const char*)P->array_ptr[an] : (const char*)P->bufs[P->array_buf[an]].d;
 }
-// the input set up by Plan::stage_input: an array where it lies, or a buffer; -> its first element, `cs` its channel stride
-static const void* stage_input_view(Plan* P, const Stage& S, int nch, int dtype, int64_t& cs) {
-    if (S.in_array_node >= 0) {
-        cs = nch == 1 ? 0 : S.in_pitch;
-        return array_base(P, S.in_array_node) + (size_t)S.in_offset * dsize(dtype);
-    }
+// The input Plan::stage_input set up: a caller's array where it lies, or a plan buffer, whose first element is the node's
+// frame `frame0`.  `dtype` is the type of the samples where they lie: the child's for SampleAt, Comb and Cumsum, the node's
+// own for the filters and resamplers.  A stage with neither (a filter whose source k_rsos reads through carriers) has no view.
+static View stage_in(Plan* P, const Stage& S, int nch, int dtype) {
+    if (S.in_array_node >= 0)
+        return View{(char*)array_base(P, S.in_array_node) + (size_t)S.in_offset * dsize(dtype), nch == 1 ? 0 : S.in_pitch};
+    if (S.in_buf < 0) return View{nullptr, 0};
     const Buf& b = P->bufs[S.in_buf];
-    cs = b.pitch;
-    return (const char*)b.d + (size_t)(S.in_offset - b.frame0) * dsize(dtype);
+    return View{(char*)b.d + (size_t)(S.in_offset - b.frame0) * dsize(dtype), b.pitch};
 }
-// the Float64 rows stage `sid` writes: its own buffer, the sink's result where the stage is aliased to it (from the
-// stage's local frame alias_skip on), or its window of the result; `cs` = the channel stride
-static double* stage_output_view(Plan* P, int sid, void* outp, int64_t& cs) {
+// Where stage `sid` writes: its own buffer; the sink's result where the stage is aliased to it (Plan::alias_stage), from
+// the stage's local frame alias_skip on -- earlier frames are not stored, and the skipped frames are counted in the type
+// the stage stores, the result's where it rounds to it (alias_narrow); or its window of the result (Stage::win_off), which
+// has the node's type (try_window_alias takes stages of the result's type only).
+// SampleAt, Comb and Cumsum, whose kernels store Float64 only, get 8 bytes for both: their nodes are Float64 (build_nodes),
+// and plan_create lets only a periodic resampler or a filter narrow, so alias_narrow is false where one of them is aliased.
+// A member of an RsBatch is never the aliased stage (fuse_plain_sos skips it): k_rsos_batch's members write windows or buffers.
+static View stage_out(Plan* P, int sid, void* outp) {
     const Stage& S = P->stages[sid];
-    const Buf& ob = P->bufs[S.out_buf];
-    void* d = ob.d;
-    cs = ob.pitch;
+    const Node& N = P->nodes[S.node];
+    const size_t esz = dsize(N.dtype);
     if (sid == P->alias_stage) {
-        if (P->out.is_device) {
-            d = outp;
-            cs = P->nodes[S.node].nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
-        } else {
-            d = P->bufs[P->out_stage_buf].d;
-            cs = P->bufs[P->out_stage_buf].pitch;
-        }
-        d = (char*)d - (size_t)P->alias_skip * 8;
-    } else if (S.win_off >= 0) {
-        const Buf& ab = P->bufs[P->out_alias_buf];
-        d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * 8;
-        cs = ab.pitch;
+        View v{(char*)outp, N.nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride};
+        if (!P->out.is_device) v = View{(char*)P->bufs[P->out_stage_buf].d, P->bufs[P->out_stage_buf].pitch};  // (a host result: its staging buffer)
+        v.d -= (size_t)P->alias_skip * (P->alias_narrow ? dsize(P->out.dtype) : esz);
+        return v;
     }
-    return (double*)d;
+    if (S.win_off >= 0) {
+        const Buf& ab = P->bufs[P->out_alias_buf];
+        return View{(char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * esz, ab.pitch};
+    }
+    const Buf& ob = P->bufs[S.out_buf];
+    return View{(char*)ob.d, ob.pitch};
+}
+
+// the fused sine source of a cascade's input (Stage::src_op): the generator's leaf and one step of its rotation
+static void set_sine_source(SosGeom& g, const Stage& S) {
+    const DLeaf& F = S.src_fn;
+    g.src_op = S.src_op;
+    g.src_has_omega = F.flag;
+    g.src_df = F.df;
+    g.src_omega = F.v0;
+    g.src_phi = F.v1;
+    g.src_fs = F.v2;
+    const double step = 6.283185307179586476925 * (F.flag ? F.v0 / F.v2 : 1.0 / F.v2);
+    g.src_cd = std::cos(step);
+    g.src_sd = std::sin(step);
+}
+// what a kernel that reads through stage S's carriers reads them with
+static RsGlobalTables global_tables(Plan* P, const Stage& S) {
+    return RsGlobalTables{(const RsCtl*)P->bufs[S.ctl_buf].d, (const DCarrier*)P->bufs[S.car_buf].d, P->d_ops, P->d_leaves};
+}
+// what k_rsos_fixup needs behind a k_rsos launch of filter S: what that launch was given (I), the reference's taps, the sections
+static void set_rsos_fixup(RsFixup& F, Plan* P, const Stage& S, const RsosItem& I) {
+    F.g = I.g;
+    F.tab = I.tab;
+    F.jend = I.jend;
+    F.jrel = (const int*)P->bufs[S.rsos_jrel_buf].d;
+    F.taps = S.rsos_taps;
+    F.cf = S.groups[0];
+    F.gsrc = I.gsrc;
+    F.y = I.y;
+}
+// "no non-finite chunk (range) yet" in every word of a SosGeom::bad / RsSos::bad array
+static void arm_bad(void* words, size_t n, hipStream_t st) { HIPCHECK((hipError_t)launch_fill_u32(words, n, 0x7f7f7f7fu, st)); }
+
+// The tuning aids' traces: the cycle stamps workgroup 0 of a launch left (waits for it), printed relative to the earliest, t0.
+static std::vector<long long> read_trace(const long long* d_trace, size_t trace_n, hipStream_t st, long long& t0) {
+    std::vector<long long> tr(trace_n);
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipMemcpy(tr.data(), d_trace, trace_n * 8, hipMemcpyDeviceToHost));
+    t0 = 0;
+    for (size_t i = 0; i < trace_n; ++i)
+        if (tr[i] && (!t0 || tr[i] < t0)) t0 = tr[i];
+    return tr;
+}
+// SIGOPS_RS_TRACE: k_resample_periodic's
+static void dump_rs_trace(const long long* d_trace, size_t trace_n, const RsPeriodic& rp, hipStream_t st) {
+    long long t0;
+    const std::vector<long long> tr = read_trace(d_trace, trace_n, st, t0);
+    for (int w = 0; w < rp.nwaves; ++w)
+        for (int it = 0; it < kRsTraceIters; ++it) {
+            const long long* q = &tr[((size_t)w * kRsTraceIters + it) * kRsTraceStamps];
+            if (!q[0]) continue;
+            std::fprintf(stderr, "[rs-trace] %s w%02d it%02d", w < rp.ncompute ? "C" : "L", w, it);
+            for (int k = 0; k < kRsTraceStamps; ++k) std::fprintf(stderr, " %lld", q[k] ? q[k] - t0 : -1);
+            std::fprintf(stderr, "\n");
+        }
+}
+// SIGOPS_RSOS_TRACE: k_rsos's; =2 (a -DSO_RSOS_COUNT=1 build): its poll counters, raw
+static void dump_rsos_trace(const long long* d_trace, size_t trace_n, const RsSos& rs, hipStream_t st) {
+    long long t0;
+    const std::vector<long long> tr = read_trace(d_trace, trace_n, st, t0);
+    const bool counters = std::atoi(std::getenv("SIGOPS_RSOS_TRACE")) == 2;
+    for (int w = 0; w < rs.nwaves; ++w)
+        for (int it = 0; it < (counters ? 5 : kRsosTraceIters); ++it) {
+            const long long* q = &tr[((size_t)w * kRsosTraceIters + it) * 8];
+            if (counters) {
+                bool any = false;
+                for (int k = 0; k < 8; ++k) any = any || q[k];
+                if (!any) continue;
+                std::fprintf(stderr, "[rsos-count] w%02d row%d", w, it);
+                for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %lld", q[k] - 1);
+            } else {
+                if (!q[0] && !q[2]) continue;
+                std::fprintf(stderr, "[rsos-trace] %s w%02d it%02d", w == 0 ? "C" : (w & 3) == 0 ? "L" : "Y", w, it);
+                for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %lld", q[k] ? q[k] - t0 : -1);
+            }
+            std::fprintf(stderr, "\n");
+        }
+}
+
+// ---------------------------------------------------------------------------
+// One routine per kind of step.  Each issues the step's launches on `st` and returns how many it issued (Step::launches).
+
+static int run_pointwise(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const PwStep& w = P->pw[s.idx];
+    if (w.nblocks <= 0) return 0;  // empty rectangle (zero-frame sink): nothing to launch
+    static const int il_scalar = std::getenv("SIGOPS_K1_ILSCALAR") ? 1 : 0;  // ablation knob
+    OutView ov{};  // a plan buffer, the device result with its own strides, or a host result's staging buffer
+    if (w.out_buf >= 0) {
+        const Buf& b = P->bufs[w.out_buf];
+        ov = OutView{b.d, 1, b.pitch, b.dtype, il_scalar};
+    } else if (P->out.is_device) {
+        ov = OutView{outp, P->out.frame_stride, P->out.chan_stride, P->out.dtype, il_scalar};
+    } else {
+        const Buf& b = P->bufs[P->out_stage_buf];
+        ov = OutView{b.d, P->interleaved_host ? P->out.nch : 1, P->interleaved_host ? 1 : b.pitch, b.dtype, il_scalar};
+    }
+    if (w.fill)
+        launch_randn_fill(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_leaves, ov, st);
+    else if (w.rtc) {
+        if (rtc_launch(w.rtc, w.nblocks, P->d_pieces + w.piece0, w.npieces, P->d_leaves, ov, st) != 0)
+            fail(SO_ERR_RUNTIME, "hipRTC kernel launch failed");
+    } else
+        launch_pointwise(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_ops, P->d_leaves, ov, w.deep, st, w.chain,
+                         w.il || (ov.fstride > 1 && ov.cstride == 1), w.math);
+    return 1;
+}
+
+// independent filters of one shape, their three passes in three launches (k_sos_batch): a descriptor per member
+static int run_sos_batch(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    SosBatch& B = P->batches[s.idx];
+    const size_t nm = B.members.size();
+    const bool poison = B.bad_buf >= 0 && !std::getenv("SIGOPS_SOS_NOPOISON");
+    std::vector<SosDesc> d(nm + 1);
+    int64_t first[3] = {0, 0, 0};
+    for (size_t m = 0; m <= nm; ++m) {
+        SosDesc& D = d[m];
+        std::memset(&D, 0, sizeof D);
+        for (int q = 0; q < 3; ++q) D.first[q] = first[q];
+        if (m == nm) break;
+        const int sid = B.members[m];
+        const Stage& S = P->stages[sid];
+        const Node& N = P->nodes[S.node];
+        const View in = stage_in(P, S, N.nch, N.dtype), out = stage_out(P, sid, outp);
+        D.x = in.d;
+        D.y = out.d;
+        D.v = S.v_buf >= 0 ? (double*)P->bufs[S.v_buf].d : nullptr;
+        D.s0 = S.s0_buf >= 0 ? (double*)P->bufs[S.s0_buf].d : nullptr;
+        D.mpow = S.mpow_buf >= 0 ? (const double*)P->bufs[S.mpow_buf].d : nullptr;
+        D.g = S.sg;
+        D.g.in_pitch = in.pitch;
+        D.g.out_pitch = out.pitch;
+        D.g.store_lo = sid == P->alias_stage ? P->alias_skip : 0;
+        if (sid == P->alias_stage && P->alias_narrow) D.g.out_dtype = SO_F32;
+        D.g.align_rows = !std::getenv("SIGOPS_SOS_NOALIGN");
+        D.g.bad = poison && S.sg.nchunks > 1 ? (int32_t*)P->bufs[B.bad_buf].d + B.bad_off[m] : nullptr;
+        if (S.src_op) set_sine_source(D.g, S);
+        D.cf = S.groups[0];
+        const int64_t nseq = (int64_t)D.g.nchunks * D.g.nch;
+        if (D.g.nchunks > 1) {
+            first[0] += ((int64_t)(D.g.nchunks - 1) * D.g.nch + kBlock - 1) / kBlock;
+            first[1] += (nseq + kBlock - 1) / kBlock;
+        } else
+            D.s0 = nullptr;  // one chunk: starts from rest
+        first[2] += (nseq + kBlock - 1) / kBlock;
+    }
+    if (first[2] >= ((int64_t)1 << 31)) fail(SO_ERR_RUNTIME, "internal: batched IIR grid too large");
+    if (B.host.size() != d.size() || std::memcmp(B.host.data(), d.data(), d.size() * sizeof(SosDesc)) != 0) {
+        // the descriptors change only when the result or an array moves -- never between the direct execute for a result
+        // pointer and the capture that follows it (plan_execute), so a captured graph holds the three launches only and
+        // reads the table this copy left on the device
+        B.host = d;
+        HIPCHECK(hipMemcpyAsync(P->bufs[B.desc_buf].d, B.host.data(), B.host.size() * sizeof(SosDesc), hipMemcpyHostToDevice, st));
+    }
+    for (int q = 0; q < 3; ++q) B.total[q] = first[q];
+    if (poison) arm_bad(P->bufs[B.bad_buf].d, P->bufs[B.bad_buf].bytes / 4, st);
+    int nl = launch_sos_batch((const SosDesc*)P->bufs[B.desc_buf].d, (int)nm, B.nsec, B.dtype, B.total, st);
+    if (poison) nl += launch_sos_poison_batch((const SosDesc*)P->bufs[B.desc_buf].d, (int)nm, B.dtype, st);
+    return nl;
+}
+
+// plain filters, one pass each, ONE launch (k_rsos_batch): per member what run_rsos_fused sets up for a launch of its own
+static int run_rsos_batch(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    RsBatch& B = P->rsbatches[s.idx];
+    const size_t nm = B.members.size();
+    std::vector<RsosItem> items(nm);
+    std::vector<RsFixup> fix(nm);
+    const bool poison = B.bad_buf >= 0 && !std::getenv("SIGOPS_SOS_NOPOISON");
+    int maxch = 1, out_f32 = 0;
+    for (size_t m = 0; m < nm; ++m) {
+        const int sid = B.members[m];
+        const Stage& S = P->stages[sid];
+        const View out = stage_out(P, sid, outp);
+        RsosItem& I = items[m];
+        std::memset(&I, 0, sizeof I);
+        RsSos rs = S.rs;
+        rs.out_pitch = out.pitch;
+        rs.out_f32 = P->nodes[S.node].dtype == SO_F32;
+        rs.f32m = 0;
+        rs.sring = 0;
+        rs.mats = (const double*)P->bufs[S.rsos_mats_buf].d;
+        rs.bad = poison ? (int32_t*)P->bufs[B.bad_buf].d + B.bad_off[m] : nullptr;
+        rs.err = kernel_error_word(P);
+        I.g = rs;
+        I.tab = (const double*)P->bufs[S.rsos_tab_buf].d;
+        I.jend = (const int*)P->bufs[S.rsos_jend_buf].d;
+        I.y = out.d - (size_t)S.rs.store_lo * (rs.out_f32 ? 4 : 8);
+        I.gsrc = global_tables(P, S);
+        std::memset(&fix[m], 0, sizeof fix[m]);
+        set_rsos_fixup(fix[m], P, S, I);
+        maxch = std::max(maxch, (int)rs.nch);
+        out_f32 = rs.out_f32;
+    }
+    if (B.host.size() != nm || std::memcmp(B.host.data(), items.data(), nm * sizeof(RsosItem)) != 0 ||
+        std::memcmp(B.fhost.data(), fix.data(), nm * sizeof(RsFixup)) != 0) {
+        // (as the three-pass batch's descriptors: the tables change only when the result or an array moves -- never
+        //  between the direct execute for a result pointer and the capture that follows it)
+        B.host = items;
+        B.fhost = fix;
+        HIPCHECK(hipMemcpyAsync(P->bufs[B.items_buf].d, B.host.data(), nm * sizeof(RsosItem), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(P->bufs[B.fix_buf].d, B.fhost.data(), nm * sizeof(RsFixup), hipMemcpyHostToDevice, st));
+    }
+    if (poison) arm_bad(P->bufs[B.bad_buf].d, P->bufs[B.bad_buf].bytes / 4, st);
+    if (launch_rsos_batch((const RsosItem*)P->bufs[B.items_buf].d, (int)nm, B.gpm, items[0].g, st) != 0)
+        fail(SO_ERR_RUNTIME, "internal: no batched one-pass IIR instantiation for this geometry");
+    int nl = 1;
+    if (poison) nl += launch_rsos_fixup_batch((const RsFixup*)P->bufs[B.fix_buf].d, (int)nm, maxch, out_f32, st);
+    return nl;
+}
+
+static int run_sample_at(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const int xdt = P->nodes[N.kids[0]].dtype;
+    const View in = stage_in(P, S, N.nch, xdt), out = stage_out(P, s.idx, outp);
+    SampleAtArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.N = S.in_frames;
+    a.x_f32 = xdt == SO_F32;
+    if (S.pos_array_node >= 0) {
+        a.pos = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
+        a.pcs = S.pos_pitch;
+    } else {
+        const Buf& b = P->bufs[S.pos_buf];
+        a.pos = (const double*)b.d;
+        a.pcs = S.pos_pitch == 0 ? 0 : b.pitch;
+    }
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.base = S.base;
+    a.n = S.need - S.base;
+    a.left = N.nd.d0;
+    a.right = N.nd.d1;
+    a.nch = N.nch;
+    a.relative = N.nd.i0 & 1;
+    a.wrap = (N.nd.i0 >> 1) & 1;
+    const int nl = launch_sample_at(a, st);
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "SampleAt: more than 65535 channels or 2^39 frames are not lowered");
+    return nl;
+}
+
+static int run_comb(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const int xdt = P->nodes[N.kids[0]].dtype;
+    const View in = stage_in(P, S, N.nch, xdt), out = stage_out(P, s.idx, outp);
+    CombArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.x_f32 = xdt == SO_F32;
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.n = S.need;
+    a.D = N.nd.l0;
+    a.b0 = N.nd.d0;
+    a.bD = N.nd.d1;
+    a.a = N.nd.d2;
+    a.nch = N.nch;
+    if (a.D < 1) fail(SO_ERR_INVALID, "Comb: a delay of less than one frame");  // (the planner has refused it)
+    const int nl = launch_comb(a, st);
+    // (one lane per frame mod D: min(D, frames) lanes a channel, in blocks of kBlock, must fit grid.x)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Comb: more than 65535 channels, or a delay AND a signal of 2^39 frames and more, are not lowered");
+    return nl;
+}
+
+static int run_cumsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const int xdt = P->nodes[N.kids[0]].dtype;
+    const View in = stage_in(P, S, N.nch, xdt), out = stage_out(P, s.idx, outp);
+    CumsumArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.x_f32 = xdt == SO_F32;
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.n = S.need;
+    a.nch = N.nch;
+    a.tot_pitch = cumsum_totals(S.need);
+    a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
+    const int nl = launch_cumsum(a, st);
+    // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Cumsum: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
+    return nl;
+}
+
+// the resampler in front and this cascade in one launch (k_rsos); `g`: the cascade's geometry as run_sos set it up
+static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View& out, hipStream_t st) {
+    const Node& N = P->nodes[S.node];
+    const Stage& S3 = P->stages[S.rsos_src];
+    RsSos rs = S.rs;
+    rs.out_pitch = out.pitch;
+    rs.out_f32 = g.out_dtype == SO_F32 || N.dtype == SO_F32;
+    if (rs.f32m && rs.out_f32) rs.ring32 = 1;  // (a Float32 result: Float32 samples in the ring, the Float32 MFMA)
+    else rs.f32m = 0;
+    rs.sring = rs.f32m && (rs.fuse == 1 || rs.fuse == 2) && !std::getenv("SIGOPS_RSOS_NO_SRING") ? 1 : 0;
+    // the kernel's output m is frame m - store_lo of this stage's buffer (a window: the resampler's warm
+    // start lies store_lo frames before the cascade's); the sink's own skipped frames come on top
+    char* const yk = out.d - (size_t)S.rs.store_lo * (rs.out_f32 ? 4 : 8);
+    rs.store_lo = S.rs.store_lo + g.store_lo;
+    rs.mats = (const double*)P->bufs[S.rsos_mats_buf].d;
+    rs.bad = nullptr;
+    if (S.bad_buf >= 0 && rs.nranges >= 1 && !std::getenv("SIGOPS_SOS_NOPOISON")) {
+        rs.bad = (int32_t*)P->bufs[S.bad_buf].d;
+        arm_bad(rs.bad, (size_t)N.nch, st);
+    }
+    rs.err = kernel_error_word(P);
+    static long long* d_rtrace = nullptr;  // SIGOPS_RSOS_TRACE tuning aid
+    // (SIGOPS_RSOS_TRACE_SKIP=n: not the first n launches of the process -- a traced launch synchronises, and a run
+    //  of traced launches never leaves the chip's power-management transient)
+    static int rtrace_seen = 0;
+    const char* const rtrace_skip = std::getenv("SIGOPS_RSOS_TRACE_SKIP");
+    const bool rtracing = std::getenv("SIGOPS_RSOS_TRACE") != nullptr && rtrace_seen++ >= (rtrace_skip ? std::atoi(rtrace_skip) : 0);
+    const size_t rtrace_n = (size_t)16 * kRsosTraceIters * 8;
+    if (rtracing) {
+        if (!d_rtrace) HIPCHECK(hipMalloc(&d_rtrace, rtrace_n * 8));
+        HIPCHECK(hipMemsetAsync(d_rtrace, 0, rtrace_n * 8, st));
+        rs.trace = d_rtrace;
+    }
+    const double* rtab = (const double*)P->bufs[S.rsos_tab_buf >= 0 ? S.rsos_tab_buf : S3.tab_buf].d;
+    const int* rjend = (const int*)P->bufs[S.rsos_jend_buf >= 0 ? S.rsos_jend_buf : S3.jend_buf].d;
+    if (launch_rsos(rtab, rjend, rs, yk, global_tables(P, S3), S.rsos_grid, st) != 0)
+        fail(SO_ERR_RUNTIME, "internal: no fused resampler + IIR instantiation for this geometry");
+    if (rtracing) dump_rsos_trace(d_rtrace, rtrace_n, rs, st);
+    int nl = 1;
+    if (rs.bad && S.rsos_jrel_buf >= 0 && !std::getenv("SIGOPS_RSOS_NO_FIXUP")) {
+        // behind a non-finite sample the reference stays non-finite: NaN over everything after the first bad
+        // range -- and INSIDE that range the block the sample fell into (the block form makes all 16 outputs
+        // non-finite, and a group's window is wider than an output's) output by output the reference's way
+        RsFixup fx{};
+        set_rsos_fixup(fx, P, S, RsosItem{rs, rtab, rjend, yk, global_tables(P, S3)});
+        nl += launch_rsos_fixup(fx, st);
+    } else if (rs.bad) {
+        SosGeom pg = g;
+        pg.n = rs.n_out;
+        pg.chunk = rs.pr * rs.L;
+        pg.nchunks = rs.nranges;
+        pg.store_lo = rs.store_lo;
+        pg.bad = rs.bad;
+        nl += launch_sos_poison(yk, pg, st);
+    }
+    return nl;
+}
+
+static int run_sos(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const size_t esz = dsize(N.dtype);
+    const View in = stage_in(P, S, N.nch, N.dtype), out = stage_out(P, s.idx, outp);
+    SosGeom g = S.sg;
+    g.in_pitch = in.pitch;
+    g.out_pitch = out.pitch;
+    g.store_lo = s.idx == P->alias_stage ? P->alias_skip : 0;
+    if (s.idx == P->alias_stage && P->alias_narrow) g.out_dtype = SO_F32;
+    g.align_rows = S.pre_stage < 0 && !std::getenv("SIGOPS_SOS_NOALIGN");
+    g.bad = nullptr;
+    // (the planner fuses only what is none of the forms below: fuse_resample_sos, fuse_plain_sos)
+    if (S.rsos_src >= 0) return run_rsos_fused(P, S, g, out, st);
+    if (S.bad_buf >= 0 && S.pre_stage < 0 && !S.onepass && !S.xscan && !g.exact && !std::getenv("SIGOPS_SOS_NOPOISON")) {
+        g.bad = (int32_t*)P->bufs[S.bad_buf].d;
+        arm_bad(g.bad, (size_t)N.nch, st);
+    }
+    int nl = 0;
+    for (size_t gi = 0; gi < S.groups.size() && S.onepass; ++gi) {
+        const void* x = gi == 0 ? (const void*)in.d : (const void*)out.d;
+        SosOne o = S.so1;
+        o.in_pitch = gi == 0 ? in.pitch : out.pitch;
+        o.out_pitch = out.pitch;
+        const int64_t al = 16 / (int64_t)esz;
+        o.vec_in = ((uintptr_t)x % 16 == 0) && (o.in_pitch % al == 0);
+        o.vec_out = ((uintptr_t)out.d % 16 == 0) && (o.out_pitch % al == 0);
+        const Buf& sb = P->bufs[S.one_sync_buf];
+        const Buf& vb = P->bufs[S.one_vpub_buf];
+        // (kernel nodes, not memset nodes, as for the poison words: this sequence is graph-capturable too, and a
+        //  stale ticket counter would hang the kernel -- k_small.hip)
+        if (sb.bytes % 4 == 0 && vb.bytes % 4 == 0) {
+            HIPCHECK((hipError_t)launch_fill_u32(sb.d, sb.bytes / 4, 0u, st));           // ticket counter
+            HIPCHECK((hipError_t)launch_fill_u32(vb.d, vb.bytes / 4, 0xffffffffu, st));  // "not published yet"
+        } else {
+            HIPCHECK(hipMemsetAsync(sb.d, 0, sb.bytes, st));
+            HIPCHECK(hipMemsetAsync(vb.d, 0xff, vb.bytes, st));
+        }
+        launch_sos_onepass(x, out.d, o, S.groups[gi], (const double*)P->bufs[S.one_tabs_buf].d + S.one_tabs_off[gi],
+                           (int*)sb.d, (double*)vb.d, N.dtype, st);
+        nl += 1;
+    }
+    if (S.pre_stage >= 0) {
+        const Stage& S3 = P->stages[S.pre_stage];
+        nl += launch_sos_prestate(in.d, out.d, (const double*)P->bufs[S3.vper_buf].d, S3.rp.nperiods,
+                                  (const double*)P->bufs[S.qmat_buf].d, S3.rp.pt, (double*)P->bufs[S.v_buf].d,
+                                  (double*)P->bufs[S.s0_buf].d, (const double*)P->bufs[S.mpow_buf].d, g, S.groups[0], st);
+    }
+    bool exact_done = false;
+    if (g.exact && !S.onepass && S.pre_stage < 0 && S.groups.size() <= 2) {
+        // ill-conditioned cascade: DSP.jl's order of operations, one sequence per channel
+        exact_done = launch_sos_exact(in.d, out.d, g, S.groups[0], S.groups.size() > 1 ? S.groups[1] : SosCoefs{}, st) == 0;
+        if (exact_done) nl += 1;
+    }
+    for (size_t gi = 0; gi < S.groups.size() && !S.onepass && S.pre_stage < 0 && !exact_done; ++gi) {
+        // (later groups filter the output in place)
+        const void* x = gi == 0 ? (const void*)in.d : (const void*)out.d;
+        SosGeom gg = g;
+        if (gi > 0) gg.in_pitch = out.pitch;
+        if (gi == 0 && S.src_op) set_sine_source(gg, S);
+        // frames beyond the child's end are zero (Pad(x.signal,zero), reference src/filters.jl:240): the materialised
+        // input covers them; a direct source always has in_frames == need
+        if (S.xscan) {  // exact scan between the state pass and the output pass
+            double* vb = (double*)P->bufs[S.v_buf].d;
+            double* sb = (double*)P->bufs[S.s0_buf].d;
+            nl += launch_sos_phase(x, out.d, vb, nullptr, gg, S.groups[gi], 1, st);
+            nl += launch_sos_xscan(vb, sb, (const double*)((char*)P->bufs[S.xs_mats_buf].d + gi * 2 * 16 * 16 * 8),
+                                   (double*)P->bufs[S.sblk_buf].d, gg, S.groups[gi].nsec, st);
+            nl += launch_sos_phase(x, out.d, nullptr, sb, gg, S.groups[gi], 3, st);
+            continue;
+        }
+        nl += launch_sos(x, out.d, S.v_buf >= 0 ? (double*)P->bufs[S.v_buf].d : nullptr,
+                         S.s0_buf >= 0 ? (double*)P->bufs[S.s0_buf].d : nullptr,
+                         S.mpow_buf >= 0 ? (const double*)((char*)P->bufs[S.mpow_buf].d + gi * S.mpow_stride() * 8) : nullptr,
+                         gg, S.groups[gi], st);
+        nl += launch_sos_poison(out.d, gg, st);  // (behind a NaN the reference stays NaN: SosGeom::bad)
+        if (gg.bad && gi + 1 < S.groups.size()) arm_bad(gg.bad, (size_t)N.nch, st);
+    }
+    return nl;
+}
+
+// the periodic resampler reads through its carriers; behind it, where a non-finite sample reached the accumulators, the
+// launch that recomputes those outputs the reference's way
+static void run_resample_periodic(Plan* P, const Step& s, const View& out, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    RsPeriodic rp = S.rp;
+    rp.in_pitch = 0;
+    rp.out_pitch = out.pitch;
+    rp.out_f32 = s.idx == P->alias_stage && P->alias_narrow;
+    if (rp.nstate > 0) {
+        rp.wtab = (const double*)P->bufs[S.wtab_buf].d;
+        rp.vper = (double*)P->bufs[S.vper_buf].d;
+    }
+    const int64_t al = 16 / (int64_t)dsize(N.dtype);
+    rp.vec_ok = ((uintptr_t)out.d % 16 == 0) && (out.pitch % al == 0) && (rp.L % al == 0);
+    static long long* d_trace = nullptr;  // SIGOPS_RS_TRACE tuning aid
+    const bool tracing = std::getenv("SIGOPS_RS_TRACE") != nullptr;
+    const size_t trace_n = (size_t)16 * kRsTraceIters * kRsTraceStamps;
+    if (tracing) {
+        if (!d_trace) HIPCHECK(hipMalloc(&d_trace, trace_n * 8));
+        HIPCHECK(hipMemsetAsync(d_trace, 0, trace_n * 8, st));
+        rp.trace = d_trace;
+    }
+    // (the list of (tile, group)s a non-finite sample reached, and the launch that recomputes them the reference's
+    //  way: plain sources only -- a gain applied at the MFMA operand, a second array, a state pass keep the kernel's set)
+    const bool nf_fix = S.rs_nf_buf >= 0 && S.rs_jrel_buf >= 0 && rp.ga == 0 && rp.arr2 == 0 && rp.nstate == 0 && S.ctl_buf >= 0 &&
+                        S.car_buf >= 0 && !S.carriers.empty() && rp.rows <= 32 && rp.kw <= 160;
+    rp.nf = nf_fix ? (uint32_t*)P->bufs[S.rs_nf_buf].d : nullptr;
+    const double* tab = (const double*)P->bufs[S.tab_buf].d;
+    const int* jend = (const int*)P->bufs[S.jend_buf].d;
+    if (launch_resample_periodic(out.d, tab, jend, rp, N.dtype, global_tables(P, S), st) != 0)
+        fail(SO_ERR_RUNTIME, "internal: no periodic resampler instantiation for this geometry");
+    if (nf_fix) {
+        RsPerFixup fx{};
+        fx.g = rp;
+        fx.tab = tab;
+        fx.jend = jend;
+        fx.jrel = (const int*)P->bufs[S.rs_jrel_buf].d;
+        fx.taps = S.rg.taps;
+        fx.out_f32 = (N.dtype == SO_F32 || rp.out_f32) ? 1 : 0;
+        fx.gsrc = global_tables(P, S);
+        fx.y = out.d;
+        (void)launch_rs_fixup(fx, st);  // (a launch Step::launches has never counted: tests and recorded profiles pin the numbers)
+    }
+    if (tracing) dump_rs_trace(d_trace, trace_n, rp, st);
+}
+
+static int run_resample(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const View in = S.periodic ? View{nullptr, 0} : stage_in(P, S, N.nch, N.dtype), out = stage_out(P, s.idx, outp);
+    const double* pfbt = S.tiled ? (const double*)P->bufs[S.pfbt_buf].d : nullptr;
+    const double* dpfbt = S.tiled ? (const double*)P->bufs[S.dpfbt_buf].d : nullptr;
+    if (S.periodic)
+        run_resample_periodic(P, s, out, st);
+    else if (S.rows) {
+        RsRows rr = S.rr;
+        rr.in_pitch = in.pitch;
+        rr.out_pitch = out.pitch;
+        if (std::getenv("SIGOPS_DEBUG_PLAN"))
+            std::fprintf(stderr, "[sigops] k_resample_rows: ct=%d pb=%d tile_len=%d pitch=%d kw=%d ngroups=%d L=%lld M=%lld taps=%d\n", rr.ct, rr.pb,
+                         rr.tile_len, rr.pitch, rr.kw, rr.ngroups, (long long)rr.L, (long long)rr.M, rr.taps);
+        launch_resample_rows(in.d, out.d, (const double*)P->bufs[S.tab_buf].d, (const int*)P->bufs[S.jend_buf].d,
+                             (const double*)P->bufs[S.mtab_buf].d, (const int*)P->bufs[S.mjend_buf].d, rr, N.dtype, st);
+    } else if (S.tiled) {
+        RsTiled rt = S.rt;
+        rt.g.in_pitch = in.pitch;
+        rt.g.out_pitch = out.pitch;
+        bool done = false;
+        if (S.arbk) {  // the persistent form, where it has an instantiation for the geometry
+            RsArb ra = S.ra;
+            ra.g.in_pitch = in.pitch;
+            ra.g.out_pitch = out.pitch;
+            ra.err = kernel_error_word(P);
+            done = launch_resample_arb(in.d, out.d, pfbt, dpfbt, ra, st) == 0;
+        }
+        if (!done && rt.pair) launch_resample_tiled2(in.d, out.d, pfbt, dpfbt, rt, st);
+        else if (!done) launch_resample_tiled(in.d, out.d, pfbt, dpfbt, rt, st);
+    } else {
+        RsGeom g = S.rg;
+        g.in_pitch = in.pitch;
+        g.out_pitch = out.pitch;
+        launch_resample(in.d, out.d, (const double*)P->bufs[S.pfb_buf].d, (const double*)P->bufs[S.dpfb_buf].d, g, st);
+    }
+    if (S.fix_buf < 0) return 1;
+    RsFixArgs fa{};  // the outputs DSP.jl's phase accumulator places differently
+    fa.fix = (const RsFix*)P->bufs[S.fix_buf].d;
+    fa.nfix = (int64_t)S.fix_host.size();
+    fa.pfb = (const double*)P->bufs[S.pfb_buf].d;
+    fa.dpfb = (const double*)P->bufs[S.dpfb_buf].d;
+    fa.n_in = S.rg.n_in;
+    fa.taps = S.rg.taps;
+    fa.nch = N.nch;
+    fa.stage_dtype = N.dtype;
+    fa.out_dtype = (s.idx == P->alias_stage && P->alias_narrow) ? SO_F32 : N.dtype;
+    if (S.periodic) {
+        fa.car = (const DCarrier*)P->bufs[S.car_buf].d;
+        fa.ncar = (int)S.carriers.size();
+        fa.ops = P->d_ops;
+        fa.leaves = P->d_leaves;
+    } else {
+        fa.x = in.d;
+        fa.in_pitch = in.pitch;
+        fa.in_dtype = N.dtype;
+    }
+    fa.y = out.d;
+    fa.out_pitch = out.pitch;
+    launch_resample_fix(fa, st);
+    return 2;
+}
+
+// the sum of squares and the rms of it (two launches), over the stage's own buffer or, norm_direct, the array where it lies
+static int run_norm(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const View v = S.norm_direct ? stage_in(P, S, N.nch, N.dtype) : stage_out(P, s.idx, outp);
+    RmsPatch patch{};
+    for (int li : S.rms_leaves) patch.dst[patch.n++] = &P->d_leaves[li].v0;
+    launch_rms(v.d, N.dtype, S.need, N.nch, v.pitch, (double*)P->bufs[S.partial_buf].d, S.nparts, (double*)P->bufs[S.rms_buf].d, st, patch);
+    return 2;
 }
 
 static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& err) {
@@ -554,603 +1130,23 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                     if (P->step_lane[d] != ln) HIPCHECK(hipStreamWaitEvent(st, P->step_done[d], 0));
             }
             if (P->profiling) HIPCHECK(hipEventRecord(P->events[ev0 + 2 * si], st));
-            if (s.kind == 0) {
-                PwStep& w = P->pw[s.idx];
-                OutView ov{};
-                if (w.nblocks <= 0) {
-                    // empty rectangle (zero-frame sink): nothing to launch
-                } else if (w.out_buf >= 0) {
-                    Buf& b = P->bufs[w.out_buf];
-                    ov.base = b.d;
-                    ov.fstride = 1;
-                    ov.cstride = b.pitch;
-                    ov.dtype = b.dtype;
-                } else if (P->out.is_device) {
-                    ov.base = outp;
-                    ov.fstride = P->out.frame_stride;
-                    ov.cstride = P->out.chan_stride;
-                    ov.dtype = P->out.dtype;
-                } else {
-                    Buf& b = P->bufs[P->out_stage_buf];
-                    ov.base = b.d;
-                    ov.fstride = P->interleaved_host ? P->out.nch : 1;
-                    ov.cstride = P->interleaved_host ? 1 : b.pitch;
-                    ov.dtype = b.dtype;
-                }
-                if (w.nblocks > 0) {
-                    static const int il_scalar = std::getenv("SIGOPS_K1_ILSCALAR") ? 1 : 0;  // ablation knob
-                    ov.pad = il_scalar;
-                    if (w.fill)
-                        launch_randn_fill(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_leaves, ov, st);
-                    else if (w.rtc) {
-                        if (rtc_launch(w.rtc, w.nblocks, P->d_pieces + w.piece0, w.npieces, P->d_leaves, ov, st) != 0)
-                            fail(SO_ERR_RUNTIME, "hipRTC kernel launch failed");
-                    } else
-                        launch_pointwise(P->d_pieces + w.piece0, w.npieces, w.nblocks, P->d_ops, P->d_leaves, ov, w.deep, st, w.chain,
-                                         w.il || (ov.fstride > 1 && ov.cstride == 1), w.math);
-                    s.launches = 1;
-                    launches++;
-                }
-            } else if (s.kind == 2) {
-                SosBatch& B = P->batches[s.idx];
-                const size_t nm = B.members.size();
-                std::vector<SosDesc> d(nm + 1);
-                int64_t first[3] = {0, 0, 0};
-                for (size_t m = 0; m <= nm; ++m) {
-                    SosDesc& D = d[m];
-                    std::memset(&D, 0, sizeof D);
-                    for (int q = 0; q < 3; ++q) D.first[q] = first[q];
-                    if (m == nm) break;
-                    const int sid = B.members[m];
-                    const Stage& S = P->stages[sid];
-                    const Node& N = P->nodes[S.node];
-                    const size_t esz = dsize(N.dtype);
-                    const so_node_t& nd = P->nodes[S.in_array_node].nd;
-                    const char* base = nd.i0 ? (const char*)P->array_ptr[S.in_array_node] : (const char*)P->bufs[P->array_buf[S.in_array_node]].d;
-                    Buf ob = P->bufs[S.out_buf];
-                    if (sid == P->alias_stage) {
-                        if (P->out.is_device) {
-                            ob.d = outp;
-                            ob.pitch = N.nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
-                        } else {
-                            ob.d = P->bufs[P->out_stage_buf].d;
-                            ob.pitch = P->bufs[P->out_stage_buf].pitch;
-                        }
-                        ob.d = (char*)ob.d - (size_t)P->alias_skip * (P->alias_narrow ? dsize(P->out.dtype) : esz);
-                    } else if (S.win_off >= 0) {
-                        const Buf& ab = P->bufs[P->out_alias_buf];
-                        ob.d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * esz;
-                        ob.pitch = ab.pitch;
-                    }
-                    D.x = base + (size_t)S.in_offset * esz;
-                    D.y = ob.d;
-                    D.v = S.v_buf >= 0 ? (double*)P->bufs[S.v_buf].d : nullptr;
-                    D.s0 = S.s0_buf >= 0 ? (double*)P->bufs[S.s0_buf].d : nullptr;
-                    D.mpow = S.mpow_buf >= 0 ? (const double*)P->bufs[S.mpow_buf].d : nullptr;
-                    D.g = S.sg;
-                    D.g.in_pitch = N.nch == 1 ? 0 : S.in_pitch;
-                    D.g.out_pitch = ob.pitch;
-                    D.g.store_lo = sid == P->alias_stage ? P->alias_skip : 0;
-                    if (sid == P->alias_stage && P->alias_narrow) D.g.out_dtype = SO_F32;
-                    D.g.align_rows = !std::getenv("SIGOPS_SOS_NOALIGN");
-                    D.g.bad = B.bad_buf >= 0 && S.sg.nchunks > 1 && !std::getenv("SIGOPS_SOS_NOPOISON")
-                                  ? (int32_t*)P->bufs[B.bad_buf].d + B.bad_off[m] : nullptr;
-                    if (S.src_op) {  // fused sine source of the cascade's input (as below)
-                        const DLeaf& F = S.src_fn;
-                        D.g.src_op = S.src_op;
-                        D.g.src_has_omega = F.flag;
-                        D.g.src_df = F.df;
-                        D.g.src_omega = F.v0;
-                        D.g.src_phi = F.v1;
-                        D.g.src_fs = F.v2;
-                        const double step = 6.283185307179586476925 * (F.flag ? F.v0 / F.v2 : 1.0 / F.v2);
-                        D.g.src_cd = std::cos(step);
-                        D.g.src_sd = std::sin(step);
-                    }
-                    D.cf = S.groups[0];
-                    const int64_t nseq = (int64_t)D.g.nchunks * D.g.nch;
-                    if (D.g.nchunks > 1) {
-                        first[0] += ((int64_t)(D.g.nchunks - 1) * D.g.nch + kBlock - 1) / kBlock;
-                        first[1] += (nseq + kBlock - 1) / kBlock;
-                    } else
-                        D.s0 = nullptr;  // one chunk: starts from rest
-                    first[2] += (nseq + kBlock - 1) / kBlock;
-                }
-                if (first[2] >= ((int64_t)1 << 31)) fail(SO_ERR_RUNTIME, "internal: batched IIR grid too large");
-                if (B.host.size() != d.size() || std::memcmp(B.host.data(), d.data(), d.size() * sizeof(SosDesc)) != 0) {
-                    // the descriptors change only when the result or an array moves -- never between the direct
-                    // execute for a result pointer and the capture that follows it (plan_execute), so a captured
-                    // graph holds the three launches only and reads the table this copy left on the device
-                    B.host = d;
-                    HIPCHECK(hipMemcpyAsync(P->bufs[B.desc_buf].d, B.host.data(), B.host.size() * sizeof(SosDesc), hipMemcpyHostToDevice, st));
-                }
-                for (int q = 0; q < 3; ++q) B.total[q] = first[q];
-                const bool poison = B.bad_buf >= 0 && !std::getenv("SIGOPS_SOS_NOPOISON");
-                if (poison) HIPCHECK((hipError_t)launch_fill_u32(P->bufs[B.bad_buf].d, P->bufs[B.bad_buf].bytes / 4, 0x7f7f7f7fu, st));  // "no non-finite chunk yet"
-                int nl = launch_sos_batch((const SosDesc*)P->bufs[B.desc_buf].d, (int)nm, B.nsec, B.dtype, B.total, st);
-                if (poison) nl += launch_sos_poison_batch((const SosDesc*)P->bufs[B.desc_buf].d, (int)nm, B.dtype, st);
-                s.launches = nl;
-                launches += nl;
-            } else if (s.kind == 3) {
-                // plain filters, one pass each, ONE launch (k_rsos_batch): per member what the single launch below sets up
-                RsBatch& B = P->rsbatches[s.idx];
-                const size_t nm = B.members.size();
-                std::vector<RsosItem> items(nm);
-                std::vector<RsFixup> fix(nm);
-                const bool poison = B.bad_buf >= 0 && !std::getenv("SIGOPS_SOS_NOPOISON");
-                int maxch = 1, out_f32 = 0;
-                for (size_t m = 0; m < nm; ++m) {
-                    const int sid = B.members[m];
-                    const Stage& S = P->stages[sid];
-                    const Node& N = P->nodes[S.node];
-                    const size_t esz = dsize(N.dtype);
-                    Buf ob = P->bufs[S.out_buf];
-                    if (S.win_off >= 0) {  // its window of the result
-                        const Buf& ab = P->bufs[P->out_alias_buf];
-                        ob.d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * esz;
-                        ob.pitch = ab.pitch;
-                    }
-                    RsosItem& I = items[m];
-                    std::memset(&I, 0, sizeof I);
-                    RsSos rs = S.rs;
-                    rs.out_pitch = ob.pitch;
-                    rs.out_f32 = N.dtype == SO_F32;
-                    rs.f32m = 0;
-                    rs.sring = 0;
-                    rs.mats = (const double*)P->bufs[S.rsos_mats_buf].d;
-                    rs.bad = poison ? (int32_t*)P->bufs[B.bad_buf].d + B.bad_off[m] : nullptr;
-                    rs.err = kernel_error_word(P);
-                    I.g = rs;
-                    I.tab = (const double*)P->bufs[S.rsos_tab_buf].d;
-                    I.jend = (const int*)P->bufs[S.rsos_jend_buf].d;
-                    I.y = (char*)ob.d - (size_t)S.rs.store_lo * (rs.out_f32 ? 4 : 8);
-                    I.gsrc = RsGlobalTables{(const RsCtl*)P->bufs[S.ctl_buf].d, (const DCarrier*)P->bufs[S.car_buf].d, P->d_ops, P->d_leaves};
-                    RsFixup& F = fix[m];
-                    std::memset(&F, 0, sizeof F);
-                    F.g = rs;
-                    F.tab = I.tab;
-                    F.jend = I.jend;
-                    F.jrel = (const int*)P->bufs[S.rsos_jrel_buf].d;
-                    F.taps = S.rsos_taps;
-                    F.cf = S.groups[0];
-                    F.gsrc = I.gsrc;
-                    F.y = I.y;
-                    maxch = std::max(maxch, (int)rs.nch);
-                    out_f32 = rs.out_f32;
-                }
-                if (B.host.size() != nm || std::memcmp(B.host.data(), items.data(), nm * sizeof(RsosItem)) != 0 ||
-                    std::memcmp(B.fhost.data(), fix.data(), nm * sizeof(RsFixup)) != 0) {
-                    // (as the three-pass batch's descriptors: the tables change only when the result or an array moves -- never
-                    //  between the direct execute for a result pointer and the capture that follows it)
-                    B.host = items;
-                    B.fhost = fix;
-                    HIPCHECK(hipMemcpyAsync(P->bufs[B.items_buf].d, B.host.data(), nm * sizeof(RsosItem), hipMemcpyHostToDevice, st));
-                    HIPCHECK(hipMemcpyAsync(P->bufs[B.fix_buf].d, B.fhost.data(), nm * sizeof(RsFixup), hipMemcpyHostToDevice, st));
-                }
-                if (poison) HIPCHECK((hipError_t)launch_fill_u32(P->bufs[B.bad_buf].d, P->bufs[B.bad_buf].bytes / 4, 0x7f7f7f7fu, st));  // "no non-finite range yet"
-                if (launch_rsos_batch((const RsosItem*)P->bufs[B.items_buf].d, (int)nm, B.gpm, items[0].g, st) != 0)
-                    fail(SO_ERR_RUNTIME, "internal: no batched one-pass IIR instantiation for this geometry");
-                int nl = 1;
-                if (poison) nl += launch_rsos_fixup_batch((const RsFixup*)P->bufs[B.fix_buf].d, (int)nm, maxch, out_f32, st);
-                s.launches = nl;
-                launches += nl;
-            } else if (P->stages[s.idx].kind == ST_SAMPLEAT) {
-                const Stage& S = P->stages[s.idx];
-                const Node& N = P->nodes[S.node];
-                SampleAtArgs a{};
-                const int xdt = P->nodes[N.kids[0]].dtype;
-                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
-                a.xfs = S.x_fstride;
-                a.N = S.in_frames;
-                a.x_f32 = xdt == SO_F32;
-                if (S.pos_array_node >= 0) {
-                    a.pos = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
-                    a.pcs = S.pos_pitch;
-                } else {
-                    const Buf& b = P->bufs[S.pos_buf];
-                    a.pos = (const double*)b.d;
-                    a.pcs = S.pos_pitch == 0 ? 0 : b.pitch;
-                }
-                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
-                a.base = S.base;
-                a.n = S.need - S.base;
-                a.left = N.nd.d0;
-                a.right = N.nd.d1;
-                a.nch = N.nch;
-                a.relative = N.nd.i0 & 1;
-                a.wrap = (N.nd.i0 >> 1) & 1;
-                const int nl = launch_sample_at(a, st);
-                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "SampleAt: more than 65535 channels or 2^39 frames are not lowered");
-                s.launches = nl;
-                launches += nl;
-            } else if (P->stages[s.idx].kind == ST_COMB) {
-                const Stage& S = P->stages[s.idx];
-                const Node& N = P->nodes[S.node];
-                CombArgs a{};
-                const int xdt = P->nodes[N.kids[0]].dtype;
-                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
-                a.xfs = S.x_fstride;
-                a.x_f32 = xdt == SO_F32;
-                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
-                a.n = S.need;
-                a.D = N.nd.l0;
-                a.b0 = N.nd.d0;
-                a.bD = N.nd.d1;
-                a.a = N.nd.d2;
-                a.nch = N.nch;
-                if (a.D < 1) fail(SO_ERR_INVALID, "Comb: a delay of less than one frame");  // (the planner has refused it)
-                const int nl = launch_comb(a, st);
-                // (one lane per frame mod D: min(D, frames) lanes a channel, in blocks of kBlock, must fit grid.x)
-                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Comb: more than 65535 channels, or a delay AND a signal of 2^39 frames and more, are not lowered");
-                s.launches = nl;
-                launches += nl;
-            } else if (P->stages[s.idx].kind == ST_CUMSUM) {
-                const Stage& S = P->stages[s.idx];
-                const Node& N = P->nodes[S.node];
-                CumsumArgs a{};
-                const int xdt = P->nodes[N.kids[0]].dtype;
-                a.x = stage_input_view(P, S, N.nch, xdt, a.xcs);
-                a.xfs = S.x_fstride;
-                a.x_f32 = xdt == SO_F32;
-                a.y = stage_output_view(P, (int)s.idx, outp, a.ycs);
-                a.n = S.need;
-                a.nch = N.nch;
-                a.tot_pitch = cumsum_totals(S.need);
-                a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
-                const int nl = launch_cumsum(a, st);
-                // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
-                if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Cumsum: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
-                s.launches = nl;
-                launches += nl;
-            } else {
-                Stage& S = P->stages[s.idx];
-                Node& N = P->nodes[S.node];
-                size_t esz = dsize(N.dtype);
-                const char* inp;
-                int64_t in_pitch;
-                if (S.kind == ST_RESAMPLE && S.periodic) {
-                    inp = nullptr;  // the periodic kernel reads through its carriers
-                    in_pitch = 0;
-                } else if (S.in_array_node >= 0) {
-                    const so_node_t& nd = P->nodes[S.in_array_node].nd;
-                    const char* base = nd.i0 ? (const char*)P->array_ptr[S.in_array_node]
-                                             : (const char*)P->bufs[P->array_buf[S.in_array_node]].d;
-                    inp = base + (size_t)S.in_offset * esz;
-                    in_pitch = N.nch == 1 ? 0 : S.in_pitch;
-                } else {
-                    Buf& b = P->bufs[S.in_buf];
-                    inp = (const char*)b.d + (size_t)(S.in_offset - b.frame0) * esz;
-                    in_pitch = b.pitch;
-                }
-                Buf ob = P->bufs[S.out_buf];
-                if (s.idx == P->alias_stage) {  // write the sink buffer directly
-                    if (P->out.is_device) {
-                        ob.d = outp;
-                        ob.pitch = N.nch == 1 ? std::max<int64_t>(P->out.chan_stride, S.need) : P->out.chan_stride;
-                    } else {
-                        ob.d = P->bufs[P->out_stage_buf].d;
-                        ob.pitch = P->bufs[P->out_stage_buf].pitch;
-                    }
-                    // (local frame alias_skip is the result's frame 0; earlier frames are not stored)
-                    ob.d = (char*)ob.d - (size_t)P->alias_skip * (P->alias_narrow ? dsize(P->out.dtype) : esz);
-                } else if (S.win_off >= 0) {  // ... or its window of it
-                    const Buf& ab = P->bufs[P->out_alias_buf];
-                    ob.d = (char*)(P->out.is_device ? outp : ab.d) + (size_t)S.win_off * esz;
-                    ob.pitch = ab.pitch;
-                }
-                if (S.kind == ST_SOS) {
-                    SosGeom g = S.sg;
-                    g.in_pitch = in_pitch;
-                    g.out_pitch = ob.pitch;
-                    g.store_lo = s.idx == P->alias_stage ? P->alias_skip : 0;
-                    if (s.idx == P->alias_stage && P->alias_narrow) g.out_dtype = SO_F32;
-                    g.align_rows = S.pre_stage < 0 && !std::getenv("SIGOPS_SOS_NOALIGN");
-                    g.bad = nullptr;
-                    if (S.bad_buf >= 0 && S.pre_stage < 0 && S.rsos_src < 0 && !S.onepass && !S.xscan && !g.exact &&
-                        !std::getenv("SIGOPS_SOS_NOPOISON")) {
-                        g.bad = (int32_t*)P->bufs[S.bad_buf].d;
-                        HIPCHECK((hipError_t)launch_fill_u32(g.bad, (size_t)N.nch, 0x7f7f7f7fu, st));  // "no non-finite chunk yet"
-                    }
-                    size_t msz = 0;
-                    for (auto& v : S.mpow_host) msz = std::max(msz, v.size());
-                    int nl = 0;
-                    if (S.rsos_src >= 0) {  // the resampler in front and this cascade in one launch (k_rsos)
-                        const Stage& S3 = P->stages[S.rsos_src];
-                        RsSos rs = S.rs;
-                        rs.out_pitch = ob.pitch;
-                        rs.out_f32 = g.out_dtype == SO_F32 || N.dtype == SO_F32;
-                        if (rs.f32m && rs.out_f32) rs.ring32 = 1;  // (a Float32 result: Float32 samples in the ring, the Float32 MFMA)
-                        else rs.f32m = 0;
-                        rs.sring = rs.f32m && (rs.fuse == 1 || rs.fuse == 2) && !std::getenv("SIGOPS_RSOS_NO_SRING") ? 1 : 0;
-                        // the kernel's output m is frame m - store_lo of this stage's buffer (a window: the resampler's warm
-                        // start lies store_lo frames before the cascade's); the sink's own skipped frames come on top
-                        char* const yk = (char*)ob.d - (size_t)S.rs.store_lo * (rs.out_f32 ? 4 : 8);
-                        rs.store_lo = S.rs.store_lo + g.store_lo;
-                        rs.mats = (const double*)P->bufs[S.rsos_mats_buf].d;
-                        rs.bad = nullptr;
-                        if (S.bad_buf >= 0 && rs.nranges >= 1 && !std::getenv("SIGOPS_SOS_NOPOISON")) {
-                            rs.bad = (int32_t*)P->bufs[S.bad_buf].d;
-                            HIPCHECK((hipError_t)launch_fill_u32(rs.bad, (size_t)N.nch, 0x7f7f7f7fu, st));  // "no non-finite range yet"
-                        }
-                        rs.err = kernel_error_word(P);
-                        static long long* d_rtrace = nullptr;  // SIGOPS_RSOS_TRACE tuning aid
-                        // (SIGOPS_RSOS_TRACE_SKIP=n: not the first n launches of the process -- a traced launch synchronises, and a run
-                        //  of traced launches never leaves the chip's power-management transient)
-                        static int rtrace_seen = 0;
-                        const char* const rtrace_skip = std::getenv("SIGOPS_RSOS_TRACE_SKIP");
-                        const bool rtracing = std::getenv("SIGOPS_RSOS_TRACE") != nullptr && rtrace_seen++ >= (rtrace_skip ? std::atoi(rtrace_skip) : 0);
-                        const size_t rtrace_n = (size_t)16 * kRsosTraceIters * 8;
-                        if (rtracing) {
-                            if (!d_rtrace) HIPCHECK(hipMalloc(&d_rtrace, rtrace_n * 8));
-                            HIPCHECK(hipMemsetAsync(d_rtrace, 0, rtrace_n * 8, st));
-                            rs.trace = d_rtrace;
-                        }
-                        const double* rtab = (const double*)P->bufs[S.rsos_tab_buf >= 0 ? S.rsos_tab_buf : S3.tab_buf].d;
-                        const int* rjend = (const int*)P->bufs[S.rsos_jend_buf >= 0 ? S.rsos_jend_buf : S3.jend_buf].d;
-                        if (launch_rsos(rtab, rjend, rs, yk,
-                                        RsGlobalTables{(const RsCtl*)P->bufs[S3.ctl_buf].d, (const DCarrier*)P->bufs[S3.car_buf].d, P->d_ops, P->d_leaves},
-                                        S.rsos_grid, st) != 0)
-                            fail(SO_ERR_RUNTIME, "internal: no fused resampler + IIR instantiation for this geometry");
-                        if (rtracing) {
-                            std::vector<long long> tr(rtrace_n);
-                            HIPCHECK(hipStreamSynchronize(st));
-                            HIPCHECK(hipMemcpy(tr.data(), d_rtrace, rtrace_n * 8, hipMemcpyDeviceToHost));
-                            long long t0 = 0;
-                            for (size_t i = 0; i < rtrace_n; ++i)
-                                if (tr[i] && (!t0 || tr[i] < t0)) t0 = tr[i];
-                            if (std::atoi(std::getenv("SIGOPS_RSOS_TRACE")) == 2) {  // a -DSO_RSOS_COUNT=1 build: poll counters, raw
-                                for (int w = 0; w < rs.nwaves; ++w)
-                                    for (int it = 0; it < 5; ++it) {
-                                        const long long* q = &tr[((size_t)w * kRsosTraceIters + it) * 8];
-                                        bool any = false;
-                                        for (int k = 0; k < 8; ++k) any = any || q[k];
-                                        if (!any) continue;
-                                        std::fprintf(stderr, "[rsos-count] w%02d row%d", w, it);
-                                        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %lld", q[k] - 1);
-                                        std::fprintf(stderr, "\n");
-                                    }
-                            } else
-                            for (int w = 0; w < rs.nwaves; ++w)
-                                for (int it = 0; it < kRsosTraceIters; ++it) {
-                                    const long long* q = &tr[((size_t)w * kRsosTraceIters + it) * 8];
-                                    if (!q[0] && !q[2]) continue;
-                                    std::fprintf(stderr, "[rsos-trace] %s w%02d it%02d", w == 0 ? "C" : (w & 3) == 0 ? "L" : "Y", w, it);
-                                    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %lld", q[k] ? q[k] - t0 : -1);
-                                    std::fprintf(stderr, "\n");
-                                }
-                        }
-                        nl = 1;
-                        if (rs.bad && S.rsos_jrel_buf >= 0 && !std::getenv("SIGOPS_RSOS_NO_FIXUP")) {
-                            // behind a non-finite sample the reference stays non-finite: NaN over everything after the first bad
-                            // range -- and INSIDE that range the block the sample fell into (the block form makes all 16 outputs
-                            // non-finite, and a group's window is wider than an output's) output by output the reference's way
-                            RsFixup fx{};
-                            fx.g = rs;
-                            fx.tab = rtab;
-                            fx.jend = rjend;
-                            fx.jrel = (const int*)P->bufs[S.rsos_jrel_buf].d;
-                            fx.taps = S.rsos_taps;
-                            fx.cf = S.groups[0];
-                            fx.gsrc = RsGlobalTables{(const RsCtl*)P->bufs[S3.ctl_buf].d, (const DCarrier*)P->bufs[S3.car_buf].d, P->d_ops, P->d_leaves};
-                            fx.y = yk;
-                            nl += launch_rsos_fixup(fx, st);
-                        } else if (rs.bad) {
-                            SosGeom pg = g;
-                            pg.n = rs.n_out;
-                            pg.chunk = rs.pr * rs.L;
-                            pg.nchunks = rs.nranges;
-                            pg.store_lo = rs.store_lo;
-                            pg.bad = rs.bad;
-                            nl += launch_sos_poison(yk, pg, st);
-                        }
-                    }
-                    for (size_t gi = 0; gi < S.groups.size() && S.onepass; ++gi) {
-                        const void* x = gi == 0 ? (const void*)inp : (const void*)ob.d;
-                        SosOne o = S.so1;
-                        o.in_pitch = gi == 0 ? in_pitch : ob.pitch;
-                        o.out_pitch = ob.pitch;
-                        const int64_t al = 16 / (int64_t)esz;
-                        o.vec_in = ((uintptr_t)x % 16 == 0) && (o.in_pitch % al == 0);
-                        o.vec_out = ((uintptr_t)ob.d % 16 == 0) && (o.out_pitch % al == 0);
-                        Buf& sb = P->bufs[S.one_sync_buf];
-                        Buf& vb = P->bufs[S.one_vpub_buf];
-                        // (kernel nodes, not memset nodes, as for the poison words: this sequence is graph-capturable too, and a
-                        //  stale ticket counter would hang the kernel -- k_small.hip)
-                        if (sb.bytes % 4 == 0 && vb.bytes % 4 == 0) {
-                            HIPCHECK((hipError_t)launch_fill_u32(sb.d, sb.bytes / 4, 0u, st));           // ticket counter
-                            HIPCHECK((hipError_t)launch_fill_u32(vb.d, vb.bytes / 4, 0xffffffffu, st));  // "not published yet"
-                        } else {
-                            HIPCHECK(hipMemsetAsync(sb.d, 0, sb.bytes, st));
-                            HIPCHECK(hipMemsetAsync(vb.d, 0xff, vb.bytes, st));
-                        }
-                        launch_sos_onepass(x, ob.d, o, S.groups[gi], (const double*)P->bufs[S.one_tabs_buf].d + S.one_tabs_off[gi],
-                                           (int*)sb.d, (double*)P->bufs[S.one_vpub_buf].d, N.dtype, st);
-                        nl += 1;
-                    }
-                    if (S.pre_stage >= 0) {
-                        const Stage& S3 = P->stages[S.pre_stage];
-                        nl += launch_sos_prestate(inp, ob.d, (const double*)P->bufs[S3.vper_buf].d, S3.rp.nperiods,
-                                                  (const double*)P->bufs[S.qmat_buf].d, S3.rp.pt, (double*)P->bufs[S.v_buf].d,
-                                                  (double*)P->bufs[S.s0_buf].d, (const double*)P->bufs[S.mpow_buf].d, g,
-                                                  S.groups[0], st);
-                    }
-                    bool exact_done = false;
-                    if (g.exact && !S.onepass && S.pre_stage < 0 && S.groups.size() <= 2) {
-                        // ill-conditioned cascade: DSP.jl's order of operations, one sequence per channel
-                        SosGeom gg = g;
-                        exact_done = launch_sos_exact(inp, ob.d, gg, S.groups[0], S.groups.size() > 1 ? S.groups[1] : SosCoefs{}, st) == 0;
-                        if (exact_done) nl += 1;
-                    }
-                    for (size_t gi = 0; gi < S.groups.size() && !S.onepass && S.pre_stage < 0 && !exact_done && S.rsos_src < 0; ++gi) {
-                        const void* x = gi == 0 ? (const void*)inp : (const void*)ob.d;
-                        SosGeom gg = g;
-                        if (gi > 0) gg.in_pitch = ob.pitch;
-                        if (gi == 0 && S.src_op) {  // fused sine source of the cascade's input
-                            const DLeaf& F = S.src_fn;
-                            gg.src_op = S.src_op;
-                            gg.src_has_omega = F.flag;
-                            gg.src_df = F.df;
-                            gg.src_omega = F.v0;
-                            gg.src_phi = F.v1;
-                            gg.src_fs = F.v2;
-                            const double step = 6.283185307179586476925 * (F.flag ? F.v0 / F.v2 : 1.0 / F.v2);
-                            gg.src_cd = std::cos(step);
-                            gg.src_sd = std::sin(step);
-                        }
-                        // frames beyond the child's end are zero (Pad(x.signal,zero), reference
-                        // src/filters.jl:240): the materialised input covers them; a direct
-                        // source always has in_frames == need
-                        if (S.xscan) {  // exact scan between the state pass and the output pass
-                            double* vb = (double*)P->bufs[S.v_buf].d;
-                            double* sb = (double*)P->bufs[S.s0_buf].d;
-                            nl += launch_sos_phase(x, ob.d, vb, nullptr, gg, S.groups[gi], 1, st);
-                            nl += launch_sos_xscan(vb, sb, (const double*)((char*)P->bufs[S.xs_mats_buf].d + gi * 2 * 16 * 16 * 8),
-                                                   (double*)P->bufs[S.sblk_buf].d, gg, S.groups[gi].nsec, st);
-                            nl += launch_sos_phase(x, ob.d, nullptr, sb, gg, S.groups[gi], 3, st);
-                            continue;
-                        }
-                        nl += launch_sos(x, ob.d, S.v_buf >= 0 ? (double*)P->bufs[S.v_buf].d : nullptr,
-                                         S.s0_buf >= 0 ? (double*)P->bufs[S.s0_buf].d : nullptr,
-                                         S.mpow_buf >= 0 ? (const double*)((char*)P->bufs[S.mpow_buf].d + gi * msz * 8) : nullptr,
-                                         gg, S.groups[gi], st);
-                        nl += launch_sos_poison(ob.d, gg, st);  // (behind a NaN the reference stays NaN: SosGeom::bad)
-                        if (gg.bad && gi + 1 < S.groups.size()) HIPCHECK((hipError_t)launch_fill_u32(gg.bad, (size_t)N.nch, 0x7f7f7f7fu, st));
-                    }
-                    s.launches = nl;
-                    launches += nl;
-                } else if (S.kind == ST_RESAMPLE) {
-                    RsGeom g = S.rg;
-                    g.in_pitch = in_pitch;
-                    g.out_pitch = ob.pitch;
-                    if (S.periodic) {
-                        RsPeriodic rp = S.rp;
-                        rp.in_pitch = in_pitch;
-                        rp.out_pitch = ob.pitch;
-                        rp.out_f32 = s.idx == P->alias_stage && P->alias_narrow;
-                        if (rp.nstate > 0) {
-                            rp.wtab = (const double*)P->bufs[S.wtab_buf].d;
-                            rp.vper = (double*)P->bufs[S.vper_buf].d;
-                        }
-                        const int64_t al = 16 / (int64_t)esz;
-                        rp.vec_ok = ((uintptr_t)ob.d % 16 == 0) && (ob.pitch % al == 0) && (rp.L % al == 0);
-                        static long long* d_trace = nullptr;  // SIGOPS_RS_TRACE tuning aid
-                        const bool tracing = std::getenv("SIGOPS_RS_TRACE") != nullptr;
-                        const size_t trace_n = (size_t)16 * kRsTraceIters * kRsTraceStamps;
-                        if (tracing) {
-                            if (!d_trace) HIPCHECK(hipMalloc(&d_trace, trace_n * 8));
-                            HIPCHECK(hipMemsetAsync(d_trace, 0, trace_n * 8, st));
-                            rp.trace = d_trace;
-                        }
-                        // (the list of (tile, group)s a non-finite sample reached, and the launch that recomputes them the reference's
-                        //  way: plain sources only -- a gain applied at the MFMA operand, a second array, a state pass keep the kernel's set)
-                        const bool nf_fix = S.rs_nf_buf >= 0 && S.rs_jrel_buf >= 0 && rp.ga == 0 && rp.arr2 == 0 && rp.nstate == 0 && S.ctl_buf >= 0 &&
-                                            S.car_buf >= 0 && !S.carriers.empty() && rp.rows <= 32 && rp.kw <= 160;
-                        rp.nf = nf_fix ? (uint32_t*)P->bufs[S.rs_nf_buf].d : nullptr;
-                        if (launch_resample_periodic(ob.d, (const double*)P->bufs[S.tab_buf].d,
-                                                     (const int*)P->bufs[S.jend_buf].d, rp, N.dtype,
-                                                     RsGlobalTables{(const RsCtl*)P->bufs[S.ctl_buf].d, (const DCarrier*)P->bufs[S.car_buf].d, P->d_ops, P->d_leaves},
-                                                     st) != 0)
-                            fail(SO_ERR_RUNTIME, "internal: no periodic resampler instantiation for this geometry");
-                        if (nf_fix) {
-                            RsPerFixup fx{};
-                            fx.g = rp;
-                            fx.tab = (const double*)P->bufs[S.tab_buf].d;
-                            fx.jend = (const int*)P->bufs[S.jend_buf].d;
-                            fx.jrel = (const int*)P->bufs[S.rs_jrel_buf].d;
-                            fx.taps = S.rg.taps;
-                            fx.out_f32 = (N.dtype == SO_F32 || rp.out_f32) ? 1 : 0;
-                            fx.gsrc = RsGlobalTables{(const RsCtl*)P->bufs[S.ctl_buf].d, (const DCarrier*)P->bufs[S.car_buf].d, P->d_ops, P->d_leaves};
-                            fx.y = ob.d;
-                            s.launches += launch_rs_fixup(fx, st);
-                        }
-                        if (tracing) {
-                            std::vector<long long> tr(trace_n);
-                            HIPCHECK(hipStreamSynchronize(st));
-                            HIPCHECK(hipMemcpy(tr.data(), d_trace, trace_n * 8, hipMemcpyDeviceToHost));
-                            long long t0 = 0;
-                            for (size_t i = 0; i < trace_n; ++i)
-                                if (tr[i] && (!t0 || tr[i] < t0)) t0 = tr[i];
-                            for (int w = 0; w < rp.nwaves; ++w)
-                                for (int it = 0; it < kRsTraceIters; ++it) {
-                                    const long long* q = &tr[((size_t)w * kRsTraceIters + it) * kRsTraceStamps];
-                                    if (!q[0]) continue;
-                                    std::fprintf(stderr, "[rs-trace] %s w%02d it%02d", w < rp.ncompute ? "C" : "L", w, it);
-                                    for (int k = 0; k < kRsTraceStamps; ++k)
-                                        std::fprintf(stderr, " %lld", q[k] ? q[k] - t0 : -1);
-                                    std::fprintf(stderr, "\n");
-                                }
-                        }
-                    } else if (S.rows) {
-                        RsRows rr = S.rr;
-                        rr.in_pitch = in_pitch;
-                        rr.out_pitch = ob.pitch;
-                        if (std::getenv("SIGOPS_DEBUG_PLAN"))
-                            std::fprintf(stderr, "[sigops] k_resample_rows: ct=%d pb=%d tile_len=%d pitch=%d kw=%d ngroups=%d L=%lld M=%lld taps=%d\n", rr.ct, rr.pb,
-                                         rr.tile_len, rr.pitch, rr.kw, rr.ngroups, (long long)rr.L, (long long)rr.M, rr.taps);
-                        launch_resample_rows(inp, ob.d, (const double*)P->bufs[S.tab_buf].d,
-                                             (const int*)P->bufs[S.jend_buf].d, (const double*)P->bufs[S.mtab_buf].d,
-                                             (const int*)P->bufs[S.mjend_buf].d, rr, N.dtype, st);
-                    } else if (S.tiled) {
-                        RsTiled rt = S.rt;
-                        rt.g.in_pitch = in_pitch;
-                        rt.g.out_pitch = ob.pitch;
-                        bool done = false;
-                        if (S.arbk) {
-                            RsArb ra = S.ra;
-                            ra.g.in_pitch = in_pitch;
-                            ra.g.out_pitch = ob.pitch;
-                            ra.err = kernel_error_word(P);
-                            done = launch_resample_arb(inp, ob.d, (const double*)P->bufs[S.pfbt_buf].d,
-                                                       (const double*)P->bufs[S.dpfbt_buf].d, ra, st) == 0;
-                        }
-                        if (done) {
-                        } else if (rt.pair)
-                            launch_resample_tiled2(inp, ob.d, (const double*)P->bufs[S.pfbt_buf].d,
-                                                  (const double*)P->bufs[S.dpfbt_buf].d, rt, st);
-                        else
-                            launch_resample_tiled(inp, ob.d, (const double*)P->bufs[S.pfbt_buf].d,
-                                                  (const double*)P->bufs[S.dpfbt_buf].d, rt, st);
-                    } else
-                        launch_resample(inp, ob.d, (const double*)P->bufs[S.pfb_buf].d,
-                                        (const double*)P->bufs[S.dpfb_buf].d, g, st);
-                    s.launches = 1;
-                    launches++;
-                    if (S.fix_buf >= 0) {  // the outputs DSP.jl's phase accumulator places differently
-                        RsFixArgs fa{};
-                        fa.fix = (const RsFix*)P->bufs[S.fix_buf].d;
-                        fa.nfix = (int64_t)S.fix_host.size();
-                        fa.pfb = (const double*)P->bufs[S.pfb_buf].d;
-                        fa.dpfb = (const double*)P->bufs[S.dpfb_buf].d;
-                        fa.n_in = g.n_in;
-                        fa.taps = g.taps;
-                        fa.nch = N.nch;
-                        fa.stage_dtype = N.dtype;
-                        fa.out_dtype = (s.idx == P->alias_stage && P->alias_narrow) ? SO_F32 : N.dtype;
-                        if (S.periodic) {
-                            fa.car = (const DCarrier*)P->bufs[S.car_buf].d;
-                            fa.ncar = (int)S.carriers.size();
-                            fa.ops = P->d_ops;
-                            fa.leaves = P->d_leaves;
-                        } else {
-                            fa.x = inp;
-                            fa.in_pitch = in_pitch;
-                            fa.in_dtype = N.dtype;
-                        }
-                        fa.y = ob.d;
-                        fa.out_pitch = ob.pitch;
-                        launch_resample_fix(fa, st);
-                        s.launches++;
-                        launches++;
-                    }
-                } else {
-                    RmsPatch patch{};
-                    for (int li : S.rms_leaves) patch.dst[patch.n++] = &P->d_leaves[li].v0;
-                    launch_rms(S.norm_direct ? (const void*)inp : ob.d, N.dtype, S.need, N.nch, S.norm_direct ? in_pitch : ob.pitch,
-                               (double*)P->bufs[S.partial_buf].d, S.nparts, (double*)P->bufs[S.rms_buf].d, st, patch);
-                    s.launches = 2;
-                    launches += 2;
+            int nl = 0;
+            switch (s.kind) {
+            case 0: nl = run_pointwise(P, s, outp, st); break;
+            case 2: nl = run_sos_batch(P, s, outp, st); break;
+            case 3: nl = run_rsos_batch(P, s, outp, st); break;
+            default:
+                switch (P->stages[s.idx].kind) {
+                case ST_SAMPLEAT: nl = run_sample_at(P, s, outp, st); break;
+                case ST_COMB: nl = run_comb(P, s, outp, st); break;
+                case ST_CUMSUM: nl = run_cumsum(P, s, outp, st); break;
+                case ST_SOS: nl = run_sos(P, s, outp, st); break;
+                case ST_RESAMPLE: nl = run_resample(P, s, outp, st); break;
+                default: nl = run_norm(P, s, outp, st); break;
                 }
             }
+            s.launches = nl;
+            launches += nl;
             if (P->profiling) HIPCHECK(hipEventRecord(P->events[ev0 + 2 * si + 1], st));
             if (lanes && (P->step_signals[si] || (ln != 0 && si + 1 == P->steps.size())))
                 HIPCHECK(hipEventRecord(P->step_done[si], st));

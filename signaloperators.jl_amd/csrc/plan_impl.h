@@ -146,6 +146,11 @@ struct Stage {
     int bad_buf = -1;    // first non-finite chunk per channel (SosGeom::bad)
     std::vector<std::vector<double>> xs_mats_host;  // per group: [M][M^kXsBlock]
     std::vector<std::vector<double>> mpow_host;  // per group
+    size_t mpow_stride() const {  // doubles between the groups' tables in mpow_buf: the longest group's
+        size_t n = 0;
+        for (auto& v : mpow_host) n = std::max(n, v.size());
+        return n;
+    }
     // single-pass kernel (k_sos_onepass)
     bool onepass = false;
     SosOne so1{};
