@@ -76,7 +76,7 @@ static AccKey acc_key(const RsGeom& g, const double* h, int hlen) {
 // fix-up list is generated, the cascade's sensitivity probes.  Part of the key (and so of the file name and of the
 // header that is compared byte for byte): a build that changes any of them bumps it, and the files of older builds are
 // simply never looked at again.
-constexpr int32_t kAccAlgoVersion = 6;
+constexpr int32_t kAccAlgoVersion = 7;  // (7: the chunked-form probe sees state-matrix powers rounded once, stages.cpp matpow)
 
 void replay_phase_accumulator(const RsGeom& g, const double* h, int hlen, int64_t need, bool bake,
                                      std::vector<uint8_t>& prev, std::vector<RsFix>& fix, int64_t from) {

@@ -12,15 +12,30 @@ static int env_int(const char* name, int dflt) {  // tuning knobs
 
 // ---------------------------------------------------------------------------
 // small dense matrices for the SOS state propagation
-Mat matmul(const Mat& a, const Mat& b, int D) {
-    Mat c((size_t)D * D, 0.0);
+// Products are accumulated in the host's 80-bit long double and rounded once per entry, and a power keeps its
+// intermediate squares in long double: the DF2T state matrix of a cascade with clustered poles (a third-order
+// high-pass at 20 Hz: three poles within 0.003 of z = 1) has entries of +-190 in A^512 that cancel in every product.
+// Squared in Float64, M = A^L was wrong by ~1e-12 of what it carries from chunk to chunk, and the chunked forms were
+// 3e-11 ... 6e-11 away from the oracle at 40 ... 50 chunks where the sequential recurrence, one chunk and k_rsos are
+// 7e-13 (tests/test_gpu_forms.py: two rungs of one case 1e-11); with M rounded once they are 6e-13 ... 1e-12 too.
+using LMat = std::vector<long double>;
+static LMat lmatmul(const LMat& a, const LMat& b, int D) {
+    LMat c((size_t)D * D, 0.0L);
     for (int i = 0; i < D; ++i)
         for (int k = 0; k < D; ++k) {
-            double v = a[(size_t)i * D + k];
-            if (v == 0.0) continue;
+            long double v = a[(size_t)i * D + k];
+            if (v == 0.0L) continue;
             for (int j = 0; j < D; ++j) c[(size_t)i * D + j] += v * b[(size_t)k * D + j];
         }
     return c;
+}
+static Mat rounded(const LMat& a) {
+    Mat r(a.size());
+    for (size_t i = 0; i < a.size(); ++i) r[i] = (double)a[i];
+    return r;
+}
+Mat matmul(const Mat& a, const Mat& b, int D) {
+    return rounded(lmatmul(LMat(a.begin(), a.end()), LMat(b.begin(), b.end()), D));
 }
 double maxabs(const Mat& a) {
     double m = 0;
@@ -54,13 +69,14 @@ Mat sos_state_matrix(const SosCoefs& cf) {
     return A;
 }
 Mat matpow(Mat A, int64_t e, int D) {
-    Mat R = ident(D);
+    const Mat I = ident(D);
+    LMat R(I.begin(), I.end()), B(A.begin(), A.end());
     while (e > 0) {
-        if (e & 1) R = matmul(R, A, D);
+        if (e & 1) R = lmatmul(R, B, D);
         e >>= 1;
-        if (e) A = matmul(A, A, D);
+        if (e) B = lmatmul(B, B, D);
     }
-    return R;
+    return rounded(R);
 }
 
 
@@ -584,7 +600,7 @@ void Plan::process_stage(int sid) {
         // (32-row tiles first; 16-row tiles -- k_resample_periodic's Q = 1 -- where two 32-row slots do not fit LDS or the
         //  window needs more k-steps than a 32-row instantiation has: long periods, e.g. 44.1 -> 16 kHz)
         for (int rows_try : {32, 16}) {
-        if (stages[sid].periodic || std::getenv(rows_try == 16 ? "SIGOPS_RS_NOQ1" : "SIGOPS_RS_NOPERIODIC_")) continue;
+        if (stages[sid].periodic || std::getenv(rows_try == 16 ? "SIGOPS_RS_NOQ1" : "SIGOPS_RS_NO32ROWS")) continue;
         if ((!g.arbitrary || g.exact) && need >= 2048) {
             constexpr int RM = 16;  // outputs per group = N of the 16x16x4 MFMA tile
             const int64_t Lb = g.L, Mb = g.M;
