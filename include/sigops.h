@@ -84,7 +84,8 @@ typedef enum so_kind {
     SO_NODE_NORMPOWER = 11,/* NormedSignal                   src/filters.jl:266-314        */
     SO_NODE_SAMPLEAT = 12,/* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
     SO_NODE_COMB = 13,    /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
-    SO_NODE_CUMSUM = 14   /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
+    SO_NODE_CUMSUM = 14,  /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
+    SO_NODE_MOVING = 15   /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -280,6 +281,15 @@ typedef enum so_rskind {
  *            The node has x's length, frame rate and channels.  Integrate(x) is a MAP that multiplies the node by the
  *            Float64 constant 1 / framerate.  Not exactly one child is SO_ERR_INVALID; an infinite child
  *            SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
+ *  MOVING    child 0 = x (Float32 / Float64, any length, infinite too)   l0 = back >= 0, l1 = ahead >= 0, the frames of
+ *            the window before and after frame n   i0 = 0 maximum, 1 minimum.
+ *            Per channel y[n] = the greatest (least) of x[k] over max(0, n - l0) <= k <= min(N - 1, n + l1): the window
+ *            is clipped to the signal, never padded.  The order is -Inf < ... < -0.0 < +0.0 < ... < +Inf; a NaN anywhere in
+ *            the clipped window makes y[n] NaN (payload unspecified), otherwise y[n] is a bit copy of the winning sample.
+ *            Nothing is rounded, so every decomposition gives the same bits ("Moving extrema";
+ *            tests/moving_ref.py is the definition).  The node has x's length, frame rate, channels AND sample type.
+ *            MovingMax(x, w, ahead=a): l0 = w - 1 - a, l1 = a, i0 = 0; MovingMin: i0 = 1.  Not exactly one child, l0 < 0,
+ *            l1 < 0 or i0 outside {0, 1} is SO_ERR_INVALID; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

@@ -99,6 +99,7 @@ static const char* stage_step_name(const Stage& S) {
     case ST_SAMPLEAT: return "k_sample_at";
     case ST_COMB: return "k_comb";
     case ST_CUMSUM: return "k_cumsum";
+    case ST_MOVING: return "k_moving";
     default: return "k_sumsq";
     }
 }
@@ -130,6 +131,8 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return S.need * (int64_t)N.nch * (kid_esz(0) + 8);
     case ST_CUMSUM:  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
         return S.need * (int64_t)N.nch * (2 * kid_esz(0) + 8);
+    case ST_MOVING:  // the frames read where x lies (the long form's second and third reads and the tile halos left out), one sample of x's type written
+        return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
     default: return (S.need - S.base) * N.nch * esz;
     }
 }
@@ -515,6 +518,7 @@ static View stage_in(Plan* P, const Stage& S, int nch, int dtype) {
 // has the node's type (try_window_alias takes stages of the result's type only).
 // SampleAt, Comb and Cumsum, whose kernels store Float64 only, get 8 bytes for both: their nodes are Float64 (build_nodes),
 // and plan_create lets only a periodic resampler or a filter narrow, so alias_narrow is false where one of them is aliased.
+// Moving stores its node's type, Float32 or Float64, and is aliased only to a result of that type.
 // A member of an RsBatch is never the aliased stage (fuse_plain_sos skips it): k_rsos_batch's members write windows or buffers.
 static View stage_out(Plan* P, int sid, void* outp) {
     const Stage& S = P->stages[sid];
@@ -818,6 +822,31 @@ static int run_cumsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
     const int nl = launch_cumsum(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
     if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Cumsum: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
+    return nl;
+}
+
+static int run_moving(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const View in = stage_in(P, S, N.nch, N.dtype), out = stage_out(P, s.idx, outp);
+    MovingArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.n_in = S.in_frames;
+    a.y = out.d;
+    a.ycs = out.pitch;
+    a.n_out = S.need - S.base;
+    a.off = S.base - S.in_base;
+    a.back = N.nd.l0;
+    a.ahead = N.nd.l1;
+    a.tab = S.aux_buf >= 0 ? P->bufs[S.aux_buf].d : nullptr;
+    a.nch = N.nch;
+    a.f32 = N.dtype == SO_F32;
+    a.is_min = N.nd.i0;
+    const int nl = launch_moving(a, st);
+    // (one workgroup per tile of kMovTile frames in grid.x, the channels in grid.y)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Moving: more than 65535 channels, or 2^31 tiles of 2048 frames and more, are not lowered");
     return nl;
 }
 
@@ -1140,6 +1169,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 case ST_SAMPLEAT: nl = run_sample_at(P, s, outp, st); break;
                 case ST_COMB: nl = run_comb(P, s, outp, st); break;
                 case ST_CUMSUM: nl = run_cumsum(P, s, outp, st); break;
+                case ST_MOVING: nl = run_moving(P, s, outp, st); break;
                 case ST_SOS: nl = run_sos(P, s, outp, st); break;
                 case ST_RESAMPLE: nl = run_resample(P, s, outp, st); break;
                 default: nl = run_norm(P, s, outp, st); break;

@@ -141,4 +141,40 @@ struct CumsumArgs {
 // the chunk totals a channel of n frames needs: one for every chunk that has a chunk behind it
 constexpr int64_t cumsum_totals(int64_t n) { return n <= kCumsumChunk ? 0 : (n - 1) / kCumsumChunk; }
 int launch_cumsum(const CumsumArgs& a, hipStream_t st);
+// MovingMax / MovingMin (k_moving.hip): output j in [0, n_out) of a channel is the greatest (least) of the input frames
+// [j + off - back, j + off + ahead] clipped to [0, n_in), under the order -Inf < .. < -0.0 < +0.0 < .. < +Inf, NaN if any of
+// them is NaN; the result has the input's type and is a bit copy of that sample.  Compared on a monotone integer key, so any
+// split of the work gives the same bits (DESIGN.md "Moving extrema").  A window of at most kMovHalo + 1 frames is one
+// launch (k_moving_short: tile + halo in LDS, a suffix and a prefix scan over power-of-two segments); a longer one is 2 + levels launches
+// (k_moving_blockmax: the maximum of every aligned block of kMovTile input frames; k_moving_level: a sparse table over
+// them; k_moving_long: in-block suffix, two table look-ups, in-block prefix).  No workgroup waits for another, no atomics.
+// Strides in elements.  Returns the number of launches, -1 when the shape cannot be launched.
+constexpr int kMovTile = 2048;  // T: output frames of a workgroup; input frames of a block of the long form (a power of two)
+constexpr int kMovHalo = 2048;  // H: the short form takes W - 1 <= H (H >= T - 1: a longer window never lies inside one block)
+struct MovingArgs {
+    const void* x;  // input frame i, channel c at x[i * xfs + c * xcs], i in [0, n_in)
+    int64_t xfs, xcs, n_in;
+    void* y;        // y[j + c * ycs], j in [0, n_out), of the input's type
+    int64_t ycs, n_out;
+    int64_t off;    // the input frame output 0 is centred on (0 <= off, off + n_out <= n_in)
+    int64_t back, ahead;
+    void* tab;      // long form: [levels + 1][nch][nblocks] keys of 8 bytes (moving_scratch); unused by the short form
+    int32_t nch, f32, is_min;
+};
+// the long form's table: its levels above the block maxima, and its entries (of 8 bytes) a channel; 0 for the short form
+constexpr int64_t moving_clamp(int64_t v, int64_t n_in) { return v < n_in ? v : n_in; }
+constexpr bool moving_is_long(int64_t n_in, int64_t back, int64_t ahead) { return moving_clamp(back, n_in) + moving_clamp(ahead, n_in) > kMovHalo; }
+constexpr int64_t moving_blocks(int64_t n_in) { return (n_in + kMovTile - 1) / kMovTile; }
+constexpr int moving_levels(int64_t n_in, int64_t back, int64_t ahead) {
+    // a window holds at most (W - 1) / T whole blocks between the two it starts and ends in
+    int64_t mid = (moving_clamp(back, n_in) + moving_clamp(ahead, n_in)) / kMovTile;
+    if (mid > moving_blocks(n_in)) mid = moving_blocks(n_in);
+    int l = 0;
+    while (((int64_t)2 << l) <= mid) ++l;
+    return l;
+}
+constexpr int64_t moving_scratch(int64_t n_in, int64_t back, int64_t ahead) {
+    return moving_is_long(n_in, back, ahead) ? (int64_t)(moving_levels(n_in, back, ahead) + 1) * moving_blocks(n_in) : 0;
+}
+int launch_moving(const MovingArgs& a, hipStream_t st);
 }  // namespace so

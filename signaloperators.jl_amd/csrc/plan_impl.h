@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -119,7 +119,7 @@ struct Stage {
     bool norm_direct = false; // Normpower of a plain array leaf: the rms is taken over the array where it lies, readers divide its loads
     bool under_norm = false;  // a Normpower consumes this stage (directly or through further stages)
     int64_t norm_df = 0;      // ... the largest frame offset it is read at on such a path (0: every Normpower's region starts at this stage's first frame)
-    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64
+    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys
     int64_t win_off = -1;  // >= 0: the stage writes the RESULT's frames [win_off, win_off + need) itself (window aliasing)
     // input source (after processing): either a materialised buffer or a direct view
     const void* in_ptr = nullptr;  // direct device pointer (nullptr -> in_buf)
@@ -474,6 +474,7 @@ struct Plan {
     void check_frames(int ni, int64_t upto);
     void process_stage(int sid);
     void process_sample_at(int sid);
+    void process_moving(int sid);
     void process_comb(int sid);  // (Comb and Cumsum: the stages that compute [0, need) from one plain input)
     bool plain_read(const std::vector<Piece>& ps, int dtype, bool unit_stride) const;
     void stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype);

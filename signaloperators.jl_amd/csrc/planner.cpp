@@ -290,6 +290,19 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = SO_F64;
             break;
         }
+        case SO_NODE_MOVING: {  // sliding-window extrema over [n - l0, n + l1] (no reference counterpart; DESIGN.md "Moving extrema")
+            const std::string where = "node " + std::to_string(i) + ": Moving ";
+            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            if (nd.l0 < 0 || nd.l1 < 0)
+                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is a maximum (0) or a minimum (1), not " + std::to_string(nd.i0));
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
+            N.nch = x.nch;
+            N.dtype = x.dtype;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -890,6 +903,30 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             return out;
         }
         const int sid = stage_for(ni, N.nd.kind == SO_NODE_CUMSUM ? ST_CUMSUM : ST_COMB);
+        use_stage(stages[sid], r, m);
+        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
+        Expr e;
+        e.op = E_LOAD;
+        e.dtype = N.dtype;
+        e.leaf = mk_leafmap(m);
+        e.leaf.fstride = 1;
+        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
+        e.leaf.dtype = N.dtype;
+        e.leaf.buf = stages[sid].out_buf;
+        e.mono = (m.sc == 0);
+        out.push_back({r, add_expr(e)});
+        return out;
+    }
+    case SO_NODE_MOVING: {
+        // a stage: the frames anybody reads, computed from those frames of the child plus `back` before and `ahead` after;
+        // the result is a plain buffer for whoever consumes it (process_moving, stages.cpp)
+        if (dry) {
+            const int64_t hi = m.sf ? r.b + m.df : m.df + 1;
+            check_frames(N.kids[0], hi < BIG - N.nd.l1 ? hi + N.nd.l1 : BIG);
+            out.push_back({r, mk_const(0.0, N.dtype)});
+            return out;
+        }
+        const int sid = stage_for(ni, ST_MOVING);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

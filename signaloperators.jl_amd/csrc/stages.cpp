@@ -468,8 +468,41 @@ void Plan::process_comb(int sid) {
                      (long long)(cumsum ? cumsum_totals(need) : nodes[ni].nd.l0), (long long)need, nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
 }
 
+// MovingMax / MovingMin: the dependence is local, so the stage computes the frames [base, need) anybody reads from the
+// child's frames [max(0, base - back), min(len, need + ahead)), taken like SampleAt's table (stage_input): in_base is the
+// child frame the input starts at.  The long form owns its block maxima and table besides, every entry written by the
+// execute that reads it (k_moving.hip), so nothing clears them.
+void Plan::process_moving(int sid) {
+    const int ni = stages[sid].node;
+    const int xk = nodes[ni].kids[0];
+    const int nch = nodes[ni].nch;
+    const int64_t need = stages[sid].need, back = nodes[ni].nd.l0, ahead = nodes[ni].nd.l1;
+    stages[sid].processed = true;
+    if (need <= 0) return;
+    const int64_t base = stages[sid].lo < need ? stages[sid].lo : 0;
+    const int64_t c0 = base > back ? base - back : 0;
+    int64_t c1 = ahead < BIG - need ? need + ahead : BIG;
+    if (!isinf_(nodes[xk].len)) c1 = std::min(c1, nodes[xk].len.n);
+    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": Moving looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
+    stages[sid].base = base;
+    stages[sid].in_base = c0;
+    bufs[stages[sid].out_buf].frame0 = base;
+    if (c0 > 0) check_frames(xk, c0);
+    stage_input(sid, lower(xk, Rect{0, c1 - c0, 0, nch}, Map{1, c0, 1, 0}), c1 - c0, nch, nodes[xk].dtype);
+    const int64_t entries = moving_scratch(c1 - c0, back, ahead);
+    if (entries > 0) {
+        const int b = raw_buf((size_t)entries * (size_t)nch * 8);
+        stages[sid].aux_buf = b;
+    }
+    if (std::getenv("SIGOPS_DEBUG_PLAN"))
+        std::fprintf(stderr, "[sigops] Moving stage %d: %s over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, %s form, x %s\n", sid,
+                     nodes[ni].nd.i0 ? "min" : "max", (long long)back, (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
+                     entries > 0 ? "long" : "short", stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+}
+
 void Plan::process_stage(int sid) {
     // NOTE: `stages` may grow while lowering the child; re-take references after.
+    if (stages[sid].kind == ST_MOVING) return process_moving(sid);
     if (stages[sid].kind == ST_SAMPLEAT) return process_sample_at(sid);
     if (stages[sid].kind == ST_COMB || stages[sid].kind == ST_CUMSUM) return process_comb(sid);
     int ni = stages[sid].node;

@@ -434,6 +434,9 @@ def _streamable(x):
     if isinstance(x, S.CumsumSignal):
         S.error("BlockStream: Cumsum / Integrate would have to carry its running sum (and its place in the summation "
                 "tree) from one push to the next, and that is not built; not streamable")
+    if isinstance(x, S.MovingSignal):
+        S.error("BlockStream: MovingMax / MovingMin would have to keep the `back` input frames of its window from one push "
+                "to the next and hold `ahead` output frames back, and that is not built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -260,6 +260,9 @@ def _demand(x, n, out, skip=0):
     elif isinstance(x, (S.CombSignal, S.CumsumSignal)):
         # the recurrence (the sum) starts at frame 0: the frames before a window are computed too
         _demand(x.signal, capped(x.signal, n), out, 0)
+    elif isinstance(x, S.MovingSignal):
+        # the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come along
+        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -551,6 +554,11 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_COMB)
             r.update(l0=s.delay, d0=s.b0, d1=s.bD, d2=s.a, children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.MovingSignal):
+            c = rec(s.signal)
+            r = common(s, K.NODE_MOVING)
+            r.update(l0=s.back, l1=s.ahead, i0=1 if s.is_min else 0, children=(c,))
             idx = lw.add(**r)
         elif isinstance(s, S.CumsumSignal):
             c = rec(s.signal)

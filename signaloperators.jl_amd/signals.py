@@ -580,6 +580,30 @@ class CumsumSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class MovingSignal(AbstractSignal):
+    """`MovingMax(x, w)` / `MovingMin(x, w)`: per channel the greatest (least) sample of `x` over the frames
+    `[n - back, n + ahead]`, clipped to the signal (no reference counterpart; include/sigops.h SO_NODE_MOVING, DESIGN.md
+    "Moving extrema").  It has the length, frame rate, channels and sample type of `x`."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x, back, ahead, is_min):
+        self.signal = x
+        self.children = (x,)
+        self.back = int(back)
+        self.ahead = int(ahead)
+        self.is_min = bool(is_min)
+        self.fs = x.fs
+        self.nch = x.nch
+        self.dtype = x.dtype
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -953,6 +977,10 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return CumsumSignal(ToFramerate(x.signal, fs, bs))
+    if isinstance(x, MovingSignal):  # Comb's two rules: the window is counted in frames, whatever rate they have
+        if known:
+            return _resample(x, fs, bs)
+        return MovingSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.is_min)
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1240,6 +1268,75 @@ def _Integrate(x):
 Integrate = Curried(_Integrate)
 Integrate.__doc__ = """`Integrate(x)`, piped `x | Integrate`: the integral of `x` over time, `Cumsum(x)` times the Float64 constant
 `1.0 / framerate(x)` (one more rounding a sample, through the map path)."""
+
+
+# --------------------------------------------------------------------------
+# MovingMax / MovingMin: sliding-window extrema (no reference counterpart)
+def _moving_frames(what, name, x, v):
+    """`_comb_delay`'s rules: a whole number of frames, a `frames` quantity, or a time converted with the rate of x"""
+    if isinstance(v, Quantity):
+        if U.is_time(v):
+            if x.fs is None:
+                error(f"{what}: {name} given as a time needs the frame rate of x")
+            return U.inframes_int(v, x.fs)
+        if not U.is_frames(v):
+            error(f"{what}: {name} {v} is neither a time nor a number of frames")
+        v = v.value
+    if not _real_number(v) or not math.isfinite(v) or v != math.floor(v):
+        error(f"{what}: {name} must be a whole number of frames, not {v!r}")
+    return int(v)
+
+
+def _Moving(what, is_min, x, w, ahead, center):
+    x = _assignal(x)
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    W = _moving_frames(what, "the window w", x, w)
+    if W < 1:
+        error(f"{what}: the window must be at least one frame ({W} given)")
+    if center:
+        if ahead is not None:
+            error(f"{what}: give `center=True` or `ahead`, not both")
+        A = (W - 1) // 2
+    else:
+        A = 0 if ahead is None else _moving_frames(what, "`ahead`", x, ahead)
+    if A < 0 or A > W - 1:
+        error(f"{what}: `ahead` must lie in [0, w - 1] = [0, {W - 1}] frames ({A} given): it is the part of the window after frame n")
+    return MovingSignal(x, W - 1 - A, A, is_min)
+
+
+def _moving_ctor(what, is_min):
+    def ctor(*args, ahead=None, center=False):
+        if len(args) == 1:
+            w = args[0]
+            return Curried(lambda x: _Moving(what, is_min, x, w, ahead, center))
+        if len(args) != 2:
+            error(f"{what}(x, w) expected")
+        return _Moving(what, is_min, args[0], args[1], ahead, center)
+
+    ctor.__name__ = ctor.__qualname__ = what
+    return ctor
+
+
+MovingMax = _moving_ctor("MovingMax", False)
+MovingMax.__doc__ = """`MovingMax(x, w, *, ahead=0, center=False)`, curried `x | MovingMax(w, ahead=...)`: the sliding-window maximum.  With
+`back = w - 1 - ahead`, frame n of a channel is the greatest of `x[k]` over `max(0, n - back) <= k <= min(N - 1, n + ahead)`:
+the window is clipped to the signal, never padded, and the result has the length, rate, channels and sample type of `x`
+(Float32 stays Float32: nothing is rounded).  `w` is the window length, at least one frame: a whole number of frames (a
+number or a `frames` quantity) or a time, converted with the rate of `x`; `ahead`, in the same units, is how much of the
+window lies after frame n (`0 <= ahead <= w - 1`); `center=True` is `ahead = (w - 1) // 2`.  The default is the causal
+window `[n - w + 1, n]`.  The samples are ordered `-Inf < ... < -0.0 < +0.0 < ... < +Inf`, so `+0.0` beats `-0.0` and a
+window of only `-0.0` gives `-0.0`; the result is a bit copy of the greatest sample.  A NaN anywhere in the window makes
+the frame NaN (its payload is unspecified).  Maximum and minimum round nothing and are associative, so every way of
+splitting the work gives the same bits: windows, `stream` blocks and the whole sink agree bit for bit where `x` does.
+The dependence is local: a window or a `stream` block computes its own frames from its own range of `x` plus `back`
+frames before and `ahead` after, so `stream` over the node is linear and an `x` of infinite length is accepted.
+`BlockStream` and multi-GPU shards refuse the node."""
+MovingMin = _moving_ctor("MovingMin", True)
+MovingMin.__doc__ = """`MovingMin(x, w, *, ahead=0, center=False)`, curried `x | MovingMin(w, ahead=...)`: the sliding-window minimum, the
+mirror image of `MovingMax`: the least sample of the clipped window under the same order, so `-0.0` beats `+0.0`, NaN
+propagates, and the result equals `-MovingMax(-x)` bit for bit.  Window, units, result type, `stream`, `BlockStream` and
+shards as for `MovingMax`."""
 
 
 # --------------------------------------------------------------------------

@@ -50,6 +50,14 @@ cases = {
     # per-frame increment (1.37 frames +- 20 %, a different trajectory per channel), `SampleAt` over `Cumsum`
     "cumsum": lambda: so.Cumsum(X),
     "vco": lambda: so.SampleAt(so.Signal(x[:2048], fs), so.Cumsum(so.Signal((1.37 + 0.2 * x.t().clamp(-1.0, 1.0).to(torch.float64)).t(), fs)), wrap=True),
+    # `MovingMax(x, w)` / `MovingMin(x, w)` (include/sigops.h SO_NODE_MOVING, csrc/k_moving.hip): a window of 480 frames is the
+    # one-launch form (a tile and its halo in LDS: 1 + 479 / 2048 reads and one write per sample), causal and centred; 48000
+    # frames is the long form (block maxima, a sparse table, two blocks recomputed per tile: about three reads and one write);
+    # the Float32 row moves half the bytes; the yardstick is the `copy (Until)` row above
+    "movingmax 480": lambda: so.MovingMax(X, 480),
+    "movingmax 480 ahead": lambda: so.MovingMax(X, 480, center=True),
+    "movingmax 48000": lambda: so.MovingMax(X, 48000),
+    "movingmin 480 f32": lambda: so.MovingMin(so.Signal(x.t().to(torch.float32).t(), fs), 480),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
     "Amplify(sin)": lambda: X | so.Amplify(tone) | so.Until(n * so.frames),
     "Mix(x, y)": lambda: so.Mix(X, Y),
@@ -129,7 +137,7 @@ for name, mk in cases.items():
     try:
         tree = mk()
         nout, co = so.nframes(tree), so.nchannels(tree)
-        odt = np.float32 if ("Float32" in name or NDT == np.float32) else np.float64
+        odt = np.float32 if ("Float32" in name or name.endswith(" f32") or NDT == np.float32) else np.float64
         tdt = torch.float32 if odt == np.float32 else torch.float64
         out = torch.empty((co, nout), dtype=tdt, device="cuda").t()
         saved = {k: os.environ.get(k) for k in case_env.get(name, {})}
