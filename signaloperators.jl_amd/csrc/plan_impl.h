@@ -112,7 +112,7 @@ struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
     int64_t lo = (int64_t)1 << 62;  // first frame anybody reads
-    int64_t base = 0;  // first frame the stage computes (warm start, see process_stage): its buffer holds [base, need)
+    int64_t base = 0;  // first frame the stage computes (warm start, see rs_warm_start / sos_warm_start in stages.cpp): its buffer holds [base, need)
     int64_t in_base = 0;  // first frame of the child the stage consumes
     bool processed = false;
     bool norm_alias = false;  // Normpower whose `vals` is its child stage's output buffer (no copy)
@@ -216,6 +216,12 @@ struct Stage {
     int partial_buf = -1, rms_buf = -1;
     std::vector<int> rms_leaves;  // scalar leaves that read rms_buf: the sum-of-squares launch writes the value into their v0 too (RmsPatch)
     int nparts = 0;
+};
+
+// What a stage computes and consumes once its warm start is decided: the node's frames [base, base + need_local) from the
+// child's frames [in_base, in_base + in_frames).  Stage::need stays the node's own count, [0, need).
+struct StageSpan {
+    int64_t base = 0, in_base = 0, need_local = 0, in_frames = 0;
 };
 
 struct PwStep {
@@ -472,12 +478,38 @@ struct Plan {
     int in_norm = 0;  // > 0: lowering below a Normpower (stages created or used here are marked Stage::under_norm)
     int dry = 0;  // > 0: lower() only looks for the errors evaluating those frames raises (no stages, no buffers)
     void check_frames(int ni, int64_t upto);
-    void process_stage(int sid);
+    void process_stage(int sid);  // (stages.cpp: the dispatch to one routine per stage kind)
     void process_sample_at(int sid);
     void process_moving(int sid);
     void process_comb(int sid);  // (Comb and Cumsum: the stages that compute [0, need) from one plain input)
-    bool plain_read(const std::vector<Piece>& ps, int dtype, bool unit_stride) const;
     void stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype);
+    // the resampler: its forms, tried in this order (each returns at once where an earlier one took the stage)
+    void process_resample(int sid);
+    void rs_polyphase_tables(int sid, const RsGeom& g);
+    void plan_rs_periodic(int sid, int64_t need, int rows_try, const std::vector<uint8_t>& wrap);
+    void plan_rs_rows(int sid, int64_t need, const std::vector<uint8_t>& wrap);
+    void plan_rs_tiled(int sid, int64_t need);
+    void plan_rs_arb(int sid, int64_t need, bool pair, double step);
+    void bind_resample_input(int sid, int child, const StageSpan& sp);
+    void size_gain_ring_ga(Stage& S) const;
+    void size_gain_ring(Stage& S, int stage_dtype) const;
+    // the SOS cascade; `Filt(Filt(x))` as one: the innermost child, all sections, the gain product, the skipped filters' block sizes
+    struct Cascade {
+        int child = -1;
+        std::vector<double> sos;  // empty: nothing merged, the node's own sections
+        double gain = 1.0;
+        std::vector<int64_t> bs;
+    };
+    Cascade merged_cascade(int ni) const;
+    void process_sos(int sid);
+    void plan_sos_onepass(int sid, int64_t need, const std::vector<SosCoefs>& groups, bool exact);
+    void bind_sos_input(int sid, const Cascade& m, const StageSpan& sp);
+    void process_norm(int sid);
+    // a stage's input: lowered, read in place, or materialised
+    std::vector<Piece> lower_input(int sid, int child, const StageSpan& sp, bool norm_below);
+    bool direct_source(Stage& S, const std::vector<Piece>& ps, int in_dtype, int nch) const;
+    bool match_sine_source(Stage& S, const std::vector<Piece>& ps, const Node& N, const StageSpan& sp);
+    void materialise_input(int sid, const std::vector<Piece>& ps, int64_t in_frames, int nch, int in_dtype);
     int emit_pointwise(const std::vector<Piece>& ps, int out_buf, int out_dtype);
     // a piece of the fill form: the noise leaf's expression, the constant factor's (or -1), kFillRound* flags
     struct RandnFill { int noise = -1, scale = -1, flags = 0; };
@@ -505,6 +537,7 @@ struct Plan {
     void fuse_state_passes();
     void fuse_resample_sos();
     void fuse_plain_sos();
+    void rsos_fuse_step(const DCarrier& c0, bool two_arrays, RsSos& g) const;  // (both of them: carrier 0's step on the loader's fast path)
     void batch_sos_stages();
     void sos_chunking(int sid, int64_t need, int nch, int dtype, const std::vector<SosCoefs>& groups, bool exact, int64_t target);
     void finalize();

@@ -1,6 +1,28 @@
 // Stage setup: geometry and tables of the stateful stages (resampler variants, SOS IIR, Normpower),
 // carrier fusion of pointwise sources into the periodic resampler, and the optional fusion of the
 // IIR's state pass into the resampler in front of it.
+//
+// Map (routine -- what it decides -- the Stage fields it writes):
+//   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
+//                            process_sample_at, process_comb, process_moving (input: stage_input)
+//   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
+//                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
+//     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
+//     plan_rs_rows             k_resample_rows, scalar and MFMA -- rows, rr, tab / jend (per output), mtab / mjend
+//     plan_rs_tiled            k_resample_tiled(2) -- tiled, rt, pfbt / dpfbt; plan_rs_arb: its persistent form -- arbk, ra
+//     bind_resample_input      direct_source | carriers (build_carriers; size_gain_ring_ga / size_gain_ring: rp.ga, fslots, fpitch,
+//                              ftwo, nslots, nload, arr2) | alt_carriers + materialise_input; default_carrier; car_buf, ctl_buf
+//   process_sos              merged_cascade, sos_section_groups, sos_wants_exact, sos_warm_start (base, in_base),
+//                            plan_sos_onepass (onepass, so1, one_*), sos_chunking (groups, sg, mpow / v / s0 / xscan / bad buffers)
+//     bind_sos_input           direct_source | match_sine_source (src_op, src_fn) | materialise_input; the candidate carrier of fuse_plain_sos
+//   process_norm             nparts, partial_buf; vals = the child stage's buffer, the array in place, or a materialised copy
+//   every bind: lower_input, the reference's block-granular check_frames, in_frames, in_buf / in_array_node / in_offset / in_pitch / pw_step
+//   fuse_resample_sos        eligibility per filter stage behind a resampler stage, then RsosFusion's decisions in order: source_form,
+//                            own_table, trim_table, sole_reader, warmup_and_ranges, worth_it, waves, ring; rewrite_carriers, commit,
+//                            wproj_tables, commit_launch -- on the filter stage rs, rsos_*; on the resampler stage carriers, fused_away
+//   fuse_plain_sos           PlainRsos::fit / commit per filter, alone or as an RsBatch -- rs, rsos_*, rsb
+//   shared: tap, period_positions, group_windows, fill_tap_blocks, aligned_window_start (tap tables); plain_load, leaf_offset (plain
+//   reads); warmup_periods, rsos_ranges, rsos_ring_frames, rsos_fuse_step (both forms of k_rsos); channels_per_group, kRsLdsAvail
 #include "plan_impl.h"
 
 namespace so {
@@ -8,6 +30,99 @@ namespace so {
 static int env_int(const char* name, int dflt) {  // tuning knobs
     const char* ev = std::getenv(name);
     return ev ? std::atoi(ev) : dflt;
+}
+
+// LDS a periodic resampler's tiles, gain arrays and staging rows share beside its control block
+constexpr size_t kRsLdsAvail = 160 * 1024 - sizeof(RsCtl) - 64;
+
+// channels of a tile or sequence group: the largest of {max, ..., 4, 2} that divides nch (max: 8 or 16), else 1
+static int channels_per_group(int nch, int max) {
+    if (max >= 16 && nch % 16 == 0) return 16;
+    for (int c : {8, 4, 2})
+        if (nch % c == 0) return c;
+    return 1;
+}
+
+// ---------------------------------------------------------------------------
+// tap tables of the rational resampler forms (periodic, row-tiled, the fused kernel's own)
+
+// polyphase tap of phase p at age k -- pfb[p][k] = h[p + nphi k] -- and its difference dh = [diff(h); 0] at the same place
+struct Tap {
+    double hv, dv;
+};
+static Tap tap(const double* h, int hlen, int nphi, int p, int64_t age) {
+    const int64_t hi = p + (int64_t)nphi * age;
+    return {hi < hlen ? h[hi] : 0.0, hi + 1 < hlen ? h[hi + 1] - h[hi] : 0.0};
+}
+
+// Position of the outputs r = 0 .. n-1 of a (super-)period as the tap tables see it: newest input j, phase p and the
+// weight alpha of the next phase -- the closed form, or, where `wrap` (per output of ONE period, null or empty: nowhere)
+// says the accumulator's wrap-around tie is the rule, the previous input's last phase with alpha = 1.
+struct PeriodPos {
+    std::vector<int64_t> j;
+    std::vector<int> p;
+    std::vector<double> alpha;
+};
+static PeriodPos period_positions(const RsGeom& g, int64_t n, const std::vector<uint8_t>* wrap) {
+    PeriodPos P{std::vector<int64_t>((size_t)n), std::vector<int>((size_t)n), std::vector<double>((size_t)n)};
+    for (int64_t r = 0; r < n; ++r) {
+        int64_t qi;
+        double alpha = 0.0;
+        if (g.arbitrary) {
+            const int64_t Nn = r * ((int64_t)g.nphi * g.M);
+            qi = g.c0i + Nn / g.L;
+            alpha = (double)(Nn % g.L) / (double)g.L;
+        } else qi = g.c0i + r * g.M;
+        if (wrap && !wrap->empty() && (*wrap)[r % g.L]) {
+            qi -= 1;
+            alpha = 1.0;
+        }
+        P.j[(size_t)r] = qi / g.nphi;
+        P.p[(size_t)r] = (int)(qi % g.nphi);
+        P.alpha[(size_t)r] = alpha;
+    }
+    return P;
+}
+
+// The outputs of a period in groups of 16 (N of the 16x16x4 MFMA tile): every group's newest input, and the most inputs
+// a group's newest inputs span.  A window of kw = 4 ksteps >= taps + maxspan slots ending at jend covers the group.
+struct GroupWindows {
+    std::vector<int> jend;
+    int64_t maxspan = 0;
+};
+template <class J>
+static GroupWindows group_windows(const std::vector<J>& jr, int64_t n) {
+    GroupWindows w;
+    w.jend.resize((size_t)((n + 15) / 16));
+    for (size_t gi = 0; gi < w.jend.size(); ++gi) {
+        const int64_t r0 = 16 * (int64_t)gi, r1 = std::min<int64_t>(n, r0 + 16);
+        w.jend[gi] = (int)jr[(size_t)r1 - 1];
+        w.maxspan = std::max<int64_t>(w.maxspan, jr[(size_t)r1 - 1] - jr[(size_t)r0]);
+    }
+    return w;
+}
+
+// first staged input of a window of kw slots that ends at jend0, rounded down to a multiple of 4 frames: tiles start on a
+// 16-byte boundary (vector loads) whenever their stride is a multiple of 4
+static int aligned_window_start(int jend0, int kw) {
+    const int jlo = jend0 - (kw - 1);
+    return jlo - ((jlo % 4) + 4) % 4;
+}
+
+// The [groups][kw][16] tap operands: slot kk of group gi is input jend[gi] - (kw - 1) + kk, and output r of the group
+// holds there its tap of that age, tap_of(r, age) -- zero where the age is outside [0, taps).
+template <class J, class F>
+static std::vector<double> fill_tap_blocks(const std::vector<J>& jr, int64_t n, const std::vector<int>& jend, int kw, int taps, F tap_of) {
+    std::vector<double> tab(jend.size() * (size_t)kw * 16, 0.0);
+    for (size_t gi = 0; gi < jend.size(); ++gi) {
+        const int64_t r0 = 16 * (int64_t)gi, r1 = std::min<int64_t>(n, r0 + 16);
+        for (int64_t r = r0; r < r1; ++r)
+            for (int kk = 0; kk < kw; ++kk) {
+                const int64_t age = jr[(size_t)r] - ((int64_t)jend[gi] - (kw - 1) + kk);
+                if (age >= 0 && age < taps) tab[(gi * (size_t)kw + kk) * 16 + (size_t)(r - r0)] = tap_of(r, age);
+            }
+    }
+    return tab;
 }
 
 // ---------------------------------------------------------------------------
@@ -230,7 +345,7 @@ static bool ga_fits(const Stage& S, int stage_dtype) {
     const RsPeriodic& rp = S.rp;
     const int gper = (rp.ngroups + rp.ncompute - 1) / std::max(1, rp.ncompute);
     if (rp.kw != 56 || gper != 1 || !(rp.ct == 8 || rp.ct == 4)) return false;
-    const size_t avail = 160 * 1024 - sizeof(RsCtl) - 64;
+    const size_t avail = kRsLdsAvail;
     const size_t pitch4 = (size_t)((rp.tile_len + 31 + 8 + 3) / 4 * 4);
     const size_t tile_bytes = (size_t)rp.ct * pitch4 * 4;
     const size_t fpitch = (size_t)((rp.tile_len + 32 + 1) & ~1);  // (Float32 tiles start up to 31 frames below their first input)
@@ -372,28 +487,36 @@ void Plan::sos_chunking(int sid, int64_t need, int nch, int dtype, const std::ve
     stages[sid].sg = g;
 }
 
-// Is this lowering of a stage's input one plain read -- an array leaf of any strides, or another stage's buffer -- that a
-// kernel can take where it lies?  (`unit_stride`: only with frame stride 1.)  SampleAt's table and positions and Comb's x.
-bool Plan::plain_read(const std::vector<Piece>& ps, int dtype, bool unit_stride) const {
-    if (ps.size() != 1) return false;
-    const Expr& e = exprs[ps[0].e];
-    return e.op == E_LOAD && e.leaf.mode == LM_PLAIN && e.leaf.sf == 1 && e.leaf.sc == 1 && e.leaf.dtype == dtype && e.leaf.df >= 0 &&
-           e.leaf.dc >= 0 && (!unit_stride || e.leaf.fstride == 1) && e.leaf.fstride >= 1 &&
-           (e.leaf.cstride > 0 || (e.leaf.cstride == -1 && e.array_node < 0 && e.leaf.dc == 0) || ps[0].r.c1 - ps[0].r.c0 == 1);
+// Is this expression one plain read of `dtype` -- an array leaf, or another stage's buffer -- that a kernel can take where
+// it lies?  Its three callers accept different sets, on purpose left as they were:
+//   - frame stride: `unit_stride` asks for 1; without it any stride >= 1 passes (stage_input: SampleAt's table, Comb's and
+//     Moving's x read an interleaved array in place).
+//   - a channel stride of -1 (the pitch of a stage buffer): `strict_pitch` takes it only from a buffer read from its first
+//     channel (array_node < 0, dc == 0) -- stage_input and SampleAt's positions.  Without it -1 passes outright, and the
+//     caller turns down a buffer with dc != 0 afterwards (direct_source, after it has written the view; match_sine_source
+//     as part of its test).  A positive channel stride or a single channel passes with any dc either way.
+//   - `nch`, the single-channel escape: the piece's own channel count for stage_input, the stage's for the other two.
+static bool plain_load(const Expr& e, int dtype, int nch, bool unit_stride, bool strict_pitch) {
+    const DLeaf& l = e.leaf;
+    if (e.op != E_LOAD || l.mode != LM_PLAIN || l.sf != 1 || l.sc != 1 || l.dtype != dtype || l.df < 0 || l.dc < 0) return false;
+    if (unit_stride ? l.fstride != 1 : l.fstride < 1) return false;
+    return l.cstride > 0 || (l.cstride == -1 && (!strict_pitch || (e.array_node < 0 && l.dc == 0))) || nch == 1;
 }
+// element offset of a plain array leaf's first element: df frames and dc channels into the array
+static int64_t leaf_offset(const DLeaf& l) { return l.df * l.fstride + l.dc * std::max<int64_t>(l.cstride, 0); }
 
 // The input of stage `sid`, `frames` x `nch` of `dtype`, lowered to `ps`: read where it lies when it is plain, materialised by
 // one pointwise step otherwise (Stage::in_array_node / in_buf / x_fstride / in_pitch / in_offset / pw_step).
 void Plan::stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype) {
     Stage& S = stages[sid];
     S.in_frames = frames;
-    if (plain_read(ps, dtype, false)) {
+    if (ps.size() == 1 && plain_load(exprs[ps[0].e], dtype, ps[0].r.c1 - ps[0].r.c0, false, true)) {
         const Expr& e = exprs[ps[0].e];
         S.in_array_node = e.array_node;
         S.in_buf = e.array_node >= 0 ? -1 : e.leaf.buf;
         S.x_fstride = e.leaf.fstride;
         S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
-        S.in_offset = e.leaf.df * e.leaf.fstride + (e.array_node >= 0 ? e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0) : 0);
+        S.in_offset = e.array_node >= 0 ? leaf_offset(e.leaf) : e.leaf.df * e.leaf.fstride;
         if (e.array_node >= 0) count_array(e.array_node);
         return;
     }
@@ -426,11 +549,11 @@ void Plan::process_sample_at(int sid) {
     {
         const std::vector<Piece> ps = lower(pk, Rect{0, need - base, 0, pch}, Map{1, base, 1, 0});
         Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
-        if (plain_read(ps, SO_F64, true) && exprs[ps[0].e].array_node >= 0) {
+        if (ps.size() == 1 && plain_load(exprs[ps[0].e], SO_F64, ps[0].r.c1 - ps[0].r.c0, true, true) && exprs[ps[0].e].array_node >= 0) {
             const Expr& e = exprs[ps[0].e];
             S.pos_array_node = e.array_node;
             S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
-            S.pos_offset = e.leaf.df + e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0);
+            S.pos_offset = leaf_offset(e.leaf);
             count_array(e.array_node);
         } else {
             const int b = new_buf(need - base, pch, SO_F64);
@@ -500,675 +623,703 @@ void Plan::process_moving(int sid) {
                      entries > 0 ? "long" : "short", stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
 }
 
+// One routine per stage kind.  Each decides the frames its stage computes and consumes (StageSpan), its form and tables,
+// and then binds its input: lower_input, the reference's block-granular check_frames, and the source -- read in place
+// (direct_source), fused into the kernel's loads (carriers, a sine), or materialised by one pointwise step.
+// `stages`, `bufs` and `exprs` may grow while a child is lowered or a pointwise step is emitted: the routines index
+// stages[sid] and re-take a `Stage&` after the last such call.  `nodes` is sized once (build_nodes): a `Node&` stays valid.
 void Plan::process_stage(int sid) {
-    // NOTE: `stages` may grow while lowering the child; re-take references after.
-    if (stages[sid].kind == ST_MOVING) return process_moving(sid);
-    if (stages[sid].kind == ST_SAMPLEAT) return process_sample_at(sid);
-    if (stages[sid].kind == ST_COMB || stages[sid].kind == ST_CUMSUM) return process_comb(sid);
-    int ni = stages[sid].node;
-    Node& N = nodes[ni];
+    switch (stages[sid].kind) {
+    case ST_MOVING: return process_moving(sid);
+    case ST_SAMPLEAT: return process_sample_at(sid);
+    case ST_COMB:
+    case ST_CUMSUM: return process_comb(sid);
+    case ST_RESAMPLE: return process_resample(sid);
+    case ST_SOS: return process_sos(sid);
+    default: return process_norm(sid);
+    }
+}
+
+// `Filt(Filt(x))` in Float64 (a band-pass written as low-pass |> high-pass): ONE cascade of all the sections -- the inner
+// filter's first, the gains multiplied -- as long as it fits one launch group: one run of the filter kernels instead of
+// two, no intermediate signal in HBM (reference src/filters.jl:240-255 filters the inner filter's blocks in place: the
+// same sections in the same order, rounded as one cascade instead of two).  Frames are one to one, so every bound of the
+// stage holds for the innermost child; each skipped filter still pulls whole blocks of ITS child (error parity).
+Plan::Cascade Plan::merged_cascade(int ni) const {
+    const Node& N = nodes[ni];
     const so_node_t& nd = N.nd;
-    int child = N.kids[0];
-    // `Filt(Filt(x))` in Float64 (a band-pass written as low-pass |> high-pass): ONE cascade of all the sections -- the inner
-    // filter's first, the gains multiplied -- as long as it fits one launch group: one run of the filter kernels instead of
-    // two, no intermediate signal in HBM (reference src/filters.jl:240-255 filters the inner filter's blocks in place: the
-    // same sections in the same order, rounded as one cascade instead of two).  Frames are one to one, so every bound below
-    // holds for the innermost child; each skipped filter still pulls whole blocks of ITS child (error parity).
-    std::vector<double> merged_sos;
-    double merged_gain = nd.d0;
-    std::vector<int64_t> merged_bs;
-    if (stages[sid].kind == ST_SOS && N.dtype == SO_F64 && !std::getenv("SIGOPS_SOS_NOMERGE")) {
+    Cascade m;
+    m.child = N.kids[0];
+    m.gain = nd.d0;
+    if (N.dtype == SO_F64 && !std::getenv("SIGOPS_SOS_NOMERGE")) {
         int tot = nd.i0;
-        while (nodes[child].nd.kind == SO_NODE_FILT_SOS && nodes[child].dtype == SO_F64 && nodes[child].nch == N.nch &&
-               nodes[child].fs == N.fs && tot + nodes[child].nd.i0 <= kMaxSec && nodes[child].nd.i0 >= 1) {
-            const so_node_t& cn = nodes[child].nd;
-            if (merged_sos.empty()) merged_sos.assign((const double*)nd.p0, (const double*)nd.p0 + 6 * (size_t)nd.i0);
-            merged_sos.insert(merged_sos.begin(), (const double*)cn.p0, (const double*)cn.p0 + 6 * (size_t)cn.i0);
-            merged_gain *= cn.d0;
-            merged_bs.push_back(std::max(1, cn.i1));
+        while (nodes[m.child].nd.kind == SO_NODE_FILT_SOS && nodes[m.child].dtype == SO_F64 && nodes[m.child].nch == N.nch &&
+               nodes[m.child].fs == N.fs && tot + nodes[m.child].nd.i0 <= kMaxSec && nodes[m.child].nd.i0 >= 1) {
+            const so_node_t& cn = nodes[m.child].nd;
+            if (m.sos.empty()) m.sos.assign((const double*)nd.p0, (const double*)nd.p0 + 6 * (size_t)nd.i0);
+            m.sos.insert(m.sos.begin(), (const double*)cn.p0, (const double*)cn.p0 + 6 * (size_t)cn.i0);
+            m.gain *= cn.d0;
+            m.bs.push_back(std::max(1, cn.i1));
             tot += cn.i0;
-            child = nodes[child].kids[0];
+            m.child = nodes[m.child].kids[0];
         }
     }
-    Node& C = nodes[child];
-    int64_t need = stages[sid].need;
+    return m;
+}
+
+// ---------------------------------------------------------------------------
+// the resampler
+
+// ratio, phases, taps and centre of the node's resampler, for `need` outputs from frame 0
+static RsGeom rs_geometry(const Node& N, double child_fs, int64_t need) {
+    const so_node_t& nd = N.nd;
+    RsGeom g{};
+    g.arbitrary = nd.i0 == SO_RS_ARBITRARY;
+    int hlen = nd.i2;
+    g.nphi = g.arbitrary ? nd.i1 : (int)nd.l0;
+    if (g.nphi < 1) fail(SO_ERR_INVALID, "resampler: bad phase count");
+    g.L = nd.l0;
+    g.M = nd.l1;
+    const bool plain_fir = nd.i0 == SO_RS_FIR;  // Filt(x,h): ratio 1, causal, no delay compensation
+    if (plain_fir) {
+        g.nphi = 1;
+        g.L = g.M = 1;
+    }
+    if (!g.arbitrary && (g.L < 1 || g.M < 1)) fail(SO_ERR_INVALID, "resampler: bad ratio");
+    g.delta = g.arbitrary ? (double)g.nphi / nd.d0 : 0.0;
+    g.c0 = plain_fir ? 0.0 : (double)(hlen - 1) / 2.0;
+    g.c0i = plain_fir ? 0 : (hlen - 1) / 2;
+    g.taps = (hlen + g.nphi - 1) / g.nphi;
+    g.nch = N.nch;
+    g.m0 = 0;
+    g.n_out = need;
+    if (g.arbitrary) rs_detect_exact(g, nd.fs, child_fs, nd.d0);
+    return g;
+}
+
+// Warm start (see the IIR's, sos_warm_start): the resampler is an FIR filter, so outputs from a whole number of periods
+// before the first frame anybody reads on are the same whether the stage starts there or at frame 0, except the first
+// few (their taps reach before the first input staged), which nobody reads either.  `need`: the node's frames [0, need)
+// somebody reads from `lo` on; the span's need_local counts from its base.
+static StageSpan rs_warm_start(RsGeom& g, int64_t lo, int64_t need) {
+    StageSpan sp;
+    sp.need_local = need;
+    if ((!g.arbitrary || g.exact) && lo >= 8192 && lo < need &&
+        !std::getenv("SIGOPS_NO_WARM_START")) {
+        const int64_t margin = (g.taps + 2 + g.M - 1) / g.M + 1;  // periods
+        int64_t k = lo / g.L - margin;
+        k = k / 16 * 16;  // (16 M inputs: the first staged input stays 128-byte aligned)
+        if (k > 0 && k * g.L >= 4096) {
+            sp.base = k * g.L;
+            sp.in_base = k * g.M;
+            sp.need_local = need - sp.base;
+            g.n_out = sp.need_local;
+        }
+    }
+    // ... and a rate without a period (no integer frame rates) has nothing to be aligned with: output m sits at
+    // q_m = c0 + m delta whatever came before it (the accumulator's deviations from that are listed from the
+    // nearest checkpoint of an earlier replay, accumulator.cpp), so the stage starts at the first frame anybody
+    // reads -- g.m0 -- and stages its input from taps + 2 frames before that output's newest input -- g.j0
+    if (g.arbitrary && !g.exact && lo >= 8192 && lo < need && !std::getenv("SIGOPS_NO_WARM_START")) {
+        sp.base = lo / 64 * 64;  // (whole lines for the kernels' stores)
+        const double q = g.c0 + (double)sp.base * g.delta;
+        const int64_t jf = (int64_t)std::floor(q) / g.nphi;
+        sp.in_base = std::max<int64_t>(0, jf - g.taps - 2) / 16 * 16;
+        g.m0 = sp.base;
+        g.j0 = sp.in_base;
+        sp.need_local = need - sp.base;
+        g.n_out = sp.need_local;
+    }
+    return sp;
+}
+
+// input frames the stage consumes from in_base on: up to the newest input of its last output, +1, within the child
+static int64_t rs_input_frames(const RsGeom& g, int64_t need, Len child_len, int64_t in_base) {
+    // newest input of the last needed output
+    int64_t jl;
+    if (g.arbitrary && g.exact) {
+        int64_t Nn = (need - 1) * ((int64_t)g.nphi * g.M);
+        jl = (g.c0i + Nn / g.L) / g.nphi;
+    } else if (g.arbitrary) {
+        double q = g.c0 + (double)(g.m0 + need - 1) * g.delta;
+        jl = (int64_t)std::floor(q) / g.nphi - g.j0;
+    } else jl = (g.c0i + (need - 1) * g.M) / g.L;
+    int64_t nin = jl + 2;  // +1 slack: host rounding of q may differ from the device's at ties
+    if (!isinf_(child_len)) nin = std::min(nin, child_len.n - in_base);
+    return nin;
+}
+
+// polyphase tables: pfb[p][k] = h[p + nphi*k]; dpfb from dh = [diff(h);0]
+void Plan::rs_polyphase_tables(int sid, const RsGeom& g) {
+    const so_node_t& nd = nodes[stages[sid].node].nd;
+    stages[sid].pfb_host.assign((size_t)g.nphi * g.taps, 0.0);
+    stages[sid].dpfb_host.assign((size_t)g.nphi * g.taps, 0.0);
+    for (int p = 0; p < g.nphi; ++p)
+        for (int k = 0; k < g.taps; ++k) {
+            const Tap t = tap((const double*)nd.p0, nd.i2, g.nphi, p, k);
+            stages[sid].pfb_host[(size_t)p * g.taps + k] = t.hv;
+            stages[sid].dpfb_host[(size_t)p * g.taps + k] = t.dv;
+        }
+    stages[sid].pfb_buf = raw_buf(stages[sid].pfb_host.size() * 8);
+    stages[sid].dpfb_buf = raw_buf(stages[sid].dpfb_host.size() * 8);
+}
+
+// The forms are tried fastest first, each under its own conditions: the periodic (SGPR-tap) kernel with 32-row tiles, then
+// with 16-row tiles -- k_resample_periodic's Q = 1 -- where two 32-row slots do not fit LDS or the window needs more k-steps
+// than a 32-row instantiation has (long periods, e.g. 44.1 -> 16 kHz); the row-tiled kernel for rational rates whose
+// geometry that one does not cover; the tiled kernel (and its persistent form) for everything else that is long enough.
+// A stage none of them takes runs the thread-per-output kernel from the polyphase tables alone.
+void Plan::process_resample(int sid) {
+    const int ni = stages[sid].node;
+    const Node& N = nodes[ni];
+    const so_node_t& nd = N.nd;
+    const int child = N.kids[0];
+    stages[sid].processed = true;
+    if (stages[sid].need <= 0) return;
+    RsGeom g = rs_geometry(N, nodes[child].fs, stages[sid].need);
+    StageSpan sp = rs_warm_start(g, stages[sid].lo, stages[sid].need);
+    stages[sid].base = sp.base;
+    stages[sid].in_base = sp.in_base;
+    const int64_t need = sp.need_local;  // local frames from here on
+    g.n_in = sp.in_frames = rs_input_frames(g, need, nodes[child].len, sp.in_base);
+    rs_polyphase_tables(sid, g);
+    g.in_dtype = g.out_dtype = N.dtype;
+    stages[sid].rg = g;
+    // reference positions: DSP.jl's phase accumulator (SIGOPS_RS_EXACT=1 keeps the closed form)
+    std::vector<uint8_t> wrap;
+    if (g.arbitrary && !std::getenv("SIGOPS_RS_EXACT")) {
+        // (period positions can only be baked into the tap tables of the periodic / row-tiled
+        //  kernels: short outputs go to the thread-per-output kernel and list every deviation)
+        replay_phase_accumulator(g, (const double*)nd.p0, nd.i2, sp.base + need, g.exact && need >= 2048, wrap, stages[sid].fix_host, sp.base);
+    }
+    for (int rows_try : {32, 16}) plan_rs_periodic(sid, need, rows_try, wrap);
+    plan_rs_rows(sid, need, wrap);
+    plan_rs_tiled(sid, need);
+    if (!wrap.empty() && !stages[sid].periodic && !stages[sid].rows)  // no tap table took the baked positions
+        replay_phase_accumulator(stages[sid].rg, (const double*)nd.p0, nd.i2, stages[sid].base + need, false, wrap, stages[sid].fix_host,
+                                 stages[sid].base);
+    if (!stages[sid].fix_host.empty()) stages[sid].fix_buf = raw_buf(stages[sid].fix_host.size() * sizeof(RsFix));
+    bind_resample_input(sid, child, sp);
+}
+
+// ---- periodic (SGPR-tap) form for rational rates: tiles of `rows_try` rows ----
+void Plan::plan_rs_periodic(int sid, int64_t need, int rows_try, const std::vector<uint8_t>& wrap) {
+    const Node& N = nodes[stages[sid].node];
+    const so_node_t& nd = N.nd;
+    const RsGeom g = stages[sid].rg;
+    const int hlen = nd.i2;
+    if (stages[sid].periodic || std::getenv(rows_try == 16 ? "SIGOPS_RS_NOQ1" : "SIGOPS_RS_NO32ROWS")) return;
+    if ((!g.arbitrary || g.exact) && need >= 2048) {
+        constexpr int RM = 16;  // outputs per group = N of the 16x16x4 MFMA tile
+        const int64_t Lb = g.L, Mb = g.M;
+        // (8 channels per tile when possible: per-frame gains of a fused source are evaluated
+        //  once per tile row-group, and 8 rows give every loader wave exactly one chunk)
+        int ct = channels_per_group(N.nch, 8);
+        if (const char* ev = std::getenv("SIGOPS_RS_CT")) {  // tuning knob
+            int c = std::atoi(ev);
+            if ((c == 1 || c == 2 || c == 4 || c == 8) && N.nch % c == 0) ct = c;
+        }
+        if (rows_try == 16 && ((N.dtype != SO_F64 && N.dtype != SO_F32) || (ct != 8 && ct != 4))) return;  // (the Q = 1 instantiations)
+        const int pt = rows_try / ct;  // tile = 32 or 16 rows (k_resample_periodic's Q)
+        // super-period: t periods so that (a) L*t is a multiple of 16 where possible and
+        // (b) a tile (pt super-periods) covers ~1100 input frames per channel
+        int64_t tmin = 16 / std::__gcd<int64_t>(Lb, 16);
+        int64_t t = std::max<int64_t>(1, 1100 / (pt * Mb));
+        t = std::max<int64_t>(tmin, t / tmin * tmin);
+        if (Lb * t > 4096) t = std::max<int64_t>(1, 4096 / Lb);
+        // ... and (c) at most twelve blocks of 16 outputs where tmin allows it: a compute wave keeps ONE block's taps
+        // in registers.  Upsampling by small ratios (x 2, x 3, x 4: few inputs per period) used to get super-periods of
+        // 30 - 70 blocks from (b), for which no instantiation exists -- the stage fell to the row-tiled kernel at a
+        // tenth of the speed (x 2 of 8 channels x 300 s: 11 ms; tools/ratio_probe.py)
+        if (!std::getenv("SIGOPS_RS_NOBLOCKCAP")) {
+            // (twenty-four -- a compute wave keeps two blocks' taps -- for x 2 and x 3, whose twelve-block super-period is
+            //  under a hundred input frames: tiles of 400 frames instead of 800, 0.64 ms instead of 0.39)
+            const int64_t nblk = env_int("SIGOPS_RS_BLOCKCAP", (Lb <= 3 && Mb * (192 / Lb) < 100) ? 24 : 12);
+            const int64_t tcap = std::max<int64_t>(tmin, (nblk * 16 / Lb) / tmin * tmin);
+            t = std::min(t, tcap);
+        }
+        const int64_t Ls = Lb * t, Ms = Mb * t;
+        const PeriodPos pos = period_positions(g, Ls, &wrap);
+        const std::vector<int64_t>& jr = pos.j;
+        const std::vector<int>& pr = pos.p;
+        const std::vector<double>& ar = pos.alpha;
+        const GroupWindows win = group_windows(jr, Ls);
+        const std::vector<int>& jend = win.jend;
+        const int ngroups = (int)jend.size();
+        // k-steps: smallest instantiated KS covering taps + span (tab is zero padded);
+        // compute waves: one (or two) groups each, taps stay in registers
+        int kw = 0, ncomp = 0, gper = 0;
+        {
+            const int ksneed = (int)((g.taps + win.maxspan + 3) / 4);
+            gper = ngroups <= 12 ? 1 : (ngroups <= 24 ? 2 : 0);
+            if (const char* ev = std::getenv("SIGOPS_RS_GPER")) gper = std::atoi(ev);  // tuning knob
+            const int ks1[] = {12, 14, 16, 20, 28}, ks2[] = {14}, ks16[] = {28, 36};
+            if (rows_try == 16) {
+                if (gper == 1)
+                    for (int k : ks16)
+                        if (!kw && k >= ksneed) kw = 4 * k;
+            } else if (gper == 1) {
+                for (int k : ks1)
+                    if (!kw && k >= ksneed) kw = 4 * k;
+            } else if (gper == 2 || gper == 3) {
+                for (int k : ks2)
+                    if (!kw && k >= ksneed) kw = 4 * k;
+            }
+            if (kw) ncomp = (ngroups + gper - 1) / gper;
+        }
+        const int jlo = aligned_window_start(jend[0], kw);
+        // (+0..3 frames: a row's staged span is a whole number of MFMA k-steps, which the fused IIR
+        //  state pass walks from jlo to the end)
+        const int64_t tile_len = (pt - 1) * Ms + (jend[ngroups - 1] - jlo + 1 + 3) / 4 * 4;
+        // tiles are kept in LDS in the sample type and staged from the 128-byte aligned frame
+        // below their first input (+15 / +31 frames); rows are 16-byte multiples for LDS-DMA
+        const int64_t esz_t = (int64_t)dsize(N.dtype), vfr = 16 / esz_t;
+        int64_t pitch = (tile_len + (128 / esz_t - 1) + 2 * vfr + vfr - 1) / vfr * vfr;
+        size_t lds_bytes = ((size_t)ct * pitch * esz_t + 7) / 8 * 8;
+        size_t tab_bytes = (size_t)ngroups * kw * RM * 8;
+        // LDS ring: as many tile slots as fit in 160 KiB, at most 4 (2 tiles in flight
+        // beyond the one being retired), at least 2 (plain double buffering)
+        int nslots = (int)std::min<size_t>(4, kRsLdsAvail / std::max<size_t>(1, lds_bytes));
+        if (const char* ev = std::getenv("SIGOPS_RS_SLOTS")) nslots = std::min(nslots, std::max(2, std::atoi(ev)));
+        if (kw && nslots >= 2 && tab_bytes <= (16u << 20) && tile_len < (1 << 30)) {
+            const double* h = (const double*)nd.p0;
+            const std::vector<double> tab = fill_tap_blocks(jr, Ls, jend, kw, g.taps, [&](int64_t r, int64_t age) {
+                const Tap t = tap(h, hlen, g.nphi, pr[(size_t)r], age);
+                return t.hv + ar[(size_t)r] * t.dv;
+            });
+            RsPeriodic rp{};
+            rp.n_in = g.n_in;
+            rp.n_out = need;
+            rp.L = Ls;
+            rp.M = Ms;
+            rp.nperiods = (need + Ls - 1) / Ls;
+            rp.pt = pt;
+            rp.ct = ct;
+            rp.rows = rows_try;
+            rp.ngroups = ngroups;
+            rp.kw = kw;
+            rp.tile_len = (int)tile_len;
+            rp.lds_pitch = (int)pitch;
+            rp.jlo = jlo;
+            rp.nch = N.nch;
+            rp.ptshift = 0;
+            while ((1 << rp.ptshift) < pt) ++rp.ptshift;  // pt is a power of two
+            rp.nslots = nslots;
+            // persistent kernel: 16 waves per workgroup (8 when a wave owns three groups and
+            // needs the registers), one workgroup per CU; the waves that do not compute load
+            rp.nwaves = gper >= 3 ? 8 : 16;
+            rp.ncompute = ncomp;
+            rp.grid = 256;
+            if (const char* ev = std::getenv("SIGOPS_RS_NWAVES")) rp.nwaves = std::max(2, std::min(16, std::atoi(ev)));
+            if (const char* ev = std::getenv("SIGOPS_RS_GRID")) rp.grid = std::max(1, std::atoi(ev));
+            if (const char* ev = std::getenv("SIGOPS_RS_DEBUG")) rp.pad = std::atoi(ev);  // ablation knob
+            if (const char* ev = std::getenv("SIGOPS_RS_NLOAD")) rp.nload = std::max(1, std::atoi(ev));  // tuning knob
+            // A Float32 signal all the way (the stage's own type: its source tile and its output are Float32): the products
+            // on the Float32 MFMA where an instantiation exists (32-row tiles, one group per compute wave, windows of up to
+            // 20 k-steps, 4 or 8 channels per tile); SIGOPS_RS_NO_F32MFMA keeps the Float64 products rounded once.
+            rp.f32m = (N.dtype == SO_F32 && rows_try == 32 && gper == 1 && kw <= 80 && ct >= 4 && !std::getenv("SIGOPS_RS_NO_F32MFMA")) ? 1 : 0;
+            stages[sid].periodic = true;
+            stages[sid].per_j = jr;
+            stages[sid].per_p = pr;
+            stages[sid].per_a = ar;
+            stages[sid].jend_last = jend[ngroups - 1];
+            stages[sid].rp = rp;
+            stages[sid].tab_host = tab;
+            stages[sid].jend_host = jend;
+            stages[sid].tab_buf = raw_buf(tab.size() * 8);
+            stages[sid].jend_buf = raw_buf(jend.size() * 4);
+            // what k_rs_fixup needs to recompute the groups a non-finite sample reached output by output
+            if (!std::getenv("SIGOPS_RS_NO_FIXUP")) {
+                stages[sid].rs_jrel_host.resize((size_t)Ls);
+                for (int64_t r = 0; r < Ls; ++r) stages[sid].rs_jrel_host[(size_t)r] = (int)(jr[r] - jend[r / RM]);
+                stages[sid].rs_jrel_buf = raw_buf((size_t)Ls * 4);
+                stages[sid].rs_nf_buf = raw_buf((size_t)(4 + 4 * (kRsNfCap + 1)) * 4);
+            }
+        }
+    }
+}
+
+// ---- row-tiled form: rational rates the MFMA kernel's geometry does not cover ----
+void Plan::plan_rs_rows(int sid, int64_t need, const std::vector<uint8_t>& wrap) {
+    const Node& N = nodes[stages[sid].node];
+    const so_node_t& nd = N.nd;
+    const RsGeom g = stages[sid].rg;
+    const int hlen = nd.i2;
+    if (!stages[sid].periodic && (!g.arbitrary || g.exact) && need >= 2048 && g.m0 == 0 &&
+        !std::getenv("SIGOPS_RS_NOROWS")) {
+        // (periods of fewer than 16 outputs -- decimation by 3, 4, 6 ...: L = 1 -- are walked as super-periods of
+        //  whole 16-output blocks: a tile row is a (super-)period, and a row of ONE output left fifteen sixteenths of
+        //  every MFMA tile and most of the staged window unused: 192 -> 48 kHz of 8 channels x 120 s took 12.3 ms,
+        //  0.15 TB/s; tools/rate_matrix.py)
+        const int64_t L1 = g.L, M1 = g.M;
+        const int64_t tsup = (L1 < 16 && !std::getenv("SIGOPS_RR_NOSUPER")) ? 16 / std::__gcd<int64_t>(L1, 16) * env_int("SIGOPS_RR_SUPERK", 2) : 1;  // (32 outputs per row: 20-38 % over 16, 64 no better)
+        const int64_t Lb = L1 * tsup, Mb = M1 * tsup;
+        const double* h = (const double*)nd.p0;
+        const PeriodPos pos = period_positions(g, Lb, &wrap);
+        std::vector<int> jr(Lb);  // (narrowed: the kernel's table of newest inputs is 32-bit; checked against jmin / jmax below)
+        std::vector<double> ctab((size_t)Lb * g.taps, 0.0);
+        int64_t jmin = INT64_MAX, jmax = INT64_MIN;
+        for (int64_t r = 0; r < Lb; ++r) {
+            const int64_t j = pos.j[(size_t)r];
+            jr[r] = (int)j;
+            jmin = std::min(jmin, j - (g.taps - 1));
+            jmax = std::max(jmax, j);
+            for (int k = 0; k < g.taps; ++k) {
+                const Tap t = tap(h, hlen, g.nphi, pos.p[(size_t)r], k);
+                ctab[(size_t)r * g.taps + k] = t.hv + pos.alpha[(size_t)r] * t.dv;
+            }
+        }
+        const int64_t esz_t = (int64_t)dsize(N.dtype);
+        int best_ct = 0, best_pb = 0;
+        int64_t best_pitch = 0, best_len = 0;
+        size_t rr_max_lds = 150 * 1024;
+        if (const char* ev = std::getenv("SIGOPS_RR_MAXLDS")) rr_max_lds = (size_t)std::atoi(ev) * 1024;  // tuning knob
+        // tile choice: the largest row count whose tile fits; two workgroups per CU (tiles of at
+        // most 75 KB) overlap one's staging with the other's MFMAs (config 5: 0.77 -> 0.66 ms),
+        // so that budget is tried first as long as it still gives an MFMA-able tile (>= 16 rows)
+        const bool lds_forced = std::getenv("SIGOPS_RR_MAXLDS") != nullptr;
+        for (int pass = 0; pass < 2 && !best_ct; ++pass) {
+            const size_t budget = lds_forced ? rr_max_lds : (pass == 0 ? (size_t)75 * 1024 : rr_max_lds);
+            for (int rows : {64, 32, 16, 8, 4, 2, 1}) {
+                if (pass == 0 && !lds_forced && rows < 16) break;
+                for (int ct : {8, 4, 2, 1}) {
+                    if (best_ct || N.nch % ct || rows % ct) continue;
+                    const int pb = rows / ct;
+                    const int64_t tile_len = (pb - 1) * Mb + (jmax - jmin + 1);
+                    const int64_t pitch = (tile_len + 3) | 1;  // odd: rows fall on different LDS banks
+                    if ((size_t)ct * pitch * esz_t <= budget && tile_len < (1 << 30)) {
+                        best_ct = ct;
+                        best_pb = pb;
+                        best_pitch = pitch;
+                        best_len = tile_len;
+                        rr_max_lds = budget;
+                    }
+                }
+            }
+        }
+        // MFMA path: groups of 16 phases against a [kw x 16] tap block (rows = 16, 32 or 64)
+        std::vector<double> mtab;
+        std::vector<int> mjend;
+        int kw_m = 0, ngroups_m = 0;
+        if (best_ct && (best_ct * best_pb) % 16 == 0 && !std::getenv("SIGOPS_RS_NOROWS_MFMA")) {
+            const int64_t jmin_scalar = jmin;
+            const GroupWindows win = group_windows(jr, Lb);
+            mjend = win.jend;
+            ngroups_m = (int)mjend.size();
+            kw_m = (int)((g.taps + win.maxspan + 3) / 4 * 4);
+            mtab = fill_tap_blocks(jr, Lb, mjend, kw_m, g.taps, [&](int64_t r, int64_t age) { return ctab[(size_t)r * g.taps + age]; });
+            for (int gi = 0; gi < ngroups_m; ++gi) jmin = std::min<int64_t>(jmin, mjend[gi] - (kw_m - 1));
+            // the window of a group may start a few frames before the oldest tap: re-size the tile
+            const int64_t tile_len = (best_pb - 1) * Mb + (jmax - jmin + 1);
+            const int64_t pitch = (tile_len + 3) | 1;
+            if ((size_t)best_ct * pitch * esz_t <= rr_max_lds + 2048) {
+                best_len = tile_len;
+                best_pitch = pitch;
+            } else {
+                kw_m = 0;
+                mtab.clear();
+                jmin = jmin_scalar;
+            }
+        }
+        if (best_ct && jmin > INT32_MIN && jmax < INT32_MAX && (size_t)Lb * g.taps * 8 <= (64u << 20)) {
+            RsRows rr{};
+            rr.kw = kw_m;
+            rr.ngroups = ngroups_m;
+            rr.pbshift = 0;
+            while ((1 << rr.pbshift) < best_pb) ++rr.pbshift;  // pb is a power of two
+            stages[sid].mtab_host = mtab;
+            stages[sid].mjend_host = mjend;
+            stages[sid].mtab_buf = raw_buf(std::max<size_t>(mtab.size(), 1) * 8);
+            stages[sid].mjend_buf = raw_buf(std::max<size_t>(mjend.size(), 1) * 4);
+            rr.n_in = g.n_in;
+            rr.n_out = need;
+            rr.L = Lb;
+            rr.M = Mb;
+            rr.nperiods = (need + Lb - 1) / Lb;
+            rr.taps = g.taps;
+            rr.ct = best_ct;
+            rr.pb = best_pb;
+            rr.jlo = (int)jmin;
+            rr.tile_len = (int)best_len;
+            rr.pitch = (int)best_pitch;
+            rr.nch = N.nch;
+            if (const char* ev = std::getenv("SIGOPS_RS_DEBUG")) rr.debug = std::atoi(ev);  // ablation knob
+            rr.threads = 1024;
+            if (const char* ev = std::getenv("SIGOPS_RR_THREADS")) rr.threads = std::max(64, std::min(1024, std::atoi(ev) / 64 * 64));  // tuning knob
+            stages[sid].rows = true;
+            stages[sid].rr = rr;
+            stages[sid].tab_host = ctab;
+            stages[sid].jend_host = jr;
+            stages[sid].tab_buf = raw_buf(ctab.size() * 8);
+            stages[sid].jend_buf = raw_buf(jr.size() * 4);
+        }
+    }
+}
+
+// ---- tiled form for everything else that is long enough (no period to exploit) ----
+void Plan::plan_rs_tiled(int sid, int64_t need) {
+    const Node& N = nodes[stages[sid].node];
+    const RsGeom g = stages[sid].rg;
+    if (!stages[sid].periodic && !stages[sid].rows && need >= 2048 && !std::getenv("SIGOPS_RS_NOTILED")) {
+        const int64_t esz_t = (int64_t)dsize(N.dtype);
+        const size_t tabs = (size_t)2 * g.taps * g.nphi * 8;
+        int ct = channels_per_group(N.nch, 8);
+        // inputs per output (fine-grid step / Nphi), for sizing the tile
+        const double step = g.arbitrary ? g.delta / g.nphi : (double)g.M / (double)g.L;
+        for (; ct >= 1; ct >>= 1) {
+            if (N.nch % ct) continue;
+            // two workgroups per CU when the tables allow it (their staging and arithmetic overlap)
+            size_t budget = tabs <= (size_t)24 * 1024 ? (size_t)77 * 1024 - tabs - (size_t)2 * (g.taps + 2 * g.nphi + 2) * 8 : (size_t)150 * 1024 - std::min<size_t>(tabs, 150 * 1024);
+            // (the two-outputs-per-lane form keeps the tile as doubles, frame by frame, in rows of ct + 2)
+            const bool pair = step <= 6.0 && !std::getenv("SIGOPS_RS_NOPAIR");  // (the windows of a pair within 8 frames)
+            const size_t frame_bytes = pair ? (size_t)(ct >= 2 ? ct + 2 : 1) * 8 : (size_t)ct * esz_t;
+            int64_t tile_in = (int64_t)(budget / frame_bytes);
+            int64_t tile_out = (int64_t)std::floor((double)(tile_in - g.taps - 24) / step);  // (k_resample_tiled2 stages 8 frames before the first window)
+            tile_out = std::min<int64_t>(tile_out, 4096);
+            if (tabs <= (size_t)100 * 1024 && tile_out >= 128) {
+                RsTiled rt{};
+                rt.g = g;
+                rt.ct = ct;
+                rt.tile_out = (int32_t)tile_out;
+                rt.tile_in = (int32_t)tile_in;
+                rt.pitch = (int32_t)(tile_in | 1);
+                rt.ntiles = (need + tile_out - 1) / tile_out;
+                rt.pair = pair;
+                stages[sid].tiled = true;
+                stages[sid].rt = rt;
+                stages[sid].pfbt_host.assign((size_t)g.taps * g.nphi, 0.0);
+                stages[sid].dpfbt_host.assign((size_t)g.taps * g.nphi, 0.0);
+                for (int p = 0; p < g.nphi; ++p)
+                    for (int k = 0; k < g.taps; ++k) {
+                        stages[sid].pfbt_host[(size_t)k * g.nphi + p] = stages[sid].pfb_host[(size_t)p * g.taps + k];
+                        stages[sid].dpfbt_host[(size_t)k * g.nphi + p] = stages[sid].dpfb_host[(size_t)p * g.taps + k];
+                    }
+                stages[sid].pfbt_buf = raw_buf(stages[sid].pfbt_host.size() * 8);
+                stages[sid].dpfbt_buf = raw_buf(stages[sid].dpfbt_host.size() * 8);
+                plan_rs_arb(sid, need, pair, step);
+                break;
+            }
+        }
+    }
+}
+
+// ---- the persistent form of the tiled kernel (k_resample_arb): Float64, DSP.jl's 32 phases, windows of a pair close ----
+// (a persistent workgroup zeroes its ring and builds its tables first: ~22 us before the first output, 15
+//  for the tiled kernel; from 1.5 M output samples on the pipelined walk is ahead -- tools/arb_len_sweep.py)
+void Plan::plan_rs_arb(int sid, int64_t need, bool pair, double step) {
+    const Node& N = nodes[stages[sid].node];
+    const RsGeom g = stages[sid].rg;
+    const int64_t arb_min = env_int("SIGOPS_ARB_MIN", 1500000);
+    if (pair && g.nphi == 32 && (N.dtype == SO_F64 || N.dtype == SO_F32) && need >= 16384 && need * N.nch >= arb_min &&
+        !std::getenv("SIGOPS_RS_NOARB")) {
+        const int esz_a = (int)dsize(N.dtype), chf = 1024 / esz_a;  // (ring element bytes; frames per loader chunk)
+        RsArb ra{};
+        ra.g = g;
+        const int cta = channels_per_group(N.nch, 8);
+        ra.ct = cta;
+        const int dmax = (int)std::ceil(step) + 1;  // newest inputs of two consecutive outputs, at most this far apart
+        // four outputs per lane where their windows stay close and all eight channels are in the
+        // workgroup: the LDS reads of a frame serve four outputs (the kernel is bound by them)
+        // (four outputs per lane -- the LDS reads of a frame serve four outputs -- is built and measured:
+        //  compute waves alone 0.204 ms instead of 0.185, its 32-byte-strided stores cost what the
+        //  reads save; opt-in)
+        int no = env_int("SIGOPS_ARB_NO", 2);
+        if (no != 4 || cta != 8 || step > 1.5) no = 2;
+        ra.no = no;
+        ra.zrows = (no - 1) * dmax + 3;
+        int ringf = 4096;
+        while (ringf >= 512 && resample_arb_lds_bytes(g.taps, ra.zrows, cta, ringf, esz_a) + 1024 > (size_t)160 * 1024) ringf >>= 1;
+        ringf = env_int("SIGOPS_ARB_RING", ringf);
+        ra.depth = env_int("SIGOPS_ARB_DEPTH", no == 4 ? 2 : 4);
+        ra.debug = env_int("SIGOPS_ARB_DEBUG", 0);
+        const int per_batch = (int)std::ceil(64.0 * no * step) + 2;
+        // a batch's own span + what the loader has in flight must fit next to NC batches in progress
+        int nc = (ringf - (ra.depth * chf + chf - 1 + g.taps + no * dmax + 32)) / per_batch;
+        nc = std::min(nc, no == 4 ? 7 : 8);  // (pairs: 4 waves 0.268 ms, 6 0.242, 8 0.231, 11 0.235 on the x pi / 3 bench)
+        nc = std::min(nc, env_int("SIGOPS_ARB_NC", nc));
+        ra.nc = nc;
+        ra.ringf = ringf;
+        ra.nbatches = (need + 64 * no - 1) / (64 * no);
+        const int64_t ncg = N.nch / cta;
+        int64_t nr = std::max<int64_t>(1, env_int("SIGOPS_ARB_GRID", 256) / ncg);
+        nr = std::min(nr, std::max<int64_t>(1, ra.nbatches / (2 * std::max(nc, 1))));
+        ra.bpr = (ra.nbatches + nr - 1) / nr;
+        ra.nranges = (int32_t)((ra.nbatches + ra.bpr - 1) / ra.bpr);
+        if (nc >= 4 && ringf >= 1024 && ringf >= 512 && ncg * ra.nranges < (1ll << 31)) {
+            stages[sid].arbk = true;
+            stages[sid].ra = ra;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// the SOS cascade
+
+// the sections in launch groups of at most kMaxSec; the cascade's gain goes with the last group
+static std::vector<SosCoefs> sos_section_groups(const double* sos, int nsec, double gain_all) {
+    std::vector<SosCoefs> groups;
+    for (int s0 = 0; s0 < nsec; s0 += kMaxSec) {
+        SosCoefs cf{};
+        cf.nsec = std::min(kMaxSec, nsec - s0);
+        for (int f = 0; f < cf.nsec; ++f) {
+            const double* b = sos + 6 * (s0 + f);
+            if (b[3] != 1.0) fail(SO_ERR_INVALID, "SOS rows must be normalised (a0 == 1)");
+            cf.b0[f] = b[0];
+            cf.b1[f] = b[1];
+            cf.b2[f] = b[2];
+            cf.a1[f] = b[4];
+            cf.a2[f] = b[5];
+        }
+        cf.gain = (s0 + kMaxSec >= nsec) ? gain_all : 1.0;
+        groups.push_back(cf);
+    }
+    return groups;
+}
+
+// ---- ill-conditioned cascade: the reference's own order of operations (see sos_rounding_sensitivity) ----
+static bool sos_wants_exact(const double* sos, int nsec, double gain_all, const std::vector<SosCoefs>& groups, int nch, int64_t need) {
+    bool exact = false;
+    {
+        const char* ev = std::getenv("SIGOPS_SOS_EXACT");  // 1: always, 0: never (measurement aid)
+        if (ev) exact = std::atoi(ev) != 0;
+        else {
+            exact = nsec >= 3 && sos_rounding_sensitivity(sos, nsec, gain_all) > kSosExactTol;
+            if (!exact && nsec >= 2) {  // ... or the chunked form itself, at the chunk length this signal would get
+                const int64_t tgt = kSosSequences / std::max(1, nch);
+                const int64_t nck = std::max<int64_t>(1, std::min<int64_t>(tgt, need / 64));
+                const int64_t Lp = ((need + nck - 1) / nck + 31) / 32 * 32;
+                const double cs = nck > 1 ? sos_chunk_sensitivity(groups, Lp, need) : 0.0;
+                exact = cs > kSosExactTol;
+                if (std::getenv("SIGOPS_DEBUG_PLAN"))
+                    std::fprintf(stderr, "[sigops] IIR of %d sections: rounding sensitivity %.3g, chunked (L = %lld) %.3g -> %s\n", nsec,
+                                 nsec >= 3 ? sos_rounding_sensitivity(sos, nsec, gain_all) : 0.0, (long long)Lp, cs, exact ? "sequential" : "time-parallel");
+            }
+        }
+    }
+    return exact;
+}
+
+// ---- warm start: frames before the first one anybody reads (After, a later window of a
+//      stream) matter only through the filter state, and what a state contributes has decayed
+//      below 2^-70 after W frames: start from zero state W frames early instead of at frame 0.
+//      (The reference filters the skipped frames, src/cutting.jl:160-173; same values.) ----
+// (not below a Normpower: the state the skipped frames leave is tiny, not negligible, once the
+//  result is divided by the rms of a decayed tail)
+// Returns the first frame to compute, 0: no warm start.
+static int64_t sos_warm_start(const std::vector<SosCoefs>& groups, bool exact, bool under_norm, int64_t lo, int64_t need) {
+    if (!exact && !under_norm && lo < need && lo >= 8192 &&
+        !std::getenv("SIGOPS_NO_WARM_START")) {
+        int64_t Wd = 0;
+        for (auto& cf : groups) {
+            const int D = 2 * cf.nsec;
+            Mat P = sos_state_matrix(cf);
+            int64_t w = 1;
+            while (maxabs(P) >= std::ldexp(1.0, -70) && w < ((int64_t)1 << 40)) {
+                P = matmul(P, P, D);
+                w <<= 1;
+            }
+            Wd += w;  // (groups are cascaded: decay times add up at worst)
+        }
+        if (lo - Wd >= 4096) return (lo - Wd) / 64 * 64;
+    }
+    return 0;
+}
+
+// ---- single pass (one read, one write): wave tiles in time order with a look-back over the
+//      zero-state end states of the kt previous tiles (see k_sos_onepass) ----
+// Opt-in (SIGOPS_SOS_ONEPASS=1): its HBM traffic is the algorithmic minimum, but on MI355X it
+// is bound by fp64 vector work and dependent chains at two waves per SIMD (28.8 M x 8, order
+// 10: 1.7 ms against 1.13 ms for the three-pass form, which streams at ~5 TB/s) -- DESIGN.md.
+void Plan::plan_sos_onepass(int sid, int64_t need, const std::vector<SosCoefs>& groups, bool exact) {
+    const Node& N = nodes[stages[sid].node];
+    if (!exact && need >= 4096 && std::getenv("SIGOPS_SOS_ONEPASS") && !std::getenv("SIGOPS_SOS_3PASS")) {
+        SosOne o{};
+        const int tf = 64 * kSosLc;
+        o.n = need;
+        o.nch = N.nch;
+        o.ntiles = (int)((need + tf - 1) / tf);
+        o.nlev = 6;
+        o.bt = std::min(4, N.nch);
+        if (const char* ev = std::getenv("SIGOPS_SOS_BT")) o.bt = std::max(1, std::min(4, std::atoi(ev)));  // tuning knob
+        if (const char* ev = std::getenv("SIGOPS_SOS_DEBUG")) o.debug = std::atoi(ev);  // ablation knob
+        const double tol1 = std::ldexp(1.0, -70);
+        bool ok = (int64_t)o.ntiles * o.nch < (1 << 30);
+        // look-back depth: first kt with ||(A^tf)^kt|| < 2^-70, the same for every group
+        int kt = 1;
+        std::vector<Mat> As, Ts;
+        for (auto& cf : groups) {
+            const int D = 2 * cf.nsec;
+            Mat A = sos_state_matrix(cf);
+            Mat T = matpow(A, tf, D);
+            As.push_back(A);
+            Ts.push_back(T);
+            Mat cur = T;
+            int k = 1;
+            while (ok && !(maxabs(cur) < tol1)) {
+                cur = matmul(cur, T, D);
+                if (++k > 64) ok = false;  // a pole this close to the unit circle: three-pass form
+            }
+            kt = std::max(kt, k);
+        }
+        if (ok) {
+            o.kt = kt;
+            std::vector<double> tabs;
+            std::vector<size_t> offs;
+            for (size_t gi = 0; gi < groups.size(); ++gi) {
+                const int D = 2 * groups[gi].nsec;
+                offs.push_back(tabs.size());
+                Mat P = matpow(As[gi], kSosLc, D);  // M = A^lc, then M^2, M^4, ...
+                for (int lev = 0; lev < o.nlev; ++lev) {
+                    tabs.insert(tabs.end(), P.begin(), P.end());
+                    P = matmul(P, P, D);
+                }
+                Mat cur = ident(D);
+                for (int j = 0; j < kt; ++j) {  // (A^tf)^j
+                    tabs.insert(tabs.end(), cur.begin(), cur.end());
+                    cur = matmul(cur, Ts[gi], D);
+                }
+            }
+            stages[sid].onepass = true;
+            stages[sid].so1 = o;
+            stages[sid].one_tabs_host = tabs;
+            stages[sid].one_tabs_off = offs;
+            stages[sid].one_tabs_buf = raw_buf(tabs.size() * 8);
+            stages[sid].one_sync_buf = raw_buf(64);
+            stages[sid].one_vpub_buf = raw_buf((size_t)o.ntiles * o.nch * 2 * kMaxSec * 8);
+        }
+    }
+}
+
+void Plan::process_sos(int sid) {
+    const int ni = stages[sid].node;
+    const Node& N = nodes[ni];
+    const Cascade m = merged_cascade(ni);
+    stages[sid].processed = true;
+    if (stages[sid].need <= 0) return;
+    const int64_t need_all = stages[sid].need;
+    const int nsec = m.sos.empty() ? N.nd.i0 : (int)(m.sos.size() / 6);
+    const double* sos = m.sos.empty() ? (const double*)N.nd.p0 : m.sos.data();
+    const std::vector<SosCoefs> groups = sos_section_groups(sos, nsec, m.gain);
+    const bool exact = sos_wants_exact(sos, nsec, m.gain, groups, N.nch, need_all);
+    StageSpan sp;
+    sp.need_local = sp.in_frames = need_all;
+    if (!isinf_(nodes[m.child].len)) sp.in_frames = std::min(need_all, nodes[m.child].len.n);
+    if (const int64_t base = sos_warm_start(groups, exact, stages[sid].under_norm, stages[sid].lo, need_all)) {
+        sp.base = sp.in_base = stages[sid].base = stages[sid].in_base = base;
+        sp.need_local = sp.in_frames = need_all - base;  // local frames from here on
+    }
+    plan_sos_onepass(sid, sp.need_local, groups, exact);
+    sos_chunking(sid, sp.need_local, N.nch, N.dtype, groups, exact, kSosSequences / std::max(1, N.nch));
+    bind_sos_input(sid, m, sp);
+}
+
+void Plan::process_norm(int sid) {
+    const Node& N = nodes[stages[sid].node];
+    const int child = N.kids[0];
+    const int64_t need = stages[sid].need;
     stages[sid].processed = true;
     if (need <= 0) return;
-
-    int64_t in_frames = need;
-    if (stages[sid].kind == ST_RESAMPLE) {
-        RsGeom g{};
-        g.arbitrary = nd.i0 == SO_RS_ARBITRARY;
-        int hlen = nd.i2;
-        g.nphi = g.arbitrary ? nd.i1 : (int)nd.l0;
-        if (g.nphi < 1) fail(SO_ERR_INVALID, "resampler: bad phase count");
-        g.L = nd.l0;
-        g.M = nd.l1;
-        const bool plain_fir = nd.i0 == SO_RS_FIR;  // Filt(x,h): ratio 1, causal, no delay compensation
-        if (plain_fir) {
-            g.nphi = 1;
-            g.L = g.M = 1;
-        }
-        if (!g.arbitrary && (g.L < 1 || g.M < 1)) fail(SO_ERR_INVALID, "resampler: bad ratio");
-        g.delta = g.arbitrary ? (double)g.nphi / nd.d0 : 0.0;
-        g.c0 = plain_fir ? 0.0 : (double)(hlen - 1) / 2.0;
-        g.c0i = plain_fir ? 0 : (hlen - 1) / 2;
-        g.taps = (hlen + g.nphi - 1) / g.nphi;
-        g.nch = N.nch;
-        g.m0 = 0;
-        g.n_out = need;
-        if (g.arbitrary) rs_detect_exact(g, nd.fs, C.fs, nd.d0);
-        // ---- warm start (see the IIR's below): the resampler is an FIR filter, so outputs from a
-        //      whole number of periods before the first frame anybody reads on are the same whether
-        //      the stage starts there or at frame 0, except the first few (their taps reach before
-        //      the first input staged), which nobody reads either ----
-        int64_t rbase = 0;
-        if ((!g.arbitrary || g.exact) && stages[sid].lo >= 8192 && stages[sid].lo < need &&
-            !std::getenv("SIGOPS_NO_WARM_START")) {
-            const int64_t margin = (g.taps + 2 + g.M - 1) / g.M + 1;  // periods
-            int64_t k = stages[sid].lo / g.L - margin;
-            k = k / 16 * 16;  // (16 M inputs: the first staged input stays 128-byte aligned)
-            if (k > 0 && k * g.L >= 4096) {
-                rbase = k * g.L;
-                stages[sid].base = rbase;
-                stages[sid].in_base = k * g.M;
-                need -= rbase;
-                g.n_out = need;
-            }
-        }
-        // ... and a rate without a period (no integer frame rates) has nothing to be aligned with: output m sits at
-        // q_m = c0 + m delta whatever came before it (the accumulator's deviations from that are listed from the
-        // nearest checkpoint of an earlier replay, accumulator.cpp), so the stage starts at the first frame anybody
-        // reads -- g.m0 -- and stages its input from taps + 2 frames before that output's newest input -- g.j0
-        if (g.arbitrary && !g.exact && stages[sid].lo >= 8192 && stages[sid].lo < need && !std::getenv("SIGOPS_NO_WARM_START")) {
-            rbase = stages[sid].lo / 64 * 64;  // (whole lines for the kernels' stores)
-            const double q = g.c0 + (double)rbase * g.delta;
-            const int64_t jf = (int64_t)std::floor(q) / g.nphi;
-            const int64_t ib = std::max<int64_t>(0, jf - g.taps - 2) / 16 * 16;
-            stages[sid].base = rbase;
-            stages[sid].in_base = ib;
-            g.m0 = rbase;
-            g.j0 = ib;
-            need -= rbase;
-            g.n_out = need;
-        }
-        // newest input of the last needed output
-        int64_t jl;
-        if (g.arbitrary && g.exact) {
-            int64_t Nn = (need - 1) * ((int64_t)g.nphi * g.M);
-            jl = (g.c0i + Nn / g.L) / g.nphi;
-        } else if (g.arbitrary) {
-            double q = g.c0 + (double)(g.m0 + need - 1) * g.delta;
-            jl = (int64_t)std::floor(q) / g.nphi - g.j0;
-        } else jl = (g.c0i + (need - 1) * g.M) / g.L;
-        int64_t nin = jl + 2;  // +1 slack: host rounding of q may differ from the device's at ties
-        if (!isinf_(C.len)) nin = std::min(nin, C.len.n - stages[sid].in_base);
-        g.n_in = nin;
-        in_frames = nin;
-        // polyphase tables: pfb[p][k] = h[p + nphi*k]; dpfb from dh = [diff(h);0]
-        const double* h = (const double*)nd.p0;
-        stages[sid].pfb_host.assign((size_t)g.nphi * g.taps, 0.0);
-        stages[sid].dpfb_host.assign((size_t)g.nphi * g.taps, 0.0);
-        for (int p = 0; p < g.nphi; ++p)
-            for (int k = 0; k < g.taps; ++k) {
-                int64_t hi = p + (int64_t)g.nphi * k;
-                stages[sid].pfb_host[(size_t)p * g.taps + k] = hi < hlen ? h[hi] : 0.0;
-                stages[sid].dpfb_host[(size_t)p * g.taps + k] = hi + 1 < hlen ? h[hi + 1] - h[hi] : 0.0;
-            }
-        stages[sid].pfb_buf = raw_buf(stages[sid].pfb_host.size() * 8);
-        stages[sid].dpfb_buf = raw_buf(stages[sid].dpfb_host.size() * 8);
-        g.in_dtype = g.out_dtype = N.dtype;
-        stages[sid].rg = g;
-        // reference positions: DSP.jl's phase accumulator (SIGOPS_RS_EXACT=1 keeps the closed form)
-        std::vector<uint8_t> wrap;
-        if (g.arbitrary && !std::getenv("SIGOPS_RS_EXACT")) {
-            // (period positions can only be baked into the tap tables of the periodic / row-tiled
-            //  kernels: short outputs go to the thread-per-output kernel and list every deviation)
-            replay_phase_accumulator(g, (const double*)nd.p0, hlen, rbase + need, g.exact && need >= 2048, wrap, stages[sid].fix_host, rbase);
-        }
-        // position of period output r as the tap tables see it: the closed form, or the
-        // accumulator's wrap-around tie (previous input, last phase, alpha = 1) where it is the rule
-        auto wrap_at = [&](int64_t r) { return !wrap.empty() && wrap[r % g.L]; };
-        // ---- periodic (SGPR-tap) variant for rational rates ---------------------------
-        // (32-row tiles first; 16-row tiles -- k_resample_periodic's Q = 1 -- where two 32-row slots do not fit LDS or the
-        //  window needs more k-steps than a 32-row instantiation has: long periods, e.g. 44.1 -> 16 kHz)
-        for (int rows_try : {32, 16}) {
-        if (stages[sid].periodic || std::getenv(rows_try == 16 ? "SIGOPS_RS_NOQ1" : "SIGOPS_RS_NO32ROWS")) continue;
-        if ((!g.arbitrary || g.exact) && need >= 2048) {
-            constexpr int RM = 16;  // outputs per group = N of the 16x16x4 MFMA tile
-            const int64_t Lb = g.L, Mb = g.M;
-            // (8 channels per tile when possible: per-frame gains of a fused source are evaluated
-            //  once per tile row-group, and 8 rows give every loader wave exactly one chunk)
-            int ct = 1;
-            for (int c : {8, 4, 2})
-                if (N.nch % c == 0) {
-                    ct = c;
-                    break;
-                }
-            if (const char* ev = std::getenv("SIGOPS_RS_CT")) {  // tuning knob
-                int c = std::atoi(ev);
-                if ((c == 1 || c == 2 || c == 4 || c == 8) && N.nch % c == 0) ct = c;
-            }
-            if (rows_try == 16 && ((N.dtype != SO_F64 && N.dtype != SO_F32) || (ct != 8 && ct != 4))) continue;  // (the Q = 1 instantiations)
-            const int pt = rows_try / ct;  // tile = 32 or 16 rows (k_resample_periodic's Q)
-            // super-period: t periods so that (a) L*t is a multiple of 16 where possible and
-            // (b) a tile (pt super-periods) covers ~1100 input frames per channel
-            int64_t tmin = 16 / std::__gcd<int64_t>(Lb, 16);
-            int64_t t = std::max<int64_t>(1, 1100 / (pt * Mb));
-            t = std::max<int64_t>(tmin, t / tmin * tmin);
-            if (Lb * t > 4096) t = std::max<int64_t>(1, 4096 / Lb);
-            // ... and (c) at most twelve blocks of 16 outputs where tmin allows it: a compute wave keeps ONE block's taps
-            // in registers.  Upsampling by small ratios (x 2, x 3, x 4: few inputs per period) used to get super-periods of
-            // 30 - 70 blocks from (b), for which no instantiation exists -- the stage fell to the row-tiled kernel at a
-            // tenth of the speed (x 2 of 8 channels x 300 s: 11 ms; tools/ratio_probe.py)
-            if (!std::getenv("SIGOPS_RS_NOBLOCKCAP")) {
-                // (twenty-four -- a compute wave keeps two blocks' taps -- for x 2 and x 3, whose twelve-block super-period is
-                //  under a hundred input frames: tiles of 400 frames instead of 800, 0.64 ms instead of 0.39)
-                const int64_t nblk = env_int("SIGOPS_RS_BLOCKCAP", (Lb <= 3 && Mb * (192 / Lb) < 100) ? 24 : 12);
-                const int64_t tcap = std::max<int64_t>(tmin, (nblk * 16 / Lb) / tmin * tmin);
-                t = std::min(t, tcap);
-            }
-            const int64_t Ls = Lb * t, Ms = Mb * t;
-            auto pos = [&](int64_t r, int64_t& j, int& p, double& alpha) {
-                int64_t qi;
-                if (g.arbitrary) {
-                    int64_t Nn = r * ((int64_t)g.nphi * Mb);
-                    qi = g.c0i + Nn / Lb;
-                    alpha = (double)(Nn % Lb) / (double)Lb;
-                } else {
-                    qi = g.c0i + r * Mb;
-                    alpha = 0.0;
-                }
-                if (wrap_at(r)) {
-                    qi -= 1;
-                    alpha = 1.0;
-                }
-                j = qi / g.nphi;
-                p = (int)(qi % g.nphi);
-            };
-            std::vector<int64_t> jr(Ls);
-            std::vector<int> pr(Ls);
-            std::vector<double> ar(Ls);
-            for (int64_t r = 0; r < Ls; ++r) pos(r, jr[r], pr[r], ar[r]);
-            const int ngroups = (int)((Ls + RM - 1) / RM);
-            int64_t maxspan = 0;
-            std::vector<int> jend(ngroups);
-            for (int gi = 0; gi < ngroups; ++gi) {
-                int64_t r0 = (int64_t)gi * RM, r1 = std::min<int64_t>(Ls, r0 + RM);
-                jend[gi] = (int)jr[r1 - 1];
-                maxspan = std::max(maxspan, jr[r1 - 1] - jr[r0]);
-            }
-            // k-steps: smallest instantiated KS covering taps + span (tab is zero padded);
-            // compute waves: one (or two) groups each, taps stay in registers
-            int kw = 0, ncomp = 0, gper = 0;
-            {
-                const int ksneed = (g.taps + (int)maxspan + 3) / 4;
-                gper = ngroups <= 12 ? 1 : (ngroups <= 24 ? 2 : 0);
-                if (const char* ev = std::getenv("SIGOPS_RS_GPER")) gper = std::atoi(ev);  // tuning knob
-                const int ks1[] = {12, 14, 16, 20, 28}, ks2[] = {14}, ks16[] = {28, 36};
-                if (rows_try == 16) {
-                    if (gper == 1)
-                        for (int k : ks16)
-                            if (!kw && k >= ksneed) kw = 4 * k;
-                } else if (gper == 1) {
-                    for (int k : ks1)
-                        if (!kw && k >= ksneed) kw = 4 * k;
-                } else if (gper == 2 || gper == 3) {
-                    for (int k : ks2)
-                        if (!kw && k >= ksneed) kw = 4 * k;
-                }
-                if (kw) ncomp = (ngroups + gper - 1) / gper;
-            }
-            // first staged input, rounded down to a multiple of 4 frames so that tiles start
-            // on a 16-byte boundary (vector loads) whenever pt*M is a multiple of 4
-            int jlo = jend[0] - (kw - 1);
-            jlo -= ((jlo % 4) + 4) % 4;
-            // (+0..3 frames: a row's staged span is a whole number of MFMA k-steps, which the fused IIR
-            //  state pass walks from jlo to the end)
-            const int64_t tile_len = (pt - 1) * Ms + (jend[ngroups - 1] - jlo + 1 + 3) / 4 * 4;
-            // tiles are kept in LDS in the sample type and staged from the 128-byte aligned frame
-            // below their first input (+15 / +31 frames); rows are 16-byte multiples for LDS-DMA
-            const int64_t esz_t = (int64_t)dsize(N.dtype), vfr = 16 / esz_t;
-            int64_t pitch = (tile_len + (128 / esz_t - 1) + 2 * vfr + vfr - 1) / vfr * vfr;
-            size_t lds_bytes = ((size_t)ct * pitch * esz_t + 7) / 8 * 8;
-            size_t tab_bytes = (size_t)ngroups * kw * RM * 8;
-            // LDS ring: as many tile slots as fit in 160 KiB, at most 4 (2 tiles in flight
-            // beyond the one being retired), at least 2 (plain double buffering)
-            int nslots = (int)std::min<size_t>(4, (160 * 1024 - sizeof(RsCtl) - 64) / std::max<size_t>(1, lds_bytes));
-            if (const char* ev = std::getenv("SIGOPS_RS_SLOTS")) nslots = std::min(nslots, std::max(2, std::atoi(ev)));
-            if (kw && nslots >= 2 && tab_bytes <= (16u << 20) && tile_len < (1 << 30)) {
-                const double* h = (const double*)nd.p0;
-                std::vector<double> tab((size_t)ngroups * kw * RM, 0.0);
-                for (int gi = 0; gi < ngroups; ++gi) {
-                    int64_t r0 = (int64_t)gi * RM, r1 = std::min<int64_t>(Ls, r0 + RM);
-                    for (int64_t r = r0; r < r1; ++r)
-                        for (int kk = 0; kk < kw; ++kk) {
-                            int64_t rel = jend[gi] - (kw - 1) + kk;  // input index of slot kk
-                            int64_t age = jr[r] - rel;               // tap age for output r
-                            if (age < 0 || age >= g.taps) continue;
-                            int64_t hi = pr[r] + (int64_t)g.nphi * age;
-                            double hv = hi < hlen ? h[hi] : 0.0;
-                            double dv = hi + 1 < hlen ? h[hi + 1] - h[hi] : 0.0;
-                            tab[((size_t)gi * kw + kk) * RM + (r - r0)] = hv + ar[r] * dv;
-                        }
-                }
-                RsPeriodic rp{};
-                rp.n_in = g.n_in;
-                rp.n_out = need;
-                rp.L = Ls;
-                rp.M = Ms;
-                rp.nperiods = (need + Ls - 1) / Ls;
-                rp.pt = pt;
-                rp.ct = ct;
-                rp.rows = rows_try;
-                rp.ngroups = ngroups;
-                rp.kw = kw;
-                rp.tile_len = (int)tile_len;
-                rp.lds_pitch = (int)pitch;
-                rp.jlo = jlo;
-                rp.nch = N.nch;
-                rp.ptshift = 0;
-                while ((1 << rp.ptshift) < pt) ++rp.ptshift;  // pt is a power of two
-                rp.nslots = nslots;
-                // persistent kernel: 16 waves per workgroup (8 when a wave owns three groups and
-                // needs the registers), one workgroup per CU; the waves that do not compute load
-                rp.nwaves = gper >= 3 ? 8 : 16;
-                rp.ncompute = ncomp;
-                rp.grid = 256;
-                if (const char* ev = std::getenv("SIGOPS_RS_NWAVES")) rp.nwaves = std::max(2, std::min(16, std::atoi(ev)));
-                if (const char* ev = std::getenv("SIGOPS_RS_GRID")) rp.grid = std::max(1, std::atoi(ev));
-                if (const char* ev = std::getenv("SIGOPS_RS_DEBUG")) rp.pad = std::atoi(ev);  // ablation knob
-                if (const char* ev = std::getenv("SIGOPS_RS_NLOAD")) rp.nload = std::max(1, std::atoi(ev));  // tuning knob
-                // A Float32 signal all the way (the stage's own type: its source tile and its output are Float32): the products
-                // on the Float32 MFMA where an instantiation exists (32-row tiles, one group per compute wave, windows of up to
-                // 20 k-steps, 4 or 8 channels per tile); SIGOPS_RS_NO_F32MFMA keeps the Float64 products rounded once.
-                rp.f32m = (N.dtype == SO_F32 && rows_try == 32 && gper == 1 && kw <= 80 && ct >= 4 && !std::getenv("SIGOPS_RS_NO_F32MFMA")) ? 1 : 0;
-                stages[sid].periodic = true;
-                stages[sid].per_j = jr;
-                stages[sid].per_p = pr;
-                stages[sid].per_a = ar;
-                stages[sid].jend_last = jend[ngroups - 1];
-                stages[sid].rp = rp;
-                stages[sid].tab_host = tab;
-                stages[sid].jend_host = jend;
-                stages[sid].tab_buf = raw_buf(tab.size() * 8);
-                stages[sid].jend_buf = raw_buf(jend.size() * 4);
-                // what k_rs_fixup needs to recompute the groups a non-finite sample reached output by output
-                if (!std::getenv("SIGOPS_RS_NO_FIXUP")) {
-                    stages[sid].rs_jrel_host.resize((size_t)Ls);
-                    for (int64_t r = 0; r < Ls; ++r) stages[sid].rs_jrel_host[(size_t)r] = (int)(jr[r] - jend[r / RM]);
-                    stages[sid].rs_jrel_buf = raw_buf((size_t)Ls * 4);
-                    stages[sid].rs_nf_buf = raw_buf((size_t)(4 + 4 * (kRsNfCap + 1)) * 4);
-                }
-            }
-        }
-        }
-        // ---- row-tiled variant: rational rates the MFMA kernel's geometry does not cover -------
-        if (!stages[sid].periodic && (!g.arbitrary || g.exact) && need >= 2048 && g.m0 == 0 &&
-            !std::getenv("SIGOPS_RS_NOROWS")) {
-            // (periods of fewer than 16 outputs -- decimation by 3, 4, 6 ...: L = 1 -- are walked as super-periods of
-            //  whole 16-output blocks: a tile row is a (super-)period, and a row of ONE output left fifteen sixteenths of
-            //  every MFMA tile and most of the staged window unused: 192 -> 48 kHz of 8 channels x 120 s took 12.3 ms,
-            //  0.15 TB/s; tools/rate_matrix.py)
-            const int64_t L1 = g.L, M1 = g.M;
-            const int64_t tsup = (L1 < 16 && !std::getenv("SIGOPS_RR_NOSUPER")) ? 16 / std::__gcd<int64_t>(L1, 16) * env_int("SIGOPS_RR_SUPERK", 2) : 1;  // (32 outputs per row: 20-38 % over 16, 64 no better)
-            const int64_t Lb = L1 * tsup, Mb = M1 * tsup;
-            const double* h = (const double*)nd.p0;
-            std::vector<int> jr(Lb);
-            std::vector<double> ctab((size_t)Lb * g.taps, 0.0);
-            int64_t jmin = INT64_MAX, jmax = INT64_MIN;
-            for (int64_t r = 0; r < Lb; ++r) {
-                int64_t qi;
-                double alpha = 0.0;
-                if (g.arbitrary) {
-                    const int64_t Nn = r * ((int64_t)g.nphi * M1);
-                    qi = g.c0i + Nn / L1;
-                    alpha = (double)(Nn % L1) / (double)L1;
-                } else qi = g.c0i + r * M1;
-                if (wrap_at(r)) {
-                    qi -= 1;
-                    alpha = 1.0;
-                }
-                const int64_t j = qi / g.nphi;
-                const int p = (int)(qi % g.nphi);
-                jr[r] = (int)j;
-                jmin = std::min(jmin, j - (g.taps - 1));
-                jmax = std::max(jmax, j);
-                for (int k = 0; k < g.taps; ++k) {
-                    const int64_t hi = p + (int64_t)g.nphi * k;
-                    const double hv = hi < hlen ? h[hi] : 0.0;
-                    const double dv = hi + 1 < hlen ? h[hi + 1] - h[hi] : 0.0;
-                    ctab[(size_t)r * g.taps + k] = hv + alpha * dv;
-                }
-            }
-            const int64_t esz_t = (int64_t)dsize(N.dtype);
-            int best_ct = 0, best_pb = 0;
-            int64_t best_pitch = 0, best_len = 0;
-            size_t rr_max_lds = 150 * 1024;
-            if (const char* ev = std::getenv("SIGOPS_RR_MAXLDS")) rr_max_lds = (size_t)std::atoi(ev) * 1024;  // tuning knob
-            // tile choice: the largest row count whose tile fits; two workgroups per CU (tiles of at
-            // most 75 KB) overlap one's staging with the other's MFMAs (config 5: 0.77 -> 0.66 ms),
-            // so that budget is tried first as long as it still gives an MFMA-able tile (>= 16 rows)
-            const bool lds_forced = std::getenv("SIGOPS_RR_MAXLDS") != nullptr;
-            for (int pass = 0; pass < 2 && !best_ct; ++pass) {
-                const size_t budget = lds_forced ? rr_max_lds : (pass == 0 ? (size_t)75 * 1024 : rr_max_lds);
-                for (int rows : {64, 32, 16, 8, 4, 2, 1}) {
-                    if (pass == 0 && !lds_forced && rows < 16) break;
-                    for (int ct : {8, 4, 2, 1}) {
-                        if (best_ct || N.nch % ct || rows % ct) continue;
-                        const int pb = rows / ct;
-                        const int64_t tile_len = (pb - 1) * Mb + (jmax - jmin + 1);
-                        const int64_t pitch = (tile_len + 3) | 1;  // odd: rows fall on different LDS banks
-                        if ((size_t)ct * pitch * esz_t <= budget && tile_len < (1 << 30)) {
-                            best_ct = ct;
-                            best_pb = pb;
-                            best_pitch = pitch;
-                            best_len = tile_len;
-                            rr_max_lds = budget;
-                        }
-                    }
-                }
-            }
-            // MFMA path: groups of 16 phases against a [kw x 16] tap block (rows = 16, 32 or 64)
-            std::vector<double> mtab;
-            std::vector<int> mjend;
-            int kw_m = 0, ngroups_m = 0;
-            if (best_ct && (best_ct * best_pb) % 16 == 0 && !std::getenv("SIGOPS_RS_NOROWS_MFMA")) {
-                const int64_t jmin_scalar = jmin;
-                ngroups_m = (int)((Lb + 15) / 16);
-                mjend.resize(ngroups_m);
-                int64_t maxspan = 0;
-                for (int gi = 0; gi < ngroups_m; ++gi) {
-                    const int64_t r0 = 16 * (int64_t)gi, r1 = std::min<int64_t>(Lb, r0 + 16);
-                    mjend[gi] = jr[r1 - 1];
-                    maxspan = std::max<int64_t>(maxspan, jr[r1 - 1] - jr[r0]);
-                }
-                kw_m = (int)((g.taps + maxspan + 3) / 4 * 4);
-                mtab.assign((size_t)ngroups_m * kw_m * 16, 0.0);
-                for (int gi = 0; gi < ngroups_m; ++gi) {
-                    const int64_t r0 = 16 * (int64_t)gi, r1 = std::min<int64_t>(Lb, r0 + 16);
-                    jmin = std::min<int64_t>(jmin, mjend[gi] - (kw_m - 1));
-                    for (int64_t r = r0; r < r1; ++r)
-                        for (int kk = 0; kk < kw_m; ++kk) {
-                            const int64_t age = jr[r] - (mjend[gi] - (kw_m - 1) + kk);
-                            if (age >= 0 && age < g.taps)
-                                mtab[((size_t)gi * kw_m + kk) * 16 + (r - r0)] = ctab[(size_t)r * g.taps + age];
-                        }
-                }
-                // the window of a group may start a few frames before the oldest tap: re-size the tile
-                const int64_t tile_len = (best_pb - 1) * Mb + (jmax - jmin + 1);
-                const int64_t pitch = (tile_len + 3) | 1;
-                if ((size_t)best_ct * pitch * esz_t <= rr_max_lds + 2048) {
-                    best_len = tile_len;
-                    best_pitch = pitch;
-                } else {
-                    kw_m = 0;
-                    mtab.clear();
-                    jmin = jmin_scalar;
-                }
-            }
-            if (best_ct && jmin > INT32_MIN && jmax < INT32_MAX && (size_t)Lb * g.taps * 8 <= (64u << 20)) {
-                RsRows rr{};
-                rr.kw = kw_m;
-                rr.ngroups = ngroups_m;
-                rr.pbshift = 0;
-                while ((1 << rr.pbshift) < best_pb) ++rr.pbshift;  // pb is a power of two
-                stages[sid].mtab_host = mtab;
-                stages[sid].mjend_host = mjend;
-                stages[sid].mtab_buf = raw_buf(std::max<size_t>(mtab.size(), 1) * 8);
-                stages[sid].mjend_buf = raw_buf(std::max<size_t>(mjend.size(), 1) * 4);
-                rr.n_in = g.n_in;
-                rr.n_out = need;
-                rr.L = Lb;
-                rr.M = Mb;
-                rr.nperiods = (need + Lb - 1) / Lb;
-                rr.taps = g.taps;
-                rr.ct = best_ct;
-                rr.pb = best_pb;
-                rr.jlo = (int)jmin;
-                rr.tile_len = (int)best_len;
-                rr.pitch = (int)best_pitch;
-                rr.nch = N.nch;
-                if (const char* ev = std::getenv("SIGOPS_RS_DEBUG")) rr.debug = std::atoi(ev);  // ablation knob
-                rr.threads = 1024;
-                if (const char* ev = std::getenv("SIGOPS_RR_THREADS")) rr.threads = std::max(64, std::min(1024, std::atoi(ev) / 64 * 64));  // tuning knob
-                stages[sid].rows = true;
-                stages[sid].rr = rr;
-                stages[sid].tab_host = ctab;
-                stages[sid].jend_host = jr;
-                stages[sid].tab_buf = raw_buf(ctab.size() * 8);
-                stages[sid].jend_buf = raw_buf(jr.size() * 4);
-            }
-        }
-        // ---- tiled variant for everything else that is long enough (no period to exploit) ----
-        if (!stages[sid].periodic && !stages[sid].rows && need >= 2048 && !std::getenv("SIGOPS_RS_NOTILED")) {
-            const int64_t esz_t = (int64_t)dsize(N.dtype);
-            const size_t tabs = (size_t)2 * g.taps * g.nphi * 8;
-            int ct = 1;
-            for (int c : {8, 4, 2})
-                if (N.nch % c == 0) {
-                    ct = c;
-                    break;
-                }
-            // inputs per output (fine-grid step / Nphi), for sizing the tile
-            const double step = g.arbitrary ? g.delta / g.nphi : (double)g.M / (double)g.L;
-            for (; ct >= 1; ct >>= 1) {
-                if (N.nch % ct) continue;
-                // two workgroups per CU when the tables allow it (their staging and arithmetic overlap)
-                size_t budget = tabs <= (size_t)24 * 1024 ? (size_t)77 * 1024 - tabs - (size_t)2 * (g.taps + 2 * g.nphi + 2) * 8 : (size_t)150 * 1024 - std::min<size_t>(tabs, 150 * 1024);
-                // (the two-outputs-per-lane form keeps the tile as doubles, frame by frame, in rows of ct + 2)
-                const bool pair = step <= 6.0 && !std::getenv("SIGOPS_RS_NOPAIR");  // (the windows of a pair within 8 frames)
-                const size_t frame_bytes = pair ? (size_t)(ct >= 2 ? ct + 2 : 1) * 8 : (size_t)ct * esz_t;
-                int64_t tile_in = (int64_t)(budget / frame_bytes);
-                int64_t tile_out = (int64_t)std::floor((double)(tile_in - g.taps - 24) / step);  // (k_resample_tiled2 stages 8 frames before the first window)
-                tile_out = std::min<int64_t>(tile_out, 4096);
-                if (tabs <= (size_t)100 * 1024 && tile_out >= 128) {
-                    RsTiled rt{};
-                    rt.g = g;
-                    rt.ct = ct;
-                    rt.tile_out = (int32_t)tile_out;
-                    rt.tile_in = (int32_t)tile_in;
-                    rt.pitch = (int32_t)(tile_in | 1);
-                    rt.ntiles = (need + tile_out - 1) / tile_out;
-                    rt.pair = pair;
-                    stages[sid].tiled = true;
-                    stages[sid].rt = rt;
-                    stages[sid].pfbt_host.assign((size_t)g.taps * g.nphi, 0.0);
-                    stages[sid].dpfbt_host.assign((size_t)g.taps * g.nphi, 0.0);
-                    for (int p = 0; p < g.nphi; ++p)
-                        for (int k = 0; k < g.taps; ++k) {
-                            stages[sid].pfbt_host[(size_t)k * g.nphi + p] = stages[sid].pfb_host[(size_t)p * g.taps + k];
-                            stages[sid].dpfbt_host[(size_t)k * g.nphi + p] = stages[sid].dpfb_host[(size_t)p * g.taps + k];
-                        }
-                    stages[sid].pfbt_buf = raw_buf(stages[sid].pfbt_host.size() * 8);
-                    stages[sid].dpfbt_buf = raw_buf(stages[sid].dpfbt_host.size() * 8);
-                    // ---- the persistent form (k_resample_arb): Float64, DSP.jl's 32 phases, windows of a pair close ----
-                    // (a persistent workgroup zeroes its ring and builds its tables first: ~22 us before the first output, 15
-                    //  for the tiled kernel; from 1.5 M output samples on the pipelined walk is ahead -- tools/arb_len_sweep.py)
-                    const int64_t arb_min = env_int("SIGOPS_ARB_MIN", 1500000);
-                    if (pair && g.nphi == 32 && (N.dtype == SO_F64 || N.dtype == SO_F32) && need >= 16384 && need * N.nch >= arb_min &&
-                        !std::getenv("SIGOPS_RS_NOARB")) {
-                        const int esz_a = (int)dsize(N.dtype), chf = 1024 / esz_a;  // (ring element bytes; frames per loader chunk)
-                        RsArb ra{};
-                        ra.g = g;
-                        int cta = 1;
-                        for (int c : {8, 4, 2})
-                            if (N.nch % c == 0) {
-                                cta = c;
-                                break;
-                            }
-                        ra.ct = cta;
-                        const int dmax = (int)std::ceil(step) + 1;  // newest inputs of two consecutive outputs, at most this far apart
-                        // four outputs per lane where their windows stay close and all eight channels are in the
-                        // workgroup: the LDS reads of a frame serve four outputs (the kernel is bound by them)
-                        // (four outputs per lane -- the LDS reads of a frame serve four outputs -- is built and measured:
-                        //  compute waves alone 0.204 ms instead of 0.185, its 32-byte-strided stores cost what the
-                        //  reads save; opt-in)
-                        int no = env_int("SIGOPS_ARB_NO", 2);
-                        if (no != 4 || cta != 8 || step > 1.5) no = 2;
-                        ra.no = no;
-                        ra.zrows = (no - 1) * dmax + 3;
-                        int ringf = 4096;
-                        while (ringf >= 512 && resample_arb_lds_bytes(g.taps, ra.zrows, cta, ringf, esz_a) + 1024 > (size_t)160 * 1024) ringf >>= 1;
-                        ringf = env_int("SIGOPS_ARB_RING", ringf);
-                        ra.depth = env_int("SIGOPS_ARB_DEPTH", no == 4 ? 2 : 4);
-                        ra.debug = env_int("SIGOPS_ARB_DEBUG", 0);
-                        const int per_batch = (int)std::ceil(64.0 * no * step) + 2;
-                        // a batch's own span + what the loader has in flight must fit next to NC batches in progress
-                        int nc = (ringf - (ra.depth * chf + chf - 1 + g.taps + no * dmax + 32)) / per_batch;
-                        nc = std::min(nc, no == 4 ? 7 : 8);  // (pairs: 4 waves 0.268 ms, 6 0.242, 8 0.231, 11 0.235 on the x pi / 3 bench)
-                        nc = std::min(nc, env_int("SIGOPS_ARB_NC", nc));
-                        ra.nc = nc;
-                        ra.ringf = ringf;
-                        ra.nbatches = (need + 64 * no - 1) / (64 * no);
-                        const int64_t ncg = N.nch / cta;
-                        int64_t nr = std::max<int64_t>(1, env_int("SIGOPS_ARB_GRID", 256) / ncg);
-                        nr = std::min(nr, std::max<int64_t>(1, ra.nbatches / (2 * std::max(nc, 1))));
-                        ra.bpr = (ra.nbatches + nr - 1) / nr;
-                        ra.nranges = (int32_t)((ra.nbatches + ra.bpr - 1) / ra.bpr);
-                        if (nc >= 4 && ringf >= 1024 && ringf >= 512 && ncg * ra.nranges < (1ll << 31)) {
-                            stages[sid].arbk = true;
-                            stages[sid].ra = ra;
-                        }
-                    }
-                    break;
-                }
-            }
-        }
-        if (!wrap.empty() && !stages[sid].periodic && !stages[sid].rows)  // no tap table took the baked positions
-            replay_phase_accumulator(stages[sid].rg, (const double*)nd.p0, nd.i2, stages[sid].base + need, false, wrap, stages[sid].fix_host,
-                                     stages[sid].base);
-        if (!stages[sid].fix_host.empty()) stages[sid].fix_buf = raw_buf(stages[sid].fix_host.size() * sizeof(RsFix));
-    } else if (stages[sid].kind == ST_SOS) {
-        if (!isinf_(C.len)) in_frames = std::min(need, C.len.n);
-        int nsec = merged_sos.empty() ? nd.i0 : (int)(merged_sos.size() / 6);
-        const double* sos = merged_sos.empty() ? (const double*)nd.p0 : merged_sos.data();
-        const double gain_all = merged_gain;
-        std::vector<SosCoefs> groups;
-        for (int s0 = 0; s0 < nsec; s0 += kMaxSec) {
-            SosCoefs cf{};
-            cf.nsec = std::min(kMaxSec, nsec - s0);
-            for (int f = 0; f < cf.nsec; ++f) {
-                const double* b = sos + 6 * (s0 + f);
-                if (b[3] != 1.0) fail(SO_ERR_INVALID, "SOS rows must be normalised (a0 == 1)");
-                cf.b0[f] = b[0];
-                cf.b1[f] = b[1];
-                cf.b2[f] = b[2];
-                cf.a1[f] = b[4];
-                cf.a2[f] = b[5];
-            }
-            cf.gain = (s0 + kMaxSec >= nsec) ? gain_all : 1.0;
-            groups.push_back(cf);
-        }
-        // ---- ill-conditioned cascade: the reference's own order of operations (see above) ----
-        bool exact = false;
-        {
-            const char* ev = std::getenv("SIGOPS_SOS_EXACT");  // 1: always, 0: never (measurement aid)
-            if (ev) exact = std::atoi(ev) != 0;
-            else {
-                exact = nsec >= 3 && sos_rounding_sensitivity(sos, nsec, gain_all) > kSosExactTol;
-                if (!exact && nsec >= 2) {  // ... or the chunked form itself, at the chunk length this signal would get
-                    const int64_t tgt = kSosSequences / std::max(1, N.nch);
-                    const int64_t nck = std::max<int64_t>(1, std::min<int64_t>(tgt, need / 64));
-                    const int64_t Lp = ((need + nck - 1) / nck + 31) / 32 * 32;
-                    const double cs = nck > 1 ? sos_chunk_sensitivity(groups, Lp, need) : 0.0;
-                    exact = cs > kSosExactTol;
-                    if (std::getenv("SIGOPS_DEBUG_PLAN"))
-                        std::fprintf(stderr, "[sigops] IIR of %d sections: rounding sensitivity %.3g, chunked (L = %lld) %.3g -> %s\n", nsec,
-                                     nsec >= 3 ? sos_rounding_sensitivity(sos, nsec, gain_all) : 0.0, (long long)Lp, cs, exact ? "sequential" : "time-parallel");
-                }
-            }
-        }
-        // ---- warm start: frames before the first one anybody reads (After, a later window of a
-        //      stream) matter only through the filter state, and what a state contributes has decayed
-        //      below 2^-70 after W frames: start from zero state W frames early instead of at frame 0.
-        //      (The reference filters the skipped frames, src/cutting.jl:160-173; same values.) ----
-        // (not below a Normpower: the state the skipped frames leave is tiny, not negligible, once the
-        //  result is divided by the rms of a decayed tail)
-        if (!exact && !stages[sid].under_norm && stages[sid].lo < need && stages[sid].lo >= 8192 &&
-            !std::getenv("SIGOPS_NO_WARM_START")) {
-            int64_t Wd = 0;
-            for (auto& cf : groups) {
-                const int D = 2 * cf.nsec;
-                Mat P = sos_state_matrix(cf);
-                int64_t w = 1;
-                while (maxabs(P) >= std::ldexp(1.0, -70) && w < ((int64_t)1 << 40)) {
-                    P = matmul(P, P, D);
-                    w <<= 1;
-                }
-                Wd += w;  // (groups are cascaded: decay times add up at worst)
-            }
-            if (stages[sid].lo - Wd >= 4096) {
-                const int64_t base = (stages[sid].lo - Wd) / 64 * 64;
-                stages[sid].base = stages[sid].in_base = base;
-                need -= base;  // local frames from here on
-                in_frames = need;
-            }
-        }
-        // ---- single pass (one read, one write): wave tiles in time order with a look-back over the
-        //      zero-state end states of the kt previous tiles (see k_sos_onepass) ----
-        // Opt-in (SIGOPS_SOS_ONEPASS=1): its HBM traffic is the algorithmic minimum, but on MI355X it
-        // is bound by fp64 vector work and dependent chains at two waves per SIMD (28.8 M x 8, order
-        // 10: 1.7 ms against 1.13 ms for the three-pass form, which streams at ~5 TB/s) -- DESIGN.md.
-        if (!exact && need >= 4096 && std::getenv("SIGOPS_SOS_ONEPASS") && !std::getenv("SIGOPS_SOS_3PASS")) {
-            SosOne o{};
-            const int tf = 64 * kSosLc;
-            o.n = need;
-            o.nch = N.nch;
-            o.ntiles = (int)((need + tf - 1) / tf);
-            o.nlev = 6;
-            o.bt = std::min(4, N.nch);
-            if (const char* ev = std::getenv("SIGOPS_SOS_BT")) o.bt = std::max(1, std::min(4, std::atoi(ev)));  // tuning knob
-            if (const char* ev = std::getenv("SIGOPS_SOS_DEBUG")) o.debug = std::atoi(ev);  // ablation knob
-            const double tol1 = std::ldexp(1.0, -70);
-            bool ok = (int64_t)o.ntiles * o.nch < (1 << 30);
-            // look-back depth: first kt with ||(A^tf)^kt|| < 2^-70, the same for every group
-            int kt = 1;
-            std::vector<Mat> As, Ts;
-            for (auto& cf : groups) {
-                const int D = 2 * cf.nsec;
-                Mat A = sos_state_matrix(cf);
-                Mat T = matpow(A, tf, D);
-                As.push_back(A);
-                Ts.push_back(T);
-                Mat cur = T;
-                int k = 1;
-                while (ok && !(maxabs(cur) < tol1)) {
-                    cur = matmul(cur, T, D);
-                    if (++k > 64) ok = false;  // a pole this close to the unit circle: three-pass form
-                }
-                kt = std::max(kt, k);
-            }
-            if (ok) {
-                o.kt = kt;
-                std::vector<double> tabs;
-                std::vector<size_t> offs;
-                for (size_t gi = 0; gi < groups.size(); ++gi) {
-                    const int D = 2 * groups[gi].nsec;
-                    offs.push_back(tabs.size());
-                    Mat P = matpow(As[gi], kSosLc, D);  // M = A^lc, then M^2, M^4, ...
-                    for (int lev = 0; lev < o.nlev; ++lev) {
-                        tabs.insert(tabs.end(), P.begin(), P.end());
-                        P = matmul(P, P, D);
-                    }
-                    Mat cur = ident(D);
-                    for (int j = 0; j < kt; ++j) {  // (A^tf)^j
-                        tabs.insert(tabs.end(), cur.begin(), cur.end());
-                        cur = matmul(cur, Ts[gi], D);
-                    }
-                }
-                stages[sid].onepass = true;
-                stages[sid].so1 = o;
-                stages[sid].one_tabs_host = tabs;
-                stages[sid].one_tabs_off = offs;
-                stages[sid].one_tabs_buf = raw_buf(tabs.size() * 8);
-                stages[sid].one_sync_buf = raw_buf(64);
-                stages[sid].one_vpub_buf = raw_buf((size_t)o.ntiles * o.nch * 2 * kMaxSec * 8);
-            }
-        }
-        sos_chunking(sid, need, N.nch, N.dtype, groups, exact, kSosSequences / std::max(1, N.nch));
-    } else {  // ST_NORM
-        in_frames = need;
+    {
         int64_t total = need * N.nch;
         int nparts = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (total + kBlock * 8 - 1) / (kBlock * 8)));
         stages[sid].nparts = nparts;
@@ -1176,27 +1327,196 @@ void Plan::process_stage(int sid) {
         const size_t nb32 = N.dtype == SO_F32 ? (size_t)((total + 1023) / 1024) : 0;
         stages[sid].partial_buf = raw_buf(std::max((size_t)nparts * 8, 2 * nb32 * 4));
     }
-
-    // lower the child over the frames this stage consumes
-    std::vector<Piece> ps;
-    const int64_t in_base = stages[sid].in_base;
-    if (in_base > 0) check_frames(child, in_base);
-    {
-        // whatever this stage reads feeds a Normpower too if the stage itself does (or is one): a
-        // filter there must keep the RELATIVE accuracy of a decayed tail (see launch_sos_xscan)
-        const bool norm_below = stages[sid].kind == ST_NORM || stages[sid].under_norm;
-        in_norm += norm_below;
-        if (in_frames > 0) ps = lower(child, Rect{0, in_frames, 0, N.nch}, Map{1, in_base, 1, 0});
-        in_norm -= norm_below;
+    StageSpan sp;
+    sp.in_base = stages[sid].in_base;
+    sp.need_local = sp.in_frames = need;
+    const std::vector<Piece> ps = lower_input(sid, child, sp, true);
+    if (stages[sid].out_buf >= 0) bufs[stages[sid].out_buf].frame0 = stages[sid].base;
+    Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
+    S.in_frames = sp.in_frames;
+    const bool direct = S.norm_direct && direct_source(S, ps, N.dtype, N.nch);
+    if (S.norm_alias) {
+        // `vals` is the child stage's buffer (planner.cpp): lowering the child above registered the frames it needs
+        if (ps.size() != 1 || exprs[ps[0].e].op != E_LOAD || exprs[ps[0].e].leaf.buf != S.out_buf)
+            fail(SO_ERR_RUNTIME, "internal: Normpower over a stage buffer expected that buffer");
+        S.in_buf = S.out_buf;
+        S.in_pitch = -1;
+    } else if (S.norm_direct && direct && S.in_array_node >= 0) {
+        // the array itself is `vals` (planner.cpp): K4 reads it in place
+    } else if (S.norm_direct) {
+        // planner.cpp took the in-place form from the node kinds (an array under Until / After), the lowered child is not
+        // ONE plain load after all (pieces split at a boundary, a view the leaf test does not take): the sum of squares
+        // is taken over a materialised copy as it used to be -- the readers, lowered as "the child's own pieces ./ rms",
+        // are unaffected -- instead of refusing the plan
+        S.norm_direct = false;
+        S.in_array_node = -1;
+        S.in_offset = 0;
+        S.pw_step = emit_pointwise(ps, S.out_buf, N.dtype);
+        S.in_buf = S.out_buf;
+        S.in_pitch = -1;
+    } else {
+        // materialise the child straight into `vals` (the stage's own output buffer)
+        S.pw_step = emit_pointwise(ps, S.out_buf, N.dtype);
+        S.in_buf = S.out_buf;
+        S.in_pitch = -1;
     }
-    if (stages[sid].kind == ST_SOS && in_frames > 0) {  // the reference filters whole blocks of its input
+}
+
+// ---------------------------------------------------------------------------
+// binding a stage to its input
+
+// The child lowered over the frames the stage consumes.  Whatever the stage reads feeds a Normpower too if the stage
+// itself does (or is one) -- `norm_below`: a filter there must keep the RELATIVE accuracy of a decayed tail (see
+// launch_sos_xscan).
+std::vector<Piece> Plan::lower_input(int sid, int child, const StageSpan& sp, bool norm_below) {
+    std::vector<Piece> ps;
+    if (sp.in_base > 0) check_frames(child, sp.in_base);
+    in_norm += norm_below;
+    if (sp.in_frames > 0) ps = lower(child, Rect{0, sp.in_frames, 0, nodes[stages[sid].node].nch}, Map{1, sp.in_base, 1, 0});
+    in_norm -= norm_below;
+    return ps;
+}
+
+// the type a filter or resampler reads its child in: the child's own, integers as Float64
+static int filter_input_dtype(const Node& N, const Node& C) {
+    if (float_of(C.dtype) != N.dtype) fail(SO_ERR_INVALID, "filter dtype mismatch");
+    return C.dtype == SO_I64 ? SO_F64 : C.dtype;
+}
+
+// Direct source: a single plain contiguous load of the right type, read where it lies (Stage::in_array_node / in_buf /
+// in_offset / in_pitch).  A stage buffer read from a later channel is turned down AFTER the view is written: the caller
+// that materialises the input overwrites it, the carrier fusion leaves in_offset / in_pitch as they are here.
+bool Plan::direct_source(Stage& S, const std::vector<Piece>& ps, int in_dtype, int nch) const {
+    if (ps.size() != 1) return false;
+    const Expr& e = exprs[ps[0].e];
+    if (!plain_load(e, in_dtype, nch, true, false)) return false;
+    S.in_array_node = e.array_node;
+    S.in_buf = e.leaf.buf;  // stage buffer or -1 (array)
+    S.in_offset = e.array_node >= 0 ? leaf_offset(e.leaf) : e.leaf.df;
+    S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
+    return e.array_node >= 0 || e.leaf.dc == 0;
+}
+
+// ... or that load plus / times ONE sine generator (`Mix(Signal(sin), x)`, `Amplify(x, Signal(sin))`
+// in Float64): the IIR forms the sum / product in its own loads (k_sos_tiled, SosGeom::src_op) --
+// no K1 pass, no intermediate in HBM (config 4: every scene is Mix |> Filt)
+bool Plan::match_sine_source(Stage& S, const std::vector<Piece>& ps, const Node& N, const StageSpan& sp) {
+    if (ps.size() != 1) return false;
+    const Expr& e = exprs[ps[0].e];
+    const int64_t in_frames = sp.in_frames, need = sp.need_local;
+    bool direct = false;
+    if ((e.op == E_ADD || e.op == E_MUL) && e.dtype == SO_F64 && N.dtype == SO_F64 &&
+        !S.sg.exact && !S.onepass && in_frames == need && !std::getenv("SIGOPS_SOS_NOSRC")) {
+        auto strip = [&](int x) {
+            while (exprs[x].op == E_RETYPE) x = exprs[x].a;
+            return x;
+        };
+        const int ea = strip(e.a), eb = strip(e.b);
+        const int li = exprs[ea].op == E_LOAD ? ea : (exprs[eb].op == E_LOAD ? eb : -1);
+        const int fi = li == ea ? eb : ea;
+        if (li >= 0) {
+            const Expr& l = exprs[li];
+            const Expr& f = exprs[fi];
+            // (a stage buffer read from a later channel is not taken: direct_source's rule, here part of the test)
+            const bool load_ok = plain_load(l, SO_F64, N.nch, true, false) && (l.array_node >= 0 || l.leaf.dc == 0);
+            const bool fn_ok = f.op == E_FUNC && f.leaf.mode == SO_FN_SIN && f.leaf.sf == 1 && f.dtype == SO_F64;
+            if (load_ok && fn_ok) {
+                direct = true;
+                S.in_array_node = l.array_node;
+                S.in_buf = l.leaf.buf;
+                S.in_offset = l.array_node >= 0 ? leaf_offset(l.leaf) : l.leaf.df;
+                S.in_pitch = l.leaf.cstride;
+                S.src_op = e.op == E_ADD ? 1 : 2;
+                S.src_fn = f.leaf;
+                if (l.array_node >= 0) count_array(l.array_node);
+            }
+        }
+    }
+    return direct;
+}
+
+// A stage's input as one pointwise step into a buffer of its own
+void Plan::materialise_input(int sid, const std::vector<Piece>& ps, int64_t in_frames, int nch, int in_dtype) {
+    const int b = new_buf(in_frames, nch, in_dtype);
+    stages[sid].in_buf = b;
+    stages[sid].in_pitch = -1;
+    stages[sid].in_array_node = -1;
+    stages[sid].in_offset = 0;
+    const int step = emit_pointwise(ps, b, in_dtype);
+    stages[sid].pw_step = step;  // (indexed after the call: the vectors may have grown)
+}
+
+// plain source (direct array / stage buffer / materialised input) as one 0-step carrier
+static DCarrier default_carrier(const Stage& S, int64_t frames, int dtype, int nch) {
+    DCarrier c{};
+    c.a = 0;
+    c.b = frames;
+    c.dtype = dtype;
+    c.array_node = S.in_array_node;
+    c.buf = S.in_array_node >= 0 ? -1 : S.in_buf;
+    c.df = S.in_offset;
+    c.cstride = S.in_array_node >= 0 ? (nch == 1 ? 0 : S.in_pitch) : -1;  // -1: buffer pitch
+    return c;
+}
+
+void Plan::bind_sos_input(int sid, const Cascade& m, const StageSpan& sp) {
+    const Node& N = nodes[stages[sid].node];
+    const int64_t in_base = sp.in_base, in_frames = sp.in_frames, need = sp.need_local;
+    const std::vector<Piece> ps = lower_input(sid, m.child, sp, stages[sid].under_norm);
+    if (in_frames > 0) {  // the reference filters whole blocks of its input
         const int64_t bs = std::max(1, N.nd.i1);
         int64_t fr = (in_base + in_frames + bs - 1) / bs * bs;
-        for (int64_t b2 : merged_bs) fr = (fr + b2 - 1) / b2 * b2;  // (... and so does every filter merged into this one)
-        check_frames(child, fr);
+        for (int64_t b2 : m.bs) fr = (fr + b2 - 1) / b2 * b2;  // (... and so does every filter merged into this one)
+        check_frames(m.child, fr);
     }
-    if (stages[sid].kind == ST_RESAMPLE && in_frames > 0) {
-        // ... and so does the resampler: it refills its input `rows` frames at a time, rows = trunc(max(1, min(N_out,
+    if (stages[sid].out_buf >= 0) bufs[stages[sid].out_buf].frame0 = stages[sid].base;
+    Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
+    S.in_frames = in_frames;
+    const int in_dtype = filter_input_dtype(N, nodes[m.child]);
+    const bool direct = direct_source(S, ps, in_dtype, N.nch) || match_sine_source(S, ps, N, sp);
+    // A filter over a plain source (an array, a stage buffer, either one plus / times a sine) may run as ONE pass of the
+    // block-state-space kernel (Plan::fuse_plain_sos: k_rsos with an identity resampler) instead of the three-pass chunked
+    // scan: its source as a carrier, like a periodic resampler's.  The direct view above stays -- what the three passes
+    // read if the fused form is not taken.
+    // (below a Normpower: where every Normpower's region starts at this filter's first frame -- Stage::norm_df == 0.  What the
+    //  one-pass form's warm starts cut, 2^-70 of what lay a decay time earlier, is then 2^-70 of something INSIDE the region
+    //  the rms is taken over; a Normpower of a decayed tail alone -- `Filt |> After |> Normpower` -- keeps the exact scan.)
+    if (direct && S.groups.size() == 1 && S.groups[0].nsec <= 6 && !S.sg.exact && !S.onepass &&
+        (!S.under_norm || (S.norm_df == 0 && !std::getenv("SIGOPS_NORM_EXACT_FILT"))) &&
+        S.base == 0 && in_base == 0 && in_frames == need && (N.dtype == SO_F64 || (N.dtype == SO_F32 && !std::getenv("SIGOPS_RSOS_NO32"))) &&
+        need * N.nch >= (std::getenv("SIGOPS_RSOS_MINGROUPS") || (std::getenv("SIGOPS_RSOS_BATCH") && std::atoi(std::getenv("SIGOPS_RSOS_BATCH")) == 1) ? (int64_t)4096 : ((int64_t)1 << 22)) && !std::getenv("SIGOPS_NO_RSOS") && !std::getenv("SIGOPS_NO_PLAIN_RSOS")) {
+        std::vector<DCarrier> cs;
+        // (a Float32 signal: a plain Float32 array or buffer only -- the kernel's ring then keeps the Float32 samples)
+        if (build_carriers(ps, N.nch, cs, false) && cs.size() == 1 && (N.dtype == SO_F64 || (cs[0].nsteps == 0 && cs[0].dtype == SO_F32))) S.carriers = cs;
+    }
+    if (!direct) materialise_input(sid, ps, in_frames, N.nch, in_dtype);
+    if (!stages[sid].carriers.empty()) {
+        const int cb = raw_buf(stages[sid].carriers.size() * sizeof(DCarrier));
+        stages[sid].car_buf = cb;
+        stages[sid].ctl_buf = raw_buf(sizeof(RsCtl));
+    }
+}
+
+// Can this periodic resampler stage read `x (op) y` of two arrays itself (the A2 instantiations)?  Float64 -- or Float32 all
+// the way --, 32-row tiles of 4 or 8 channels, 14 k-steps, one group per compute wave, and two tile slots + the loader
+// waves' staging rows of the second array fit LDS.
+// (Float64 groups of FOUR channels: measured 1.81 ms for two 25 M x 4 arrays where K1's sum + the one-array
+//  kernel take 0.87 -- round 6, tools/operator_matrix.py NCH=4; left to K1 unless SIGOPS_RS_ARR2_CT4.  With a
+//  filter behind, the fused kernel takes both arrays itself: Stage::alt_carriers, bind_resample_input)
+static bool arr2_fits(const Stage& S, int stage_dtype) {
+    return (stage_dtype == SO_F64 || (stage_dtype == SO_F32 && S.rp.f32m)) && S.rp.rows == 32 &&
+           (S.rp.ct == 8 || (S.rp.ct == 4 && (stage_dtype == SO_F32 || std::getenv("SIGOPS_RS_ARR2_CT4")))) && S.rp.kw == 56 &&
+           (S.rp.ngroups + S.rp.ncompute - 1) / S.rp.ncompute == 1 &&
+           (size_t)2 * S.rp.ct * S.rp.lds_pitch * dsize(stage_dtype) + (size_t)(S.rp.nwaves - S.rp.ncompute) * S.rp.ct * 1024 <= kRsLdsAvail;
+}
+
+void Plan::bind_resample_input(int sid, int child, const StageSpan& sp) {
+    const int ni = stages[sid].node;
+    const Node& N = nodes[ni];
+    const int64_t in_base = sp.in_base, in_frames = sp.in_frames;
+    const std::vector<Piece> ps = lower_input(sid, child, sp, stages[sid].under_norm);
+    if (in_frames > 0) {
+        // ... and so does the resampler (as the IIR, bind_sos_input): it refills its input `rows` frames at a time, rows = trunc(max(1, min(N_out,
         // blocksize) / ratio)) (reference src/filters.jl:185-199 init_length, :237-244 refill), so an error that sits in
         // child frames the outputs asked for never depend on -- an indexing pad on a computed signal beyond them -- is
         // raised all the same (tools/tree_soak_multirate.py seed 16046)
@@ -1210,113 +1530,9 @@ void Plan::process_stage(int sid) {
     if (stages[sid].out_buf >= 0) bufs[stages[sid].out_buf].frame0 = stages[sid].base;
     Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
     S.in_frames = in_frames;
-    int in_dtype = S.kind == ST_NORM ? N.dtype : C.dtype;
-    if (S.kind != ST_NORM && float_of(C.dtype) != N.dtype) fail(SO_ERR_INVALID, "filter dtype mismatch");
-    if (S.kind != ST_NORM && C.dtype == SO_I64) in_dtype = SO_F64;
-    // direct source: a single plain contiguous load of the right type
-    bool direct = false;
-    if ((S.kind != ST_NORM || S.norm_direct) && ps.size() == 1) {
-        const Expr& e = exprs[ps[0].e];
-        if (e.op == E_LOAD && e.leaf.mode == LM_PLAIN && e.leaf.sf == 1 && e.leaf.sc == 1 &&
-            e.leaf.fstride == 1 && e.leaf.dtype == in_dtype && e.leaf.df >= 0 && e.leaf.dc >= 0 &&
-            (e.leaf.cstride > 0 || e.leaf.cstride == -1 || N.nch == 1)) {
-            direct = true;
-            S.in_array_node = e.array_node;
-            S.in_buf = e.leaf.buf;  // stage buffer or -1 (array)
-            S.in_offset = e.leaf.df;
-            S.in_pitch = e.leaf.cstride;  // -1: pitch of in_buf
-            if (e.array_node >= 0) {
-                // element offset = df*fstride + dc*cstride
-                S.in_offset = e.leaf.df + e.leaf.dc * std::max<int64_t>(e.leaf.cstride, 0);
-            } else {
-                if (e.leaf.dc != 0) direct = false;
-            }
-        }
-        // ... or that load plus / times ONE sine generator (`Mix(Signal(sin), x)`, `Amplify(x, Signal(sin))`
-        // in Float64): the IIR forms the sum / product in its own loads (k_sos_tiled, SosGeom::src_op) --
-        // no K1 pass, no intermediate in HBM (config 4: every scene is Mix |> Filt)
-        if (!direct && S.kind == ST_SOS && (e.op == E_ADD || e.op == E_MUL) && e.dtype == SO_F64 && N.dtype == SO_F64 &&
-            !S.sg.exact && !S.onepass && in_frames == need && !std::getenv("SIGOPS_SOS_NOSRC")) {
-            auto strip = [&](int x) {
-                while (exprs[x].op == E_RETYPE) x = exprs[x].a;
-                return x;
-            };
-            const int ea = strip(e.a), eb = strip(e.b);
-            const int li = exprs[ea].op == E_LOAD ? ea : (exprs[eb].op == E_LOAD ? eb : -1);
-            const int fi = li == ea ? eb : ea;
-            if (li >= 0) {
-                const Expr& l = exprs[li];
-                const Expr& f = exprs[fi];
-                const bool load_ok = l.leaf.mode == LM_PLAIN && l.leaf.sf == 1 && l.leaf.sc == 1 && l.leaf.fstride == 1 &&
-                                     l.leaf.dtype == SO_F64 && l.leaf.df >= 0 && l.leaf.dc >= 0 &&
-                                     (l.leaf.cstride > 0 || l.leaf.cstride == -1 || N.nch == 1) &&
-                                     (l.array_node >= 0 || l.leaf.dc == 0);
-                const bool fn_ok = f.op == E_FUNC && f.leaf.mode == SO_FN_SIN && f.leaf.sf == 1 && f.dtype == SO_F64;
-                if (load_ok && fn_ok) {
-                    direct = true;
-                    S.in_array_node = l.array_node;
-                    S.in_buf = l.leaf.buf;
-                    S.in_offset = l.leaf.df;
-                    S.in_pitch = l.leaf.cstride;
-                    if (l.array_node >= 0) S.in_offset = l.leaf.df + l.leaf.dc * std::max<int64_t>(l.leaf.cstride, 0);
-                    S.src_op = e.op == E_ADD ? 1 : 2;
-                    S.src_fn = f.leaf;
-                    if (l.array_node >= 0) count_array(l.array_node);
-                }
-            }
-        }
-    }
-    // A filter over a plain source (an array, a stage buffer, either one plus / times a sine) may run as ONE pass of the
-    // block-state-space kernel (Plan::fuse_plain_sos: k_rsos with an identity resampler) instead of the three-pass chunked
-    // scan: its source as a carrier, like a periodic resampler's.  The direct view above stays -- what the three passes
-    // read if the fused form is not taken.
-    // (below a Normpower: where every Normpower's region starts at this filter's first frame -- Stage::norm_df == 0.  What the
-    //  one-pass form's warm starts cut, 2^-70 of what lay a decay time earlier, is then 2^-70 of something INSIDE the region
-    //  the rms is taken over; a Normpower of a decayed tail alone -- `Filt |> After |> Normpower` -- keeps the exact scan.)
-    if (direct && S.kind == ST_SOS && S.groups.size() == 1 && S.groups[0].nsec <= 6 && !S.sg.exact && !S.onepass &&
-        (!S.under_norm || (S.norm_df == 0 && !std::getenv("SIGOPS_NORM_EXACT_FILT"))) &&
-        S.base == 0 && in_base == 0 && in_frames == need && (N.dtype == SO_F64 || (N.dtype == SO_F32 && !std::getenv("SIGOPS_RSOS_NO32"))) &&
-        need * N.nch >= (std::getenv("SIGOPS_RSOS_MINGROUPS") || (std::getenv("SIGOPS_RSOS_BATCH") && std::atoi(std::getenv("SIGOPS_RSOS_BATCH")) == 1) ? (int64_t)4096 : ((int64_t)1 << 22)) && !std::getenv("SIGOPS_NO_RSOS") && !std::getenv("SIGOPS_NO_PLAIN_RSOS")) {
-        std::vector<DCarrier> cs;
-        // (a Float32 signal: a plain Float32 array or buffer only -- the kernel's ring then keeps the Float32 samples)
-        if (build_carriers(ps, N.nch, cs, false) && cs.size() == 1 && (N.dtype == SO_F64 || (cs[0].nsteps == 0 && cs[0].dtype == SO_F32))) S.carriers = cs;
-    }
-    if (S.kind == ST_NORM && S.norm_alias) {
-        // `vals` is the child stage's buffer (planner.cpp): lowering the child above registered the frames it needs
-        if (ps.size() != 1 || exprs[ps[0].e].op != E_LOAD || exprs[ps[0].e].leaf.buf != S.out_buf)
-            fail(SO_ERR_RUNTIME, "internal: Normpower over a stage buffer expected that buffer");
-        S.in_buf = S.out_buf;
-        S.in_pitch = -1;
-    } else if (S.kind == ST_NORM && S.norm_direct && direct && S.in_array_node >= 0) {
-        // the array itself is `vals` (planner.cpp): K4 reads it in place
-    } else if (S.kind == ST_NORM && S.norm_direct) {
-        // planner.cpp took the in-place form from the node kinds (an array under Until / After), the lowered child is not
-        // ONE plain load after all (pieces split at a boundary, a view the leaf test does not take): the sum of squares
-        // is taken over a materialised copy as it used to be -- the readers, lowered as "the child's own pieces ./ rms",
-        // are unaffected -- instead of refusing the plan
-        S.norm_direct = false;
-        S.in_array_node = -1;
-        S.in_offset = 0;
-        S.pw_step = emit_pointwise(ps, S.out_buf, N.dtype);
-        S.in_buf = S.out_buf;
-        S.in_pitch = -1;
-    } else if (S.kind == ST_NORM) {
-        // materialise the child straight into `vals` (the stage's own output buffer)
-        S.pw_step = emit_pointwise(ps, S.out_buf, N.dtype);
-        S.in_buf = S.out_buf;
-        S.in_pitch = -1;
-    } else if (!direct && S.kind == ST_RESAMPLE && S.periodic &&
-               build_carriers(ps, N.nch, S.carriers, ga_fits(S, N.dtype),
-                              // (the A2 instantiations: Float64 -- or Float32 all the way --, 32-row tiles of 4 or 8 channels, 14 k-steps, one group per compute wave)
-                              // ... and two tile slots + the loader waves' staging rows of the second array fit LDS)
-                              // (Float64 groups of FOUR channels: measured 1.81 ms for two 25 M x 4 arrays where K1's sum + the one-array
-                              //  kernel take 0.87 -- round 6, tools/operator_matrix.py NCH=4; left to K1 unless SIGOPS_RS_ARR2_CT4.  With a
-                              //  filter behind, the fused kernel takes both arrays itself: Stage::alt_carriers below)
-                              (N.dtype == SO_F64 || (N.dtype == SO_F32 && S.rp.f32m)) && S.rp.rows == 32 &&
-                                  (S.rp.ct == 8 || (S.rp.ct == 4 && (N.dtype == SO_F32 || std::getenv("SIGOPS_RS_ARR2_CT4")))) && S.rp.kw == 56 &&
-                                  (S.rp.ngroups + S.rp.ncompute - 1) / S.rp.ncompute == 1 &&
-                                  (size_t)2 * S.rp.ct * S.rp.lds_pitch * dsize(N.dtype) + (size_t)(S.rp.nwaves - S.rp.ncompute) * S.rp.ct * 1024 <=
-                                      160 * 1024 - sizeof(RsCtl) - 64)) {
+    const int in_dtype = filter_input_dtype(N, nodes[child]);
+    const bool direct = direct_source(S, ps, in_dtype, N.nch);
+    if (!direct && S.periodic && build_carriers(ps, N.nch, S.carriers, ga_fits(S, N.dtype), arr2_fits(S, N.dtype))) {
         // every piece is `array (op) per-frame values`: evaluated inside the kernel's LDS
         // staging, no intermediate in HBM
         S.in_buf = -1;
@@ -1324,92 +1540,83 @@ void Plan::process_stage(int sid) {
         for (auto& c : S.carriers)
             if (car_has_arr2(c)) S.rp.arr2 = 1;
         if (S.rp.arr2) S.rp.nslots = 2;  // (the A2 instantiation: one tile of look-ahead, the rest of LDS for the second array's staging rows)
-        if (S.carriers[0].pad_) {
-            // GA instantiation: Float32 tiles (pitch in floats, 16-byte rows, 128-byte aligned start),
-            // three gain arrays, no in-place work for the loaders
-            RsPeriodic& rp = S.rp;
-            const size_t avail = 160 * 1024 - sizeof(RsCtl) - 64;
-            rp.ga = S.carriers[0].pad_ >= 3 ? 2 : 1;
-            rp.lds_pitch = (int)((rp.tile_len + 31 + 8 + 3) / 4 * 4);
-            const size_t tile_bytes = (size_t)rp.ct * rp.lds_pitch * 4;
-            rp.fslots = 1;
-            // gains are indexed from the 128-byte aligned frame the tile is staged from: up to 31 frames
-            // below its first input for Float32 tiles (16 were reserved until a long-signal soak found the
-            // gains of one tile running into the array the compute waves were reading)
-            rp.fpitch = (rp.tile_len + 32 + 1) & ~1;
-            const DLeaf& L0 = leaves[S.carriers[0].slot_leaf[0]];
-            const bool two = !std::getenv("SIGOPS_RS_NOTWO") && rp.tile_len <= 64 * kRsTwoBases &&
-                             (S.carriers[0].slot_kind[0] & 0xff) == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1;
-            rp.ftwo = two ? 1 : 0;
-            const size_t fbytes = (size_t)3 * rp.fpitch * 8 + (two ? kRsTwoDoubles * 8 : 0);
-            rp.nslots = (int)std::min<size_t>(4, (avail - fbytes) / tile_bytes);
-            if (const char* ev = std::getenv("SIGOPS_RS_SLOTS")) rp.nslots = std::min(rp.nslots, std::max(2, std::atoi(ev)));
-            rp.nload = 0;
-        } else {
-        // gain ring: two LDS arrays [slots][tile frames] next to the tile ring, if at least two
-        // tile slots still fit (see k_resample_periodic)
-            RsPeriodic& rp = S.rp;
-            const int ns0 = S.carriers[0].nslots;
-            const size_t tile_bytes = (size_t)rp.ct * rp.lds_pitch * dsize(N.dtype);
-            const size_t avail = 160 * 1024 - sizeof(RsCtl) - 64;
-            const int fpitch = (rp.tile_len + 16 + 1) & ~1;
-            // slot 0 (the only one) a sine generator: the kernel's two-level evaluation (TWO)
-            bool two = !std::getenv("SIGOPS_RS_NOTWO") && rp.tile_len <= 64 * kRsTwoBases && ns0 == 1 && N.dtype == SO_F64 &&
-                       (rp.ngroups + rp.ncompute - 1) / rp.ncompute == 1;
-            if (two) {
-                const DLeaf& L0 = leaves[S.carriers[0].slot_leaf[0]];
-                two = (S.carriers[0].slot_kind[0] & 0xff) == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1;
-            }
-            const size_t fbytes = (size_t)2 * ns0 * fpitch * 8 + (two ? kRsTwoDoubles * 8 : 0);
-            if (ns0 > 0 && S.carriers[0].nsteps > 0 && !std::getenv("SIGOPS_RS_NOFRING") &&
-                fbytes + 2 * tile_bytes <= avail) {
-                rp.fslots = ns0;
-                rp.fpitch = fpitch;
-                rp.ftwo = two ? 1 : 0;
-                // the in-place multiply is vector-ALU work next to the MFMAs: keep it off the
-                // SIMDs that carry the most compute waves (10 compute waves: loaders 10,11,14,15
-                // on SIMD 2/3 copy and modify, 12,13 only keep the barrier count; measured
-                // 0.790 -> 0.780 ms on config 3, three alternating runs each)
-                if (!std::getenv("SIGOPS_RS_NLOAD")) {
-                    auto ncomp_on = [&](int w) { return (rp.ncompute - (w & 3) + 3) >> 2; };
-                    int minc = 1 << 30, cnt = 0;
-                    for (int w = rp.ncompute; w < rp.nwaves; ++w) minc = std::min(minc, ncomp_on(w));
-                    for (int w = rp.ncompute; w < rp.nwaves; ++w) cnt += ncomp_on(w) == minc;
-                    if (cnt >= 2) rp.nload = cnt;
-                }
-                rp.nslots = (int)std::min<size_t>(rp.nslots, (avail - fbytes) / tile_bytes);
-            }
-        }
+        if (S.carriers[0].pad_) size_gain_ring_ga(S);
+        else size_gain_ring(S, N.dtype);
     } else if (!direct) {
         // (a periodic resampler over `x (op) y` of two Float64 arrays in a shape its own two-array form does not take -- two
         //  channels --: K1 materialises the map, but the fused resampler + IIR kernel could read both arrays itself; keep the
         //  map as a two-array carrier for fuse_resample_sos to swap in IF it takes the stage)
-        if (S.kind == ST_RESAMPLE && S.periodic && N.dtype == SO_F64 && in_dtype == SO_F64 && N.nch % 2 == 0 && !std::getenv("SIGOPS_RSOS_NO_ARR2") &&
+        if (S.periodic && N.dtype == SO_F64 && in_dtype == SO_F64 && N.nch % 2 == 0 && !std::getenv("SIGOPS_RSOS_NO_ARR2") &&
             !std::getenv("SIGOPS_NO_ARR2")) {
             std::vector<DCarrier> alt;
             if (build_carriers(ps, N.nch, alt, false, true) && alt.size() == 1 && alt[0].nsteps == 1 && car_has_arr2(alt[0])) S.alt_carriers = alt;
         }
-        S.in_buf = new_buf(in_frames, N.nch, in_dtype);
-        S.in_pitch = -1;
-        S.in_array_node = -1;
-        S.in_offset = 0;
-        S.pw_step = emit_pointwise(ps, S.in_buf, in_dtype);
+        materialise_input(sid, ps, in_frames, N.nch, in_dtype);
     }
-    if (S.kind == ST_RESAMPLE && S.periodic && S.carriers.empty()) {
-        // plain source (direct array / stage buffer / materialised input): one 0-step carrier
-        DCarrier c{};
-        c.a = 0;
-        c.b = in_frames;
-        c.dtype = in_dtype;
-        c.array_node = S.in_array_node;
-        c.buf = S.in_array_node >= 0 ? -1 : S.in_buf;
-        c.df = S.in_offset;
-        c.cstride = S.in_array_node >= 0 ? (N.nch == 1 ? 0 : S.in_pitch) : -1;  // -1: buffer pitch
-        S.carriers.push_back(c);
+    Stage& S2 = stages[sid];  // (re-taken: the vectors may have grown)
+    if (S2.periodic && S2.carriers.empty()) S2.carriers.push_back(default_carrier(S2, in_frames, in_dtype, N.nch));
+    if (!S2.carriers.empty()) {
+        S2.car_buf = raw_buf(S2.carriers.size() * sizeof(DCarrier));
+        S2.ctl_buf = raw_buf(sizeof(RsCtl));
     }
-    if (!S.carriers.empty()) {
-        S.car_buf = raw_buf(S.carriers.size() * sizeof(DCarrier));
-        S.ctl_buf = raw_buf(sizeof(RsCtl));
+}
+
+// The carrier fusion's LDS beside the tile ring, GA instantiation: Float32 tiles (pitch in floats, 16-byte rows, 128-byte
+// aligned start), three gain arrays, no in-place work for the loaders
+void Plan::size_gain_ring_ga(Stage& S) const {
+    RsPeriodic& rp = S.rp;
+    const size_t avail = kRsLdsAvail;
+    rp.ga = S.carriers[0].pad_ >= 3 ? 2 : 1;
+    rp.lds_pitch = (int)((rp.tile_len + 31 + 8 + 3) / 4 * 4);
+    const size_t tile_bytes = (size_t)rp.ct * rp.lds_pitch * 4;
+    rp.fslots = 1;
+    // gains are indexed from the 128-byte aligned frame the tile is staged from: up to 31 frames
+    // below its first input for Float32 tiles (16 were reserved until a long-signal soak found the
+    // gains of one tile running into the array the compute waves were reading)
+    rp.fpitch = (rp.tile_len + 32 + 1) & ~1;
+    const DLeaf& L0 = leaves[S.carriers[0].slot_leaf[0]];
+    const bool two = !std::getenv("SIGOPS_RS_NOTWO") && rp.tile_len <= 64 * kRsTwoBases &&
+                     (S.carriers[0].slot_kind[0] & 0xff) == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1;
+    rp.ftwo = two ? 1 : 0;
+    const size_t fbytes = (size_t)3 * rp.fpitch * 8 + (two ? kRsTwoDoubles * 8 : 0);
+    rp.nslots = (int)std::min<size_t>(4, (avail - fbytes) / tile_bytes);
+    if (const char* ev = std::getenv("SIGOPS_RS_SLOTS")) rp.nslots = std::min(rp.nslots, std::max(2, std::atoi(ev)));
+    rp.nload = 0;
+}
+
+// ... and the other instantiations' gain ring: two LDS arrays [slots][tile frames] next to the tile ring, if at least two
+// tile slots still fit (see k_resample_periodic)
+void Plan::size_gain_ring(Stage& S, int stage_dtype) const {
+    RsPeriodic& rp = S.rp;
+    const int ns0 = S.carriers[0].nslots;
+    const size_t tile_bytes = (size_t)rp.ct * rp.lds_pitch * dsize(stage_dtype);
+    const size_t avail = kRsLdsAvail;
+    const int fpitch = (rp.tile_len + 16 + 1) & ~1;
+    // slot 0 (the only one) a sine generator: the kernel's two-level evaluation (TWO)
+    bool two = !std::getenv("SIGOPS_RS_NOTWO") && rp.tile_len <= 64 * kRsTwoBases && ns0 == 1 && stage_dtype == SO_F64 &&
+               (rp.ngroups + rp.ncompute - 1) / rp.ncompute == 1;
+    if (two) {
+        const DLeaf& L0 = leaves[S.carriers[0].slot_leaf[0]];
+        two = (S.carriers[0].slot_kind[0] & 0xff) == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1;
+    }
+    const size_t fbytes = (size_t)2 * ns0 * fpitch * 8 + (two ? kRsTwoDoubles * 8 : 0);
+    if (ns0 > 0 && S.carriers[0].nsteps > 0 && !std::getenv("SIGOPS_RS_NOFRING") &&
+        fbytes + 2 * tile_bytes <= avail) {
+        rp.fslots = ns0;
+        rp.fpitch = fpitch;
+        rp.ftwo = two ? 1 : 0;
+        // the in-place multiply is vector-ALU work next to the MFMAs: keep it off the
+        // SIMDs that carry the most compute waves (10 compute waves: loaders 10,11,14,15
+        // on SIMD 2/3 copy and modify, 12,13 only keep the barrier count; measured
+        // 0.790 -> 0.780 ms on config 3, three alternating runs each)
+        if (!std::getenv("SIGOPS_RS_NLOAD")) {
+            auto ncomp_on = [&](int w) { return (rp.ncompute - (w & 3) + 3) >> 2; };
+            int minc = 1 << 30, cnt = 0;
+            for (int w = rp.ncompute; w < rp.nwaves; ++w) minc = std::min(minc, ncomp_on(w));
+            for (int w = rp.ncompute; w < rp.nwaves; ++w) cnt += ncomp_on(w) == minc;
+            if (cnt >= 2) rp.nload = cnt;
+        }
+        rp.nslots = (int)std::min<size_t>(rp.nslots, (avail - fbytes) / tile_bytes);
     }
 }
 
@@ -1881,115 +2088,176 @@ void rsos_wproj_matrix_sos(const double* sos, int nsec, double gain, const doubl
     rsos_wproj_matrix(cf, tab, jend, ngroups, kw, M, wp, V, j0, K);
 }
 
-void Plan::fuse_resample_sos() {
-    if (std::getenv("SIGOPS_NO_RSOS")) return;
-    auto env_int = [](const char* name, int dflt) {
-        const char* ev = std::getenv(name);
-        return ev ? std::atoi(ev) : dflt;
-    };
-    for (size_t i2 = 0; i2 < stages.size(); ++i2) {
-        Stage& S2 = stages[i2];
-        if (S2.kind != ST_SOS || S2.onepass || S2.need <= 0 || S2.groups.size() != 1 || S2.groups[0].nsec > 6 ||
-            S2.in_buf < 0 || S2.in_array_node >= 0 || S2.in_offset != S2.base || S2.pw_step >= 0 || S2.sg.exact || (S2.xscan && !S2.under_norm) ||
-            (S2.under_norm && (S2.norm_df != 0 || S2.base != 0 || std::getenv("SIGOPS_NORM_EXACT_FILT"))) || S2.src_op || S2.batch >= 0 || S2.pre_stage >= 0 ||
-            (nodes[S2.node].dtype != SO_F64 && nodes[S2.node].dtype != SO_F32) || S2.in_frames != S2.need - S2.base)
-            continue;  // (below a Normpower: only where its region starts at the filter's first frame -- fuse_plain_sos, Stage::norm_df)
-        // A Float32 signal all the way (Float32 source, resampler and filter stages): the kernel rounds the resampled values to
-        // Float32 where the reference's resampler stores them (RsSos::x32) and stores a Float32 result; its sources are plain
-        // Float32 arrays or buffers (a Float32 x Float32 step rounds too: K1 materialises it)
-        const bool pure32 = nodes[S2.node].dtype == SO_F32;
-        if (pure32 && std::getenv("SIGOPS_RSOS_NO32")) continue;
-        if (S2.base > 0 && std::getenv("SIGOPS_RSOS_NOWINDOWS")) continue;
-        int i3 = -1;
-        for (size_t j = 0; j < stages.size(); ++j)
-            if (stages[j].kind == ST_RESAMPLE && stages[j].out_buf == S2.in_buf) i3 = (int)j;
-        if (i3 < 0 || i3 == alias_stage || stages[i3].win_off >= 0) continue;
-        Stage& S3 = stages[i3];
-        const RsPeriodic& rp = S3.rp;
-        // A window (After, a block of so.stream, a rank's time range): both stages are warm-started -- the cascade a decay
-        // time before the window (S2.base), the resampler a few periods before that (S3.base, whole periods).  The fused
-        // kernel's coordinates are the resampler stage's: its output 0 is frame S3.base, the cascade starts from rest
-        // there (earlier than the cascade stage alone would: a longer warm-up), and nothing below S2.base is stored.
-        if (S3.base > S2.base) continue;
-        if (rp.nstate || nodes[S3.node].dtype != nodes[S2.node].dtype || !S3.fix_host.empty() || S3.need < S2.need || (int)S3.carriers.size() > kCtlCar)
-            continue;
-        // (arr2: a source of two arrays -- K3's A2 instantiation's alone; this kernel's loader takes the second one for groups of
-        //  two, four or eight channels, Float64, ONE carrier whose one step is `v (op) y`: k_rsos.hip, rsos_loader's A2)
-        // ... also where K1 materialises the map for K3 (Stage::alt_carriers): tried with the two-array carrier in place of the
-        // materialised buffer's; whatever makes this stage `continue` below puts K1's step and the buffer's carrier back
-        struct AltGuard {
-            Stage& S;
-            std::vector<DCarrier> car;
-            int pw;
-            bool armed;
-            ~AltGuard() {
-                if (armed) {
-                    S.carriers = car;
-                    S.pw_step = pw;
-                }
+// ---------------------------------------------------------------------------
+// what the two one-pass forms of k_rsos (fuse_resample_sos, fuse_plain_sos) decide the same way
+
+// First wp with ||(A^L)^wp|| < tol: the periods of L frames after which what a state held has decayed below tol.
+// 0: it does not (an unstable cascade, a pole too close to the unit circle).
+static int64_t warmup_periods(const SosCoefs& cf, int64_t L, double tol) {
+    const int D = 2 * cf.nsec;
+    int64_t wp = 1;
+    const Mat P = matpow(sos_state_matrix(cf), L, D);
+    Mat cur = P;
+    while (!(maxabs(cur) < tol) && wp < 1000000 && std::isfinite(maxabs(cur))) {
+        cur = matmul(cur, P, D);
+        ++wp;
+    }
+    return maxabs(cur) < tol ? wp : 0;
+}
+
+// Rows of a sequence group -- ct channels x rgs ranges -- and the ranges a signal of `nperiods` periods is cut into: one
+// sequence group per CU (the last wave of groups of a longer grid would run on a draining machine), fewer where a range
+// would otherwise be shorter than `min_pr` periods.  Where the two forms differ:
+//   gpm > 0 (plain form): a member of a batched launch with gpm workgroups of its own -- false where it has more channel
+//     groups than that; SIGOPS_RSOS_RANGES applies to launches of their own only (gpm == 0).
+//   align_M > 0 (resampler form, M input frames per period): groups of fewer than eight channels walk several ranges side
+//     by side: where a range is a multiple of 16 input frames long all of them stage their chunks at the same alignment and
+//     the loader addresses its units by scalar additions (k_rsos.hip, the loader's `klo_all`): a few periods more per
+//     range, fewer ranges.
+struct RsosRanges {
+    int ct = 1, rgs = 16;
+    int64_t ncg = 0, nranges = 0, pr = 0, ngrp = 0;
+};
+static bool rsos_ranges(int nch, int64_t nperiods, int64_t min_pr, int gpm, int cus, int64_t align_M, RsosRanges& R) {
+    R.ct = channels_per_group(nch, 16);
+    R.rgs = 16 / R.ct;
+    R.ncg = nch / R.ct;
+    if (gpm > 0 && R.ncg > gpm) return false;
+    const int64_t rgroups = gpm > 0 ? gpm / R.ncg : std::max<int64_t>(1, cus / R.ncg);  // range groups per channel group
+    int64_t nranges = rgroups * R.rgs;
+    if (nperiods / nranges < min_pr) nranges = std::max<int64_t>(R.rgs, nperiods / min_pr / R.rgs * R.rgs);
+    if (const char* ev = std::getenv("SIGOPS_RSOS_RANGES"))
+        if (gpm == 0) nranges = std::max<int64_t>(1, std::atoll(ev));
+    R.pr = (nperiods + nranges - 1) / nranges;
+    if (align_M > 0 && R.ct < 8 && !std::getenv("SIGOPS_RSOS_NOALIGNPR")) {
+        const int64_t mlt = 16 / std::__gcd<int64_t>(align_M % 16 == 0 ? 16 : align_M % 16, 16);
+        if (R.pr % mlt != 0 && R.pr >= 8 * mlt) R.pr = (R.pr + mlt - 1) / mlt * mlt;
+    }
+    R.nranges = (nperiods + R.pr - 1) / R.pr;
+    R.ngrp = R.ncg * ((R.nranges + R.rgs - 1) / R.rgs);
+    return true;
+}
+
+// frames of the input ring: as many as fit next to the tap table (if any) and the exchange slots (below 128: none do)
+static int rsos_ring_frames(const RsSos& g) {
+    int ring = 4096;  // (a multiple of 128: whole chunks, and rows of ring + 2 doubles fall on different banks)
+    while (ring >= 128 && rsos_lds_bytes(g.ngroups, g.ks, ring + 2, g.nwaves, g.cyc) > rsos_lds_budget()) ring -= 128;
+    if (const char* ev = std::getenv("SIGOPS_RSOS_RING")) ring = std::min(ring, std::max(128, std::atoi(ev) / 128 * 128));
+    return ring;
+}
+
+// carrier 0's step on the loader's fast path: RsSos::fuse (-1 none, 0 multiply, 1 add, 2 / 3 subtract / reversed, -2: every
+// chunk takes the general staging path), fuse_sine (the operand is one sine generator) and arr2 (... a second array)
+void Plan::rsos_fuse_step(const DCarrier& c0, bool two_arrays, RsSos& g) const {
+    g.fuse = -1;
+    if (two_arrays) {
+        g.fuse = c0.op[0] == OP_MUL ? 0 : c0.op[0] == OP_ADD ? 1 : ((c0.arg[0] & 0x100) ? 3 : 2);
+        g.fuse_sine = 0;
+        g.arr2 = 1;
+    } else if (c0.nsteps == 1 && (c0.arg[0] & 0x2ff) == 0 && c0.nslots >= 1 &&
+               (c0.op[0] == OP_MUL || c0.op[0] == OP_ADD || c0.op[0] == OP_SUB)) {
+        g.fuse = c0.op[0] == OP_MUL ? 0 : c0.op[0] == OP_ADD ? 1 : ((c0.arg[0] & 0x100) ? 3 : 2);
+        const DLeaf& L0 = leaves[c0.slot_leaf[0]];
+        const int kind = c0.slot_kind[0];
+        if (kind == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1) g.fuse_sine = 1;
+        else if (kind == OP_CONST || kind == OP_SCALAR) g.fuse_sine = 0;
+        else g.fuse = -2;
+    } else if (c0.nsteps > 0)
+        g.fuse = -2;
+}
+
+// A filter stage S2 and the resampler stage S3 whose output it alone reads, on their way to ONE launch of k_rsos (fuse_resample_sos).
+// Each decision returns whether the fusion goes on and leaves what it settled in the members; the first that declines leaves
+// both stages as they were (`alt`).
+struct RsosFusion : RsosRanges {
+    Plan& P;
+    std::vector<Node>& nodes;
+    std::vector<Stage>& stages;
+    std::vector<DLeaf>& leaves;
+    const size_t i2;
+    const int i3;
+    Stage &S2, &S3;
+    const RsPeriodic& rp;
+    const bool pure32;
+    // (arr2: a source of two arrays -- K3's A2 instantiation's alone; this kernel's loader takes the second one for groups of
+    //  two, four or eight channels, Float64, ONE carrier whose one step is `v (op) y`: k_rsos.hip, rsos_loader's A2)
+    // ... also where K1 materialises the map for K3 (Stage::alt_carriers): tried with the two-array carrier in place of the
+    // materialised buffer's; whatever makes the fusion decline puts K1's step and the buffer's carrier back
+    struct AltGuard {
+        Stage& S;
+        std::vector<DCarrier> car;
+        int pw;
+        bool armed;
+        ~AltGuard() {
+            if (armed) {
+                S.carriers = car;
+                S.pw_step = pw;
             }
-        } alt{S3, S3.carriers, S3.pw_step, false};
+        }
+    } alt;
+    bool two_arrays = false, plain_src = false, was_ga = false, own_tab = false, blocks_ok = false;
+    int64_t Lp, Mp;  // the period the kernel walks, in outputs and inputs
+    int ngp, kwp, jlop, ks = 0;
+    std::vector<double> own_taps;
+    std::vector<int> own_jend;
+    std::vector<int64_t> own_jr;  // (newest input of every output of the own table's super-period)
+    int nch = 0, cus = 0;
+    int64_t need = 0, L = 0, store_lo = 0, wp = 0;
+    RsSos g{};
+    RsosFusion(Plan& P_, size_t i2_, int i3_)
+        : P(P_), nodes(P_.nodes), stages(P_.stages), leaves(P_.leaves), i2(i2_), i3(i3_), S2(P_.stages[i2_]), S3(P_.stages[i3_]), rp(S3.rp),
+          pure32(nodes[S2.node].dtype == SO_F32), alt{S3, S3.carriers, S3.pw_step, false}, Lp(rp.L), Mp(rp.M), ngp(rp.ngroups), kwp(rp.kw), jlop(rp.jlo) {}
+
+    bool source_form() {
         if (!rp.arr2 && !S3.alt_carriers.empty() && S3.pw_step >= 0 && S3.in_buf >= 0 && !std::getenv("SIGOPS_RSOS_NO_ARR2")) {
             S3.carriers = S3.alt_carriers;
             S3.pw_step = -1;
             alt.armed = true;
         }
-        bool two_arrays = false;
         if (rp.arr2 || alt.armed) {
             const bool ok = !pure32 && nodes[S2.node].dtype == SO_F64 && S3.carriers.size() == 1 && S3.carriers[0].nsteps == 1 &&
                             (S3.carriers[0].arg[0] & kCarArr2) && !(S3.carriers[0].arg[0] & 0x200) && S3.carriers[0].dtype == SO_F64 &&
                             S3.carriers[0].dtype2 == SO_F64 && nodes[S2.node].nch % 2 == 0 &&
                             (S3.carriers[0].op[0] == OP_ADD || S3.carriers[0].op[0] == OP_SUB || S3.carriers[0].op[0] == OP_MUL) &&
                             !std::getenv("SIGOPS_RSOS_NO_ARR2");
-            if (!ok) continue;
+            if (!ok) return false;
             two_arrays = true;
         }
         if (pure32) {
             bool plain = nodes[nodes[S3.node].kids[0]].dtype == SO_F32 && rp.ga == 0;
             for (auto& c : S3.carriers)
                 if (c.nsteps != 0 || c.pad_ != 0 || c.dtype != SO_F32) plain = false;
-            if (!plain) continue;
+            if (!plain) return false;
         }
         // (a stage that does not run the periodic kernel -- long super-periods: x 2 of eight channels -- has no carriers:
         //  its plain source, an array or a stage buffer, becomes one below)
-        const bool plain_src = S3.carriers.empty() && (S3.in_buf >= 0 || S3.in_array_node >= 0);
-        if (S3.carriers.empty() && !plain_src) continue;
+        plain_src = S3.carriers.empty() && (S3.in_buf >= 0 || S3.in_array_node >= 0);
+        return !S3.carriers.empty() || plain_src;
+    }
+
+    bool own_table() {
         // The period the kernel walks: blocks of 16 outputs, each with its own [k-steps x 16] tap operand.  The resampler
         // stage's own (44.1 -> 48 kHz: 160 outputs, ten blocks) where it splits into whole blocks -- or, for the small
         // rational ratios (x 2, x 3, x 3/2 ...: DSP.jl's FIRInterpolator / FIRRational, reference src/reformatting.jl:103-111)
         // whose stage runs on super-periods sized for K3's tiles, the shortest super-period of whole blocks, with a tap
         // table of this stage's own.
-        int64_t Lp = rp.L, Mp = rp.M;
-        int ngp = rp.ngroups, kwp = rp.kw, jlop = rp.jlo;
-        bool own_tab = false;
-        std::vector<double> own_taps;
-        std::vector<int> own_jend;
-        std::vector<int64_t> own_jr;  // (newest input of every output of the own table's super-period)
-        const bool blocks_ok = S3.periodic && Lp > 0 && Lp % 16 == 0 && (int64_t)ngp * 16 == Lp && ngp <= 256;
+        blocks_ok = S3.periodic && Lp > 0 && Lp % 16 == 0 && (int64_t)ngp * 16 == Lp && ngp <= 256;
         if (!S3.rg.arbitrary && (!blocks_ok || ngp > 10) && !std::getenv("SIGOPS_RSOS_NOOWNTAB")) {
             const RsGeom& rg = S3.rg;
             const so_node_t& nd3 = nodes[S3.node].nd;
             const double* h = (const double*)nd3.p0;
             const int hlen = nd3.i2;
             const int64_t tmin = 16 / std::__gcd<int64_t>(rg.L, 16);
-            bool found = false;
             for (int64_t m : {1, 2, 3, 5}) {
                 const int64_t Ls = rg.L * tmin * m, Ms = rg.M * tmin * m;
                 const int ng = (int)(Ls / 16);
                 if (Ls > 4096 || (ng != 1 && ng != 2 && ng != 3 && ng != 5 && ng != 6 && ng != 10)) continue;
-                std::vector<int64_t> jr((size_t)Ls);
-                std::vector<int> prr((size_t)Ls);
-                for (int64_t r = 0; r < Ls; ++r) {
-                    const int64_t qi = rg.c0i + r * rg.M;  // (rational: nphi == L, no interpolation between phases)
-                    jr[(size_t)r] = qi / rg.nphi;
-                    prr[(size_t)r] = (int)(qi % rg.nphi);
-                }
-                std::vector<int> jend((size_t)ng);
-                int64_t maxspan = 0;
-                for (int gi = 0; gi < ng; ++gi) {
-                    jend[(size_t)gi] = (int)jr[(size_t)gi * 16 + 15];
-                    maxspan = std::max(maxspan, jr[(size_t)gi * 16 + 15] - jr[(size_t)gi * 16]);
-                }
+                // (rational: nphi == L, no interpolation between phases, and no accumulator ties: the closed form)
+                PeriodPos pos = period_positions(rg, Ls, nullptr);
+                const std::vector<int64_t>& jr = pos.j;
+                GroupWindows win = group_windows(jr, Ls);
+                std::vector<int>& jend = win.jend;
+                const int64_t maxspan = win.maxspan;
                 const int ksneed = (int)((rg.taps + maxspan + 3) / 4);
                 int ksc = 0;
                 for (int k : {12, 14, 16, 20})
@@ -1999,18 +2267,8 @@ void Plan::fuse_resample_sos() {
                                  (long long)rg.L, (long long)rg.M, (long long)(tmin * m), ng, rg.taps, (long long)maxspan, ksneed, ksc);
                 if (!ksc) break;  // (a longer super-period does not shorten the windows)
                 const int kw = 4 * ksc;
-                int jlo = jend[0] - (kw - 1);
-                jlo -= ((jlo % 4) + 4) % 4;
-                std::vector<double> tab((size_t)ng * kw * 16, 0.0);
-                for (int gi = 0; gi < ng; ++gi)
-                    for (int rr = 0; rr < 16; ++rr)
-                        for (int kk = 0; kk < kw; ++kk) {
-                            const int64_t r = (int64_t)gi * 16 + rr;
-                            const int64_t age = jr[(size_t)r] - ((int64_t)jend[(size_t)gi] - (kw - 1) + kk);
-                            if (age < 0 || age >= rg.taps) continue;
-                            const int64_t hi = prr[(size_t)r] + (int64_t)rg.nphi * age;
-                            tab[((size_t)gi * kw + kk) * 16 + rr] = hi < hlen ? h[hi] : 0.0;
-                        }
+                const int jlo = aligned_window_start(jend[0], kw);
+                std::vector<double> tab = fill_tap_blocks(jr, Ls, jend, kw, rg.taps, [&](int64_t r, int64_t age) { return tap(h, hlen, rg.nphi, pos.p[(size_t)r], age).hv; });
                 Lp = Ls;
                 Mp = Ms;
                 ngp = ng;
@@ -2018,14 +2276,17 @@ void Plan::fuse_resample_sos() {
                 jlop = jlo;
                 own_taps.swap(tab);
                 own_jend.swap(jend);
-                own_jr = jr;
-                own_tab = found = true;
+                own_jr.swap(pos.j);
+                own_tab = true;
                 break;
             }
-            (void)found;
         }
-        if (!own_tab && (!blocks_ok || !S3.periodic)) continue;
-        if (S3.base % Lp != 0 || Mp >= (1 << 20)) continue;
+        if (!own_tab && (!blocks_ok || !S3.periodic)) return false;
+        return S3.base % Lp == 0 && Mp < (1 << 20);
+    }
+
+    // false: a window length k_rsos is not instantiated for
+    bool trim_table() {
         // The resampler stage's table has the k-steps of K3's instantiations (12, 14, 16 ...); its windows end at the
         // group's newest input, so what a group does not need are its OLDEST slots.  Where every group's first slots are
         // zero the fused kernel takes a shorter window from the same table -- 44.1 -> 48 kHz: 38 taps + a span of 14
@@ -2060,13 +2321,16 @@ void Plan::fuse_resample_sos() {
                                  (kw + drop) / 4);
             }
         }
-        const int ks = kwp / 4;
-        if (!(ks == 12 || ks == 13 || ks == 14 || ks == 16 || ks == 20)) continue;  // (the window lengths k_rsos is instantiated for)
+        ks = kwp / 4;
+        return ks == 12 || ks == 13 || ks == 14 || ks == 16 || ks == 20;  // (the window lengths k_rsos is instantiated for)
+    }
+
+    bool sole_reader() {
         bool ok = true;
         // GA carriers (a Float32 array whose Float64 gain or summand K3's compute waves apply at the MFMA operand): this
         // kernel's loader widens the landed Float32 chunk in place and applies the step on the way, so the carriers go
         // back to their plain form below -- array + one step, generated pieces that load the operand
-        const bool was_ga = rp.ga != 0;
+        was_ga = rp.ga != 0;
         for (auto& c : S3.carriers)
             if ((c.pad_ != 0) != was_ga) ok = false;
         if (was_ga && std::getenv("SIGOPS_RSOS_NO32")) ok = false;
@@ -2079,57 +2343,30 @@ void Plan::fuse_resample_sos() {
                 for (auto& c : stages[j].carriers)
                     if (c.buf == S2.in_buf) ok = false;
         }
-        if (!ok) continue;
+        return ok;
+    }
+
+    bool warmup_and_ranges() {
         const SosCoefs& cf = S2.groups[0];
-        const int D = 2 * cf.nsec;
-        const int nch = nodes[S2.node].nch;
-        const int64_t need = S2.need - S3.base, L = Lp;
-        const int64_t store_lo = S2.base - S3.base;
+        nch = nodes[S2.node].nch;
+        need = S2.need - S3.base, L = Lp;
+        store_lo = S2.base - S3.base;
         const int64_t nperiods = (need + L - 1) / L;
         // warm-up: the first wp with ||A^(wp L)|| < 2^-56: what the frames in front of the warm-up leave in the state is an
         // eighth of the state's own rounding unit (2^-53) by the time the range's first output is stored -- below anything
         // the 50-term MFMA sums of a block can resolve.  (Round 4 cut at 2^-70 like the warm starts of windows, whose
         // results are compared with cold starts at 1e-13: 27 periods instead of 22 for the headline's band-stop, 1.3 % of
         // all blocks.  SIGOPS_RSOS_WTOL: another exponent.)
-        int64_t wp = 1;
-        {
-            const double tol = std::ldexp(1.0, -std::abs(env_int("SIGOPS_RSOS_WTOL", S2.under_norm ? 70 : 56)));  // (below a Normpower: the plain form's cut)
-            const Mat P = matpow(sos_state_matrix(cf), L, D);
-            Mat cur = P;
-            while (!(maxabs(cur) < tol) && wp < 1000000 && std::isfinite(maxabs(cur))) {
-                cur = matmul(cur, P, D);
-                ++wp;
-            }
-            if (!(maxabs(cur) < tol)) continue;
-        }
-        // rows of a sequence group: ct channels x rgs ranges
-        int ct = 1;
-        for (int c : {16, 8, 4, 2})
-            if (nch % c == 0) {
-                ct = c;
-                break;
-            }
-        const int rgs = 16 / ct;
-        const int64_t ncg = nch / ct;
-        // ranges: one sequence group per CU (the last wave of groups of a longer grid would run on a draining machine),
-        // fewer where a range would otherwise be shorter than its own warm-up
-        const int cus = env_int("SIGOPS_RSOS_GRID", 256);
-        int64_t rgroups = std::max<int64_t>(1, cus / ncg);  // range groups per channel group
-        int64_t nranges = rgroups * rgs;
-        const int64_t min_pr = std::max<int64_t>(1, wp);
-        if (nperiods / nranges < min_pr) nranges = std::max<int64_t>(rgs, nperiods / min_pr / rgs * rgs);
-        if (const char* ev = std::getenv("SIGOPS_RSOS_RANGES")) nranges = std::max<int64_t>(1, std::atoll(ev));
-        int64_t pr = (nperiods + nranges - 1) / nranges;
-        // groups of fewer than eight channels walk several ranges side by side: where a range is a multiple of 16 input frames long
-        // all of them stage their chunks at the same alignment and the loader addresses its units by scalar additions
-        // (k_rsos.hip, the loader's `klo_all`): a few periods more per range, fewer ranges
-        if (ct < 8 && !std::getenv("SIGOPS_RSOS_NOALIGNPR")) {
-            const int64_t mlt = 16 / std::__gcd<int64_t>(Mp % 16 == 0 ? 16 : Mp % 16, 16);
-            if (pr % mlt != 0 && pr >= 8 * mlt) pr = (pr + mlt - 1) / mlt * mlt;
-        }
-        nranges = (nperiods + pr - 1) / pr;
-        const int64_t ngrp = ncg * ((nranges + rgs - 1) / rgs);
-        if ((pr + wp) * ngp >= (1 << 30) || (pr + wp) * Mp >= ((int64_t)1 << 30)) continue;
+        const double wtol = std::ldexp(1.0, -std::abs(env_int("SIGOPS_RSOS_WTOL", S2.under_norm ? 70 : 56)));  // (below a Normpower: the plain form's cut)
+        wp = warmup_periods(cf, L, wtol);
+        if (!wp) return false;
+        // ranges, none shorter than its own warm-up
+        cus = env_int("SIGOPS_RSOS_GRID", 256);
+        rsos_ranges(nch, nperiods, std::max<int64_t>(1, wp), 0, cus, Mp, *this);
+        return (pr + wp) * ngp < (1 << 30) && (pr + wp) * Mp < ((int64_t)1 << 30);
+    }
+
+    bool worth_it() const {
         // Worth it?  A workgroup walks its (pr + wp) periods block by block -- 0.30 us per block of 16 outputs x 16 rows
         // with 14 k-step windows -- however few workgroups there are, while the two kernels use the whole chip for any
         // length: 8 ps per output sample + 95 us of launches, scans and tails (tools/rsos_len_sweep.sh, 8 channels at
@@ -2137,7 +2374,7 @@ void Plan::fuse_resample_sos() {
         // 0.306 / 0.710).  Short signals and short windows keep the two kernels (8 channels: below ~30 s).
         // SIGOPS_RSOS_MINGROUPS=n replaces the estimate by "at least n sequence groups" (tests, measurements).
         if (const char* ev = std::getenv("SIGOPS_RSOS_MINGROUPS")) {
-            if (ngrp < std::atoll(ev)) continue;
+            if (ngrp < std::atoll(ev)) return false;
         } else {
             // (groups of fewer than eight channels have 4, 8 or 16 loader units per chunk instead of 2, each with its own
             //  lane-table reads next to the chain wave's MFMAs: the loader sets the pace there -- 1e8 samples: 0.65 ms
@@ -2164,9 +2401,14 @@ void Plan::fuse_resample_sos() {
             if (std::getenv("SIGOPS_DEBUG_PLAN"))
                 std::fprintf(stderr, "[sigops] k_rsos estimate: fused %.0f us (%lld groups, %lld + %lld periods), two kernels %.0f us\n", t_fused,
                              (long long)ngrp, (long long)pr, (long long)wp, t_two);
-            if (t_fused > t_two) continue;
+            if (t_fused > t_two) return false;
         }
-        RsSos g{};
+        return true;
+    }
+
+    // the launch geometry so far, and the waves; false: a combination launch_rsos_t does not instantiate
+    bool waves() {
+        const SosCoefs& cf = S2.groups[0];
         g.n_in = S3.rg.n_in;
         g.n_out = need;
         g.store_lo = store_lo;
@@ -2215,7 +2457,7 @@ void Plan::fuse_resample_sos() {
             if (const char* ev = std::getenv("SIGOPS_RSOS_NWAVES")) nw = std::atoi(ev) == 8 ? 8 : (std::atoi(ev) == 16 || std::atoi(ev) == 17) && cyc_of(16) == 1 && ks <= 16 ? std::atoi(ev) : 12;
             // (a source of two arrays: the second one goes through the registers of the sixteen-wave geometry's two step waves)
             if (two_arrays) {
-                if (!(cyc_of(16) == 1 && ks <= 16)) continue;
+                if (!(cyc_of(16) == 1 && ks <= 16)) return false;
                 nw = 16;
             }
             g.nwaves = nw;
@@ -2225,35 +2467,33 @@ void Plan::fuse_resample_sos() {
             const bool inst = nw == 12 ? (g.cyc == 0 || g.cyc == 1 || (g.cyc == 2 && ks <= 16))
                             : nw >= 16 ? g.cyc == 1
                                        : (g.cyc == 0 || g.cyc == 1 || g.cyc == 2 || (g.cyc == 3 && ks <= 20) || (g.cyc == 5 && ks <= 16));
-            if (!inst) continue;
+            return inst;
         }
-        // input ring: as large as fits next to the tap table (if any) and the exchange slots
+    }
+
+    // input ring: as large as fits next to the tap table (if any) and the exchange slots
+    bool ring() {
         {
             const int ny = g.nwaves >= 16 ? 10 : g.nwaves - 2;
             // (a y wave's front part runs up to one of its own blocks ahead: the windows in use span 2 ny - 1 blocks)
             const int64_t span = (int64_t)(2 * ny - 1) * ((16 * Mp + L - 1) / L + 1) + kwp + 16 + 2 * g.chunk;
-            int ring = 4096;  // (a multiple of 128: whole chunks, and rows of ring + 2 doubles fall on different banks)
-            while (ring >= 128 && rsos_lds_bytes(g.ngroups, ks, ring + 2, g.nwaves, g.cyc) > rsos_lds_budget()) ring -= 128;
-            if (const char* ev = std::getenv("SIGOPS_RSOS_RING")) ring = std::min(ring, std::max(128, std::atoi(ev) / 128 * 128));
+            const int ring = rsos_ring_frames(g);
             if (std::getenv("SIGOPS_DEBUG_PLAN"))
                 std::fprintf(stderr, "[sigops] k_rsos: ring %d frames (needs %lld), LDS %zu of %zu\n", ring, (long long)span,
                              rsos_lds_bytes(g.ngroups, ks, ring + 2, g.nwaves, g.cyc), rsos_lds_budget());
-            if (ring < 128 || ring < span) continue;
+            if (ring < 128 || ring < span) return false;
             g.ring = ring;
             g.rpitch = ring + 2;
         }
+        return true;
+    }
+
+    // the resampler stage's carriers as this kernel's loader reads them, and what of the geometry follows from them
+    void rewrite_carriers() {
         if (plain_src) {
-            DCarrier c{};
-            c.a = 0;
-            c.b = S3.in_frames;
-            c.dtype = nodes[nodes[S3.node].kids[0]].dtype == SO_F32 ? SO_F32 : SO_F64;
-            c.array_node = S3.in_array_node;
-            c.buf = S3.in_array_node >= 0 ? -1 : S3.in_buf;
-            c.df = S3.in_offset;
-            c.cstride = S3.in_array_node >= 0 ? (nch == 1 ? 0 : S3.in_pitch) : -1;  // -1: buffer pitch
-            S3.carriers.push_back(c);
-            S3.car_buf = raw_buf(sizeof(DCarrier));
-            S3.ctl_buf = raw_buf(sizeof(RsCtl));
+            S3.carriers.push_back(default_carrier(S3, S3.in_frames, nodes[nodes[S3.node].kids[0]].dtype == SO_F32 ? SO_F32 : SO_F64, nch));
+            S3.car_buf = P.raw_buf(sizeof(DCarrier));
+            S3.ctl_buf = P.raw_buf(sizeof(RsCtl));
         }
         if (was_ga) {
             for (size_t i = 0; i < S3.carriers.size(); ++i) {
@@ -2267,25 +2507,7 @@ void Plan::fuse_resample_sos() {
         } else
             g.src32 = S3.carriers[0].dtype == SO_F32 && S3.carriers[0].nsteps == 0 ? 1 : 0;
         g.x32 = pure32 ? 1 : 0;
-        // carrier 0's step on the fast path
-        {
-            const DCarrier& c0 = S3.carriers[0];
-            g.fuse = -1;
-            if (two_arrays) {
-                g.fuse = c0.op[0] == OP_MUL ? 0 : c0.op[0] == OP_ADD ? 1 : ((c0.arg[0] & 0x100) ? 3 : 2);
-                g.fuse_sine = 0;
-                g.arr2 = 1;
-            } else if (c0.nsteps == 1 && (c0.arg[0] & 0x2ff) == 0 && c0.nslots >= 1 &&
-                (c0.op[0] == OP_MUL || c0.op[0] == OP_ADD || c0.op[0] == OP_SUB)) {
-                g.fuse = c0.op[0] == OP_MUL ? 0 : c0.op[0] == OP_ADD ? 1 : ((c0.arg[0] & 0x100) ? 3 : 2);
-                const DLeaf& L0 = leaves[c0.slot_leaf[0]];
-                const int kind = c0.slot_kind[0];
-                if (kind == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1) g.fuse_sine = 1;
-                else if (kind == OP_CONST || kind == OP_SCALAR) g.fuse_sine = 0;
-                else g.fuse = -2;
-            } else if (c0.nsteps > 0)
-                g.fuse = -2;  // (every chunk takes the general staging path)
-        }
+        P.rsos_fuse_step(S3.carriers[0], two_arrays, g);  // carrier 0's step on the fast path
         g.gsplit = g.nwaves == 16 && !g.src32 && g.fuse >= 0 && (g.arr2 || ((ct == 2 || ct == 4) && !std::getenv("SIGOPS_RSOS_NOGSPLIT"))) ? 1 : 0;
         g.ring32 = g.src32 && g.fuse == -1 && pure32 && !std::getenv("SIGOPS_RSOS_NO_RING32") ? 1 : 0;  // (no step: the ring keeps the Float32 samples)
         // A Float32 array -- with or without the fast path's one step -- into a Float32 RESULT (known at execute time: the stage
@@ -2297,9 +2519,14 @@ void Plan::fuse_resample_sos() {
         // profiles/r06/relerr_maxima_rsos_f32m.json: worst 1.5e-7; gate 3e-7), SIGOPS_RSOS_NO_F32MFMA=1 keeps the Float64 products.
         g.help = g.nwaves == 17 ? 1 : 0;
         g.f32m = g.src32 && g.fuse >= -1 && g.cyc > 0 && !std::getenv("SIGOPS_RSOS_NO_F32MFMA") && !std::getenv("SIGOPS_RSOS_NO_RING32") ? 1 : 0;
+    }
+
+    // taken: the filter stage gets the geometry, the tables and the buffers of the launch, the resampler stage is `fused_away`
+    void commit() {
+        const SosCoefs& cf = S2.groups[0];
         S2.rs = g;
         S2.rsos_src = i3;
-        S2.carriers.clear();  // (what process_stage prepared for the single-pass form of a plain filter: the resampler's serve now)
+        S2.carriers.clear();  // (what bind_sos_input prepared for the single-pass form of a plain filter: the resampler's serve now)
         {  // what k_rsos_fixup needs to recompute single outputs the reference's way
             const std::vector<int64_t>& jr = own_jr.empty() ? S3.per_j : own_jr;
             const std::vector<int>& je = own_tab ? own_jend : S3.jend_host;
@@ -2307,18 +2534,23 @@ void Plan::fuse_resample_sos() {
             if ((int64_t)jr.size() >= Lp && (int64_t)je.size() >= ngp) {
                 S2.rsos_jrel_host.resize((size_t)Lp);
                 for (int64_t r = 0; r < Lp; ++r) S2.rsos_jrel_host[(size_t)r] = (int)(jr[(size_t)r] - je[(size_t)(r / 16)]);
-                S2.rsos_jrel_buf = raw_buf(S2.rsos_jrel_host.size() * 4);
+                S2.rsos_jrel_buf = P.raw_buf(S2.rsos_jrel_host.size() * 4);
                 S2.rsos_taps = S3.rg.taps;
             }
         }
         if (own_tab) {
             S2.rsos_tab_host.swap(own_taps);
             S2.rsos_jend_host.swap(own_jend);
-            S2.rsos_tab_buf = raw_buf(S2.rsos_tab_host.size() * 8);
-            S2.rsos_jend_buf = raw_buf(S2.rsos_jend_host.size() * 4);
+            S2.rsos_tab_buf = P.raw_buf(S2.rsos_tab_host.size() * 8);
+            S2.rsos_jend_buf = P.raw_buf(S2.rsos_jend_host.size() * 4);
         }
         S2.rsos_grid = (int)std::min<int64_t>(ngrp, cus);
         rsos_block_matrices(cf, S2.rsos_mats_host);
+    }
+
+    // appends to the filter stage's rsos_mats_host; sets RsSos::wproj / wk / wj0
+    void wproj_tables() {
+        const SosCoefs& cf = S2.groups[0];
         // The warm-up of a range as ONE product (rsos_wproj_matrix above; k_rsos.hip, rsos_wproj_*) instead of wp periods of the
         // block walk: a Float64 ARRAY on the loader's fast path (not a stage buffer: what K1 materialised for this kernel takes the
         // path the two-array form of the same tree takes -- their results are compared bit for bit), plain or `v +- one sine`, groups of 8 or 16 channels, the
@@ -2373,12 +2605,15 @@ void Plan::fuse_resample_sos() {
                                  (long long)(wp * ngp));
             }
         }
-        S2.rsos_mats_buf = raw_buf(S2.rsos_mats_host.size() * 8);
-        if (S2.bad_buf < 0) S2.bad_buf = raw_buf((size_t)nch * 4);  // first range per channel that ended in a non-finite state
+    }
+
+    void commit_launch() {
+        S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
+        if (S2.bad_buf < 0) S2.bad_buf = P.raw_buf((size_t)nch * 4);  // first range per channel that ended in a non-finite state
         S3.fused_away = true;
         if (alt.armed) {  // (K1's copy of `x (op) y` is never made: its step is not in the plan, its buffer holds nothing)
             alt.armed = false;
-            bufs[S3.in_buf].bytes = 0;
+            P.bufs[S3.in_buf].bytes = 0;
         }
         if (std::getenv("SIGOPS_DEBUG_PLAN"))
             std::fprintf(stderr,
@@ -2387,6 +2622,45 @@ void Plan::fuse_resample_sos() {
                          (long long)nranges, (long long)pr, (long long)wp, (long long)ngrp, ct, rgs, ks, g.ring, g.chunk, g.nwaves, g.cyc,
                          g.fuse, g.fuse_sine);
     }
+};
+
+void Plan::fuse_resample_sos() {
+    if (std::getenv("SIGOPS_NO_RSOS")) return;
+    for (size_t i2 = 0; i2 < stages.size(); ++i2) {
+        Stage& S2 = stages[i2];
+        if (S2.kind != ST_SOS || S2.onepass || S2.need <= 0 || S2.groups.size() != 1 || S2.groups[0].nsec > 6 ||
+            S2.in_buf < 0 || S2.in_array_node >= 0 || S2.in_offset != S2.base || S2.pw_step >= 0 || S2.sg.exact || (S2.xscan && !S2.under_norm) ||
+            (S2.under_norm && (S2.norm_df != 0 || S2.base != 0 || std::getenv("SIGOPS_NORM_EXACT_FILT"))) || S2.src_op || S2.batch >= 0 || S2.pre_stage >= 0 ||
+            (nodes[S2.node].dtype != SO_F64 && nodes[S2.node].dtype != SO_F32) || S2.in_frames != S2.need - S2.base)
+            continue;  // (below a Normpower: only where its region starts at the filter's first frame -- fuse_plain_sos, Stage::norm_df)
+        // A Float32 signal all the way (Float32 source, resampler and filter stages): the kernel rounds the resampled values to
+        // Float32 where the reference's resampler stores them (RsSos::x32) and stores a Float32 result; its sources are plain
+        // Float32 arrays or buffers (a Float32 x Float32 step rounds too: K1 materialises it)
+        const bool pure32 = nodes[S2.node].dtype == SO_F32;
+        if (pure32 && std::getenv("SIGOPS_RSOS_NO32")) continue;
+        if (S2.base > 0 && std::getenv("SIGOPS_RSOS_NOWINDOWS")) continue;
+        int i3 = -1;
+        for (size_t j = 0; j < stages.size(); ++j)
+            if (stages[j].kind == ST_RESAMPLE && stages[j].out_buf == S2.in_buf) i3 = (int)j;
+        if (i3 < 0 || i3 == alias_stage || stages[i3].win_off >= 0) continue;
+        Stage& S3 = stages[i3];
+        const RsPeriodic& rp = S3.rp;
+        // A window (After, a block of so.stream, a rank's time range): both stages are warm-started -- the cascade a decay
+        // time before the window (S2.base), the resampler a few periods before that (S3.base, whole periods).  The fused
+        // kernel's coordinates are the resampler stage's: its output 0 is frame S3.base, the cascade starts from rest
+        // there (earlier than the cascade stage alone would: a longer warm-up), and nothing below S2.base is stored.
+        if (S3.base > S2.base) continue;
+        if (rp.nstate || nodes[S3.node].dtype != nodes[S2.node].dtype || !S3.fix_host.empty() || S3.need < S2.need || (int)S3.carriers.size() > kCtlCar)
+            continue;
+        RsosFusion F(*this, i2, i3);
+        if (!F.source_form() || !F.own_table() || !F.trim_table() || !F.sole_reader() || !F.warmup_and_ranges() || !F.worth_it() || !F.waves() ||
+            !F.ring())
+            continue;
+        F.rewrite_carriers();
+        F.commit();
+        F.wproj_tables();
+        F.commit_launch();
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2394,20 +2668,18 @@ void Plan::fuse_resample_sos() {
 // nextblock filters every block of its child once, src/filters.jl:240-255; K2's chunked scan reads its input twice).
 // Period = ten blocks of 16 frames, every block's [16 x 16] tap operand the identity over the block's own 16 inputs
 // (4 k-steps: X = I . Win, exact), so a block costs 4 + 4 + 4 + 3 MFMAs on its y wave and 3 on the chain wave against 27
-// for the headline -- and the input is read once.  Conditions: process_stage built a carrier for the source (whole-signal
+// for the headline -- and the input is read once.  Conditions: bind_sos_input built a carrier for the source (whole-signal
 // filters over an array / a buffer, optionally plus or times one sine; one group of at most 6 sections; not the
 // sequential / exact-scan / under-Normpower variants), and the estimate below.
-void Plan::fuse_plain_sos() {
-    if (std::getenv("SIGOPS_NO_RSOS") || std::getenv("SIGOPS_NO_PLAIN_RSOS")) return;
-    auto env_int = [](const char* name, int dflt) {
-        const char* ev = std::getenv(name);
-        return ev ? std::atoi(ev) : dflt;
-    };
-    const int cus = env_int("SIGOPS_RSOS_GRID", 256);
+struct PlainRsos {
+    Plan& P;
+    std::vector<Node>& nodes;
+    std::vector<Stage>& stages;
+    const int cus;
     // One filter's geometry for this kernel.  gpm == 0: a launch of its own (ranges to fill the chip, the estimate against the
     // three passes decides); gpm > 0: as a member of a batched launch with gpm workgroups of its own (the caller decides for
     // the batch as a whole; cost: the microseconds one of its workgroups works).
-    auto fit = [&](size_t i2, int gpm, RsSos& g, double& cost) -> bool {
+    bool fit(size_t i2, int gpm, RsSos& g, double& cost) const {
         Stage& S2 = stages[i2];
         const int dt = nodes[S2.node].dtype;
         if (dt != SO_F64 && dt != SO_F32) return false;
@@ -2416,7 +2688,6 @@ void Plan::fuse_plain_sos() {
         if (pure32 && (c0.nsteps != 0 || c0.dtype != SO_F32)) return false;
         if (!pure32 && c0.dtype != SO_F64) return false;
         const SosCoefs& cf = S2.groups[0];
-        const int D = 2 * cf.nsec;
         const int nch = nodes[S2.node].nch;
         const int64_t need = S2.need, L = 160;
         const int ngp = 10, ks = 4, kw = 16;
@@ -2424,35 +2695,12 @@ void Plan::fuse_plain_sos() {
         // warm-up cut of the PLAIN filter: 2^-70, as the warm starts of windows (its warm-up blocks are cheap -- 18 MFMAs, no
         // resampling --, and this is the default path of any long Filt: a range that starts in near silence behind a loud passage
         // must not see what the cut dropped; the fused resampler + IIR form above cuts at 2^-56)
-        int64_t wp = 1;
-        {
-            const double tol = std::ldexp(1.0, -std::abs(env_int("SIGOPS_PLAIN_WTOL", 70)));
-            const Mat P = matpow(sos_state_matrix(cf), L, D);
-            Mat cur = P;
-            while (!(maxabs(cur) < tol) && wp < 1000000 && std::isfinite(maxabs(cur))) {
-                cur = matmul(cur, P, D);
-                ++wp;
-            }
-            if (!(maxabs(cur) < tol)) return false;
-        }
-        int ct = 1;
-        for (int c : {16, 8, 4, 2})
-            if (nch % c == 0) {
-                ct = c;
-                break;
-            }
-        const int rgs = 16 / ct;
-        const int64_t ncg = nch / ct;
-        if (gpm > 0 && ncg > gpm) return false;
-        int64_t rgroups = gpm > 0 ? gpm / ncg : std::max<int64_t>(1, cus / ncg);
-        int64_t nranges = rgroups * rgs;
-        const int64_t min_pr = std::max<int64_t>(1, 4 * wp);  // (a range at least four warm-ups long: <= 25 % of the blocks)
-        if (nperiods / nranges < min_pr) nranges = std::max<int64_t>(rgs, nperiods / min_pr / rgs * rgs);
-        if (const char* ev = std::getenv("SIGOPS_RSOS_RANGES"))
-            if (gpm == 0) nranges = std::max<int64_t>(1, std::atoll(ev));
-        const int64_t pr = (nperiods + nranges - 1) / nranges;
-        nranges = (nperiods + pr - 1) / pr;
-        const int64_t ngrp = ncg * ((nranges + rgs - 1) / rgs);
+        const int64_t wp = warmup_periods(cf, L, std::ldexp(1.0, -std::abs(env_int("SIGOPS_PLAIN_WTOL", 70))));
+        if (!wp) return false;
+        RsosRanges R;  // (a range at least four warm-ups long: <= 25 % of the blocks)
+        if (!rsos_ranges(nch, nperiods, std::max<int64_t>(1, 4 * wp), gpm, cus, 0, R)) return false;
+        const int ct = R.ct, rgs = R.rgs;
+        const int64_t pr = R.pr, nranges = R.nranges, ngrp = R.ngrp;
         if ((pr + wp) * ngp >= (1 << 30) || (pr + wp) * L >= ((int64_t)1 << 30)) return false;
         const bool stepped_few = (ct == 2 || ct == 4) && !pure32 && c0.nsteps == 1 && !std::getenv("SIGOPS_RSOS_NOGSPLIT");
         const int plain_nw = env_int("SIGOPS_PLAIN_NWAVES", stepped_few ? 16 : 12) == 16 ? 16 : 12;
@@ -2511,9 +2759,7 @@ void Plan::fuse_plain_sos() {
         {
             const int ny = 10;
             const int64_t span = (int64_t)(2 * ny - 1) * 17 + kw + 16 + 2 * g.chunk;
-            int ring = 4096;
-            while (ring >= 128 && rsos_lds_bytes(g.ngroups, ks, ring + 2, g.nwaves, g.cyc) > rsos_lds_budget()) ring -= 128;
-            if (const char* ev = std::getenv("SIGOPS_RSOS_RING")) ring = std::min(ring, std::max(128, std::atoi(ev) / 128 * 128));
+            const int ring = rsos_ring_frames(g);
             if (ring < 128 || ring < span) return false;
             g.ring = ring;
             g.rpitch = ring + 2;
@@ -2523,21 +2769,12 @@ void Plan::fuse_plain_sos() {
         g.x32 = pure32 ? 1 : 0;
         g.ring32 = pure32 && !std::getenv("SIGOPS_RSOS_NO_RING32") ? 1 : 0;
         g.gsplit = 0;
-        g.fuse = -1;
-        if (c0.nsteps == 1 && (c0.arg[0] & 0x2ff) == 0 && c0.nslots >= 1 && (c0.op[0] == OP_MUL || c0.op[0] == OP_ADD || c0.op[0] == OP_SUB)) {
-            g.fuse = c0.op[0] == OP_MUL ? 0 : c0.op[0] == OP_ADD ? 1 : ((c0.arg[0] & 0x100) ? 3 : 2);
-            const DLeaf& L0 = leaves[c0.slot_leaf[0]];
-            const int kind = c0.slot_kind[0];
-            if (kind == OP_FUNC && L0.mode == SO_FN_SIN && L0.sf == 1) g.fuse_sine = 1;
-            else if (kind == OP_CONST || kind == OP_SCALAR) g.fuse_sine = 0;
-            else g.fuse = -2;
-        } else if (c0.nsteps > 0)
-            g.fuse = -2;
+        P.rsos_fuse_step(c0, false, g);
         g.gsplit = g.nwaves == 16 && !g.src32 && g.fuse >= 0 && (ct == 2 || ct == 4) && !std::getenv("SIGOPS_RSOS_NOGSPLIT") ? 1 : 0;
         return true;
-    };
+    }
     // identity taps: block gi of the period reads inputs [16 gi, 16 gi + 16)
-    auto commit = [&](size_t i2, const RsSos& g) {
+    void commit(size_t i2, const RsSos& g) const {
         Stage& S2 = stages[i2];
         const int ngp = g.ngroups, kw = 16;
         const int64_t L = g.L;
@@ -2547,22 +2784,28 @@ void Plan::fuse_plain_sos() {
             S2.rsos_jend_host[(size_t)gi] = 16 * gi + 15;
             for (int kk = 0; kk < kw; ++kk) S2.rsos_tab_host[((size_t)gi * kw + kk) * 16 + kk] = 1.0;
         }
-        S2.rsos_tab_buf = raw_buf(S2.rsos_tab_host.size() * 8);
-        S2.rsos_jend_buf = raw_buf(S2.rsos_jend_host.size() * 4);
+        S2.rsos_tab_buf = P.raw_buf(S2.rsos_tab_host.size() * 8);
+        S2.rsos_jend_buf = P.raw_buf(S2.rsos_jend_host.size() * 4);
         S2.rsos_jrel_host.resize((size_t)L);  // (identity: output r's one tap is its own input)
         for (int64_t r = 0; r < L; ++r) S2.rsos_jrel_host[(size_t)r] = (int)(r % 16) - 15;
-        S2.rsos_jrel_buf = raw_buf(S2.rsos_jrel_host.size() * 4);
+        S2.rsos_jrel_buf = P.raw_buf(S2.rsos_jrel_host.size() * 4);
         S2.rsos_taps = 1;
         S2.rs = g;
         S2.rsos_src = (int)i2;  // (its own carriers, control block and tables)
         const int64_t ngrp = (int64_t)(g.nch / g.ct) * ((g.nranges + g.rgs - 1) / g.rgs);
         S2.rsos_grid = (int)std::min<int64_t>(ngrp, cus);
         rsos_block_matrices(S2.groups[0], S2.rsos_mats_host);
-        S2.rsos_mats_buf = raw_buf(S2.rsos_mats_host.size() * 8);
+        S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
         if (std::getenv("SIGOPS_DEBUG_PLAN"))
             std::fprintf(stderr, "[sigops] IIR in one pass (k_rsos, identity resampler%s): %lld ranges of %lld periods (+%d warm-up), %lld groups of %d ch x %d ranges, ring=%d fuse=%d/%d\n",
                          S2.rsb >= 0 ? ", batched" : "", (long long)g.nranges, (long long)g.pr, g.wp, (long long)ngrp, g.ct, g.rgs, g.ring, g.fuse, g.fuse_sine);
-    };
+    }
+};
+
+void Plan::fuse_plain_sos() {
+    if (std::getenv("SIGOPS_NO_RSOS") || std::getenv("SIGOPS_NO_PLAIN_RSOS")) return;
+    const int cus = env_int("SIGOPS_RSOS_GRID", 256);
+    const PlainRsos one{*this, nodes, stages, cus};
     // Several filters of this kind in one plan (config 4's 64 scenes) are ONE batched launch per pass of the three-pass form
     // (batch_sos_stages, 26 us per scene); as launches of their own of this kernel they would be 42 us each.  Small ones go
     // through this kernel TOGETHER (k_rsos_batch) where that wins, and stay for the three-pass batch otherwise.
@@ -2582,8 +2825,8 @@ void Plan::fuse_plain_sos() {
         }
         RsSos g{};
         double cost = 0.0;
-        if (!fit(i2, 0, g, cost)) continue;
-        commit(i2, g);
+        if (!one.fit(i2, 0, g, cost)) continue;
+        one.commit(i2, g);
         if (S2.bad_buf < 0) S2.bad_buf = raw_buf((size_t)g.nch * 4);
     }
     // ---- the small ones, together: members that share the kernel's instantiation (waves; the result's type) ----
@@ -2604,7 +2847,7 @@ void Plan::fuse_plain_sos() {
         }
         RsSos g{};
         double cost = 0.0;
-        if (!fit(i2, 1 << 20, g, cost)) continue;  // (which instantiation it would take)
+        if (!one.fit(i2, 1 << 20, g, cost)) continue;  // (which instantiation it would take)
         kinds[{nodes[stages[i2].node].dtype == SO_F32 ? 1 : 0, g.nwaves}].push_back(i2);
     }
     for (auto& kv : kinds) {
@@ -2619,7 +2862,7 @@ void Plan::fuse_plain_sos() {
         for (size_t i2 : cand) {
             RsSos g{};
             double cost = 0.0;
-            if (!fit(i2, gpm, g, cost) || g.nwaves != kv.first.second) continue;
+            if (!one.fit(i2, gpm, g, cost) || g.nwaves != kv.first.second) continue;
             if (!gs.empty() && (g.ring != gs[0].ring || g.ngroups != gs[0].ngroups)) continue;
             B.members.push_back((int)i2);
             gs.push_back(g);
@@ -2641,7 +2884,7 @@ void Plan::fuse_plain_sos() {
         int off = 0;
         for (size_t m = 0; m < B.members.size(); ++m) {
             stages[B.members[m]].rsb = bi;
-            commit((size_t)B.members[m], gs[m]);
+            one.commit((size_t)B.members[m], gs[m]);
             B.bad_off.push_back(off);
             off += gs[m].nch;
         }
@@ -2747,7 +2990,7 @@ void Plan::fuse_state_passes() {
         if (!ok) continue;
         // LDS: the taps ([4*ksw][10] doubles) go behind the gain ring; keep at least three tile slots
         {
-            const size_t avail = 160 * 1024 - sizeof(RsCtl) - 64;
+            const size_t avail = kRsLdsAvail;
             const size_t tile_bytes = (size_t)rp0.ct * rp0.lds_pitch * 8;
             const size_t fbytes = (size_t)2 * rp0.fslots * rp0.fpitch * 8 + (rp0.ftwo ? kRsTwoDoubles * 8 : 0);
             const size_t wbytes = (size_t)4 * ksw * 10 * 8;

@@ -138,6 +138,109 @@ def seed_starts():
     return starts
 
 
+# ---- the ladders of tests/test_gpu_forms.py: one small input per case, one rung per form ---------------------------------
+F64, F32 = np.float64, np.float32
+NFRAMES = 20001
+# every switch a ladder uses is cleared around a rung, so that a rung is its own environment and nothing else
+RS_SWITCHES = ("SIGOPS_RS_NO_F32MFMA", "SIGOPS_RS_NO32ROWS", "SIGOPS_RS_NOQ1", "SIGOPS_RS_NOROWS_MFMA", "SIGOPS_RS_NOROWS",
+               "SIGOPS_RS_NOPAIR", "SIGOPS_RS_NOTILED", "SIGOPS_RS_NOARB", "SIGOPS_ARB_MIN")
+SOS_SWITCHES = ("SIGOPS_RSOS_MINGROUPS", "SIGOPS_NO_PLAIN_RSOS", "SIGOPS_NO_RSOS", "SIGOPS_SOS_CHUNK", "SIGOPS_SOS_ONEPASS",
+                "SIGOPS_SOS_3PASS", "SIGOPS_SOS_EXACT", "SIGOPS_SOS_NOALIGN", "SIGOPS_NORM_EXACT_FILT", "SIGOPS_SOS_NOXSCAN")
+
+
+def rung_env(switches, kv):
+    return env(**{**{k: None for k in switches}, **kv})
+
+
+def ladder_noise(seed, n, nch, dt):
+    return np.asfortranarray(np.random.default_rng(seed).standard_normal((n, nch)).astype(dt))
+
+
+# 1. the resampler ladder
+RATES = [(44100, 48000, 21770), (48000, 44100, 18376), (44100, 16000, 7257), (8000, 16000, 40002), (48000, 16000, 6667), (44100, 12000, 5443)]
+COMBOS = [(8, F64), (3, F64), (4, F32)]  # tiles of 8 channels; of one (no 16-row and no narrow-store form); the Float32 MFMA form
+_R1 = {"SIGOPS_RS_NO32ROWS": 1}
+_R2 = {**_R1, "SIGOPS_RS_NOQ1": 1}
+_R4 = {**_R2, "SIGOPS_RS_NOROWS": 1}
+R_LADDER = [("R0", {}), ("R0f", {"SIGOPS_RS_NO_F32MFMA": 1}), ("R1", _R1), ("R2", _R2), ("R3", {**_R2, "SIGOPS_RS_NOROWS_MFMA": 1}), ("R4", _R4),
+            ("R5", {**_R4, "SIGOPS_RS_NOPAIR": 1}), ("R6", {**_R4, "SIGOPS_RS_NOTILED": 1})]
+R_CASES = [(fi, fo, nout, nch, dt, False) for fi, fo, nout in RATES for nch, dt in COMBOS] + [(44100, 48000, 9001, nch, dt, True) for nch, dt in COMBOS]
+A_RATES = [(1000.0, 1000.0 * np.pi, 125664), (48000.0, 44100.5, 36751)]
+A_LADDER = [("A0", {"SIGOPS_ARB_MIN": 1}), ("A1", {"SIGOPS_RS_NOARB": 1}), ("A2", {"SIGOPS_RS_NOARB": 1, "SIGOPS_RS_NOPAIR": 1}), ("A3", {"SIGOPS_RS_NOTILED": 1})]
+A_CASES = [(fi, fo, nout, nch, dt) for fi, fo, nout in A_RATES for nch, dt in ((8, F64), (3, F32))]
+
+
+def resampler_rungs(case):
+    return [r for r in R_LADDER if r[0] != "R0f" or case[4] == F32]
+
+
+def resampler_tree(case):
+    fi, fo, nout, nch, dt, window = case
+    x = so.Signal(ladder_noise(1000 + nch, 40000 if window else NFRAMES, nch, dt), fi * so.Hz) | so.ToFramerate(fo * so.Hz)
+    if window:  # a warm start and a non-zero initial phase
+        x = x | so.After(12345 * so.frames) | so.Until(9001 * so.frames)
+    return x
+
+
+def arbitrary_tree(case):
+    fi, fo, nout, nch, dt = case
+    return so.Signal(ladder_noise(2000 + nch, 40000, nch, dt), fi * so.Hz) | so.ToFramerate(fo * so.Hz)
+
+
+# 2. the IIR ladder
+FILTERS = {  # name: (filter, sections)
+    "lowpass1_pole0": (lambda: so.Filt(so.Lowpass, 11025 * so.Hz, method=so.Butterworth(1)), 1),  # pole at 0: forgets within a tile step
+    "bandstop5": (lambda: so.Filt(so.Bandstop, 0.5 * so.kHz, 2 * so.kHz), 5),
+    "lowpass6": (lambda: so.Filt(so.Lowpass, 5 * so.kHz, order=12), 6),  # the most k_rsos takes
+    "bandpass8": (lambda: so.Filt(so.Bandpass, 1 * so.kHz, 3 * so.kHz, method=so.Butterworth(8)), 8),  # the NS = 8 instantiation
+    "bandpass10": (lambda: so.Filt(so.Bandpass, 1 * so.kHz, 4 * so.kHz, order=10), 10),  # two cascaded groups
+    "highpass_slow": (lambda: so.Filt(so.Highpass, 20 * so.Hz, order=3), 2),  # slow decay: the chunk length doubles
+}
+I_COMBOS = [(1, F64), (5, F64), (4, F32)]
+CHUNKS = (32, 64, 512, 4096, 20032)  # more than 64 chunks (32, 64), 2 to 64 (512, 4096), one chunk and a single launch (20032)
+_I1 = {"SIGOPS_NO_PLAIN_RSOS": 1}
+I_LADDER = ([("I0", {"SIGOPS_RSOS_MINGROUPS": 1}), ("I1", _I1)] + [("I2_%d" % c, {**_I1, "SIGOPS_SOS_CHUNK": c}) for c in CHUNKS]
+            + [("I3", {"SIGOPS_SOS_ONEPASS": 1}), ("I4", {"SIGOPS_SOS_EXACT": 1}), ("I5", {**_I1, "SIGOPS_SOS_NOALIGN": 1})])
+_I6a = {"SIGOPS_RSOS_MINGROUPS": 1}
+_I6b = {**_I6a, "SIGOPS_NORM_EXACT_FILT": 1}
+N_LADDER = [("I6a", _I6a), ("I6b", _I6b), ("I6c", {**_I6b, "SIGOPS_SOS_NOXSCAN": 1})]
+I_CASES = [(f, nch, dt) for f in FILTERS for nch, dt in I_COMBOS]
+
+
+def filter_rungs(case):
+    return [r for r in I_LADDER if r[0] != "I0" or FILTERS[case[0]][1] <= 6]  # (k_rsos takes at most six sections)
+
+
+def filter_tree(case):
+    f, nch, dt = case
+    return so.Signal(ladder_noise(3000 + nch, NFRAMES, nch, dt), 44.1 * so.kHz) | FILTERS[f][0]()
+
+
+def resampler_id(c):
+    return "%g-%g-%dx%s%s" % (c[0], c[1], c[3], np.dtype(c[4]).name, "-window" if len(c) > 5 and c[5] else "")
+
+
+def filter_id(c):
+    return "%s-%dx%s" % (c[0], c[1], np.dtype(c[2]).name)
+
+
+def ladders():
+    """every (case, rung) of the four ladders as (name, tree builder, switches to clear, the rung's switches), sunk into a
+    planar host result as test_gpu_forms.py's run_host sinks them"""
+    for c in R_CASES:
+        for rung, kv in resampler_rungs(c):
+            yield "resample %s %s" % (resampler_id(c), rung), (lambda c=c: resampler_tree(c)), RS_SWITCHES, kv
+    for c in A_CASES:
+        for rung, kv in A_LADDER:
+            yield "arbitrary %s %s" % (resampler_id(c), rung), (lambda c=c: arbitrary_tree(c)), RS_SWITCHES, kv
+    for c in I_CASES:
+        for rung, kv in filter_rungs(c):
+            yield "filter %s %s" % (filter_id(c), rung), (lambda c=c: filter_tree(c)), SOS_SWITCHES, kv
+    for c in I_CASES:
+        for rung, kv in N_LADDER:
+            yield "filter|norm %s %s" % (filter_id(c), rung), (lambda c=c: filter_tree(c) | so.Normpower), SOS_SWITCHES, kv
+
+
 class ResultView:
     """A result for `tree` to be sunk into -- dtype `dt` (the tree's own by default); where="dev": a device tensor
     [nch][n + pad], time fastest, filled with NaN; where="host": a NumPy array in `layout` ("planar", "interleaved", or

@@ -38,11 +38,13 @@ from comb_ref import comb
 from cumsum_ref import cumsum_ref
 from sampleat_ref import sampleat_np
 from forms_corpus import POS, ResultView, at_seed, corpus, env, seed_starts
+# the ladders' tables and trees (tools/plan_fingerprint.py --ladders walks the same ones)
+from forms_corpus import (A_CASES, A_LADDER, CHUNKS, F32, F64, FILTERS, I_CASES, I_LADDER, N_LADDER, NFRAMES, R_CASES, RS_SWITCHES, SOS_SWITCHES,
+                          _I1, arbitrary_tree, filter_rungs, filter_tree, resampler_rungs, resampler_tree, rung_env)
+from forms_corpus import filter_id as _iid, resampler_id as _rid
 
 pytestmark = pytest.mark.gpu
 
-F64, F32 = np.float64, np.float32
-NFRAMES = 20001
 BLOCK = 1024
 
 
@@ -85,21 +87,8 @@ def bounds(kind, dt):
 
 RUNGS_TWO = 1e-11  # two rungs of one Float64 case
 
-# every switch a ladder uses is cleared around a rung, so that a rung is its own environment and nothing else
-RS_SWITCHES = ("SIGOPS_RS_NO_F32MFMA", "SIGOPS_RS_NO32ROWS", "SIGOPS_RS_NOQ1", "SIGOPS_RS_NOROWS_MFMA", "SIGOPS_RS_NOROWS",
-               "SIGOPS_RS_NOPAIR", "SIGOPS_RS_NOTILED", "SIGOPS_RS_NOARB", "SIGOPS_ARB_MIN")
-SOS_SWITCHES = ("SIGOPS_RSOS_MINGROUPS", "SIGOPS_NO_PLAIN_RSOS", "SIGOPS_NO_RSOS", "SIGOPS_SOS_CHUNK", "SIGOPS_SOS_ONEPASS",
-                "SIGOPS_SOS_3PASS", "SIGOPS_SOS_EXACT", "SIGOPS_SOS_NOALIGN", "SIGOPS_NORM_EXACT_FILT", "SIGOPS_SOS_NOXSCAN")
 STAGE_STEPS = ("k_resample_periodic", "k_resample_rows", "k_resample_arb", "k_resample_tiled2", "k_resample_tiled", "k_resample",
                "k_rsos", "k_sos", "k_sos_exact")
-
-
-def rung_env(switches, kv):
-    return env(**{**{k: None for k in switches}, **kv})
-
-
-def noise(seed, n, nch, dt):
-    return np.asfortranarray(np.random.default_rng(seed).standard_normal((n, nch)).astype(dt))
 
 
 def run_host(tree, dt=None, nexec=1):
@@ -161,47 +150,21 @@ def skip_cap(rows):
     assert 2 * sum(not r["live"] for r in rows) <= len(rows), [(r["rung"], r["step"], r["live"]) for r in rows]
 
 
-# ---- 1. the resampler ladder ------------------------------------------------------------------------------------------
-RATES = [(44100, 48000, 21770), (48000, 44100, 18376), (44100, 16000, 7257), (8000, 16000, 40002), (48000, 16000, 6667), (44100, 12000, 5443)]
-COMBOS = [(8, F64), (3, F64), (4, F32)]  # tiles of 8 channels; of one (no 16-row and no narrow-store form); the Float32 MFMA form
-_R1 = {"SIGOPS_RS_NO32ROWS": 1}
-_R2 = {**_R1, "SIGOPS_RS_NOQ1": 1}
-_R4 = {**_R2, "SIGOPS_RS_NOROWS": 1}
-R_LADDER = [("R0", {}), ("R0f", {"SIGOPS_RS_NO_F32MFMA": 1}), ("R1", _R1), ("R2", _R2), ("R3", {**_R2, "SIGOPS_RS_NOROWS_MFMA": 1}), ("R4", _R4),
-            ("R5", {**_R4, "SIGOPS_RS_NOPAIR": 1}), ("R6", {**_R4, "SIGOPS_RS_NOTILED": 1})]
-R_CASES = [(fi, fo, nout, nch, dt, False) for fi, fo, nout in RATES for nch, dt in COMBOS] + [(44100, 48000, 9001, nch, dt, True) for nch, dt in COMBOS]
-A_RATES = [(1000.0, 1000.0 * np.pi, 125664), (48000.0, 44100.5, 36751)]
-A_LADDER = [("A0", {"SIGOPS_ARB_MIN": 1}), ("A1", {"SIGOPS_RS_NOARB": 1}), ("A2", {"SIGOPS_RS_NOARB": 1, "SIGOPS_RS_NOPAIR": 1}), ("A3", {"SIGOPS_RS_NOTILED": 1})]
-A_CASES = [(fi, fo, nout, nch, dt) for fi, fo, nout in A_RATES for nch, dt in ((8, F64), (3, F32))]
-
-
-def _rid(c):
-    return "%g-%g-%dx%s%s" % (c[0], c[1], c[3], np.dtype(c[4]).name, "-window" if len(c) > 5 and c[5] else "")
-
-
-def resampler_tree(case):
-    fi, fo, nout, nch, dt, window = case
-    x = so.Signal(noise(1000 + nch, 40000 if window else NFRAMES, nch, dt), fi * so.Hz) | so.ToFramerate(fo * so.Hz)
-    if window:  # a warm start and a non-zero initial phase
-        x = x | so.After(12345 * so.frames) | so.Until(9001 * so.frames)
-    return x
-
-
+# ---- 1. the resampler ladder (tables and trees: forms_corpus.py) ------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def resampler_case(case):
     fi, fo, nout, nch, dt, window = case
     x = resampler_tree(case)
     want = oracle_sink(x)
     assert want.shape == (nout, nch) and want.dtype == dt and np.isfinite(want).all()
-    rungs = [r for r in R_LADDER if r[0] != "R0f" or dt == F32]
-    rows = walk("resample", "resample", x, want, rungs, RS_SWITCHES, dt)
+    rows = walk("resample", "resample", x, want, resampler_rungs(case), RS_SWITCHES, dt)
     return rows, want.shape, want.dtype
 
 
 @functools.lru_cache(maxsize=None)
 def arbitrary_case(case):
     fi, fo, nout, nch, dt = case
-    x = so.Signal(noise(2000 + nch, 40000, nch, dt), fi * so.Hz) | so.ToFramerate(fo * so.Hz)
+    x = arbitrary_tree(case)
     want = oracle_sink(x)
     assert want.shape == (nout, nch) and want.dtype == dt and np.isfinite(want).all()
     return walk("arbitrary", "resample", x, want, A_LADDER, RS_SWITCHES, dt), want.shape, want.dtype
@@ -234,45 +197,17 @@ def test_arbitrary_rate_ladder(case):
     assert [r["step"][0] for r in rows][-1] == "k_resample"
 
 
-# ---- 2. the IIR ladder ------------------------------------------------------------------------------------------------
-FILTERS = {  # name: (filter, sections)
-    "lowpass1_pole0": (lambda: so.Filt(so.Lowpass, 11025 * so.Hz, method=so.Butterworth(1)), 1),  # pole at 0: forgets within a tile step
-    "bandstop5": (lambda: so.Filt(so.Bandstop, 0.5 * so.kHz, 2 * so.kHz), 5),
-    "lowpass6": (lambda: so.Filt(so.Lowpass, 5 * so.kHz, order=12), 6),  # the most k_rsos takes
-    "bandpass8": (lambda: so.Filt(so.Bandpass, 1 * so.kHz, 3 * so.kHz, method=so.Butterworth(8)), 8),  # the NS = 8 instantiation
-    "bandpass10": (lambda: so.Filt(so.Bandpass, 1 * so.kHz, 4 * so.kHz, order=10), 10),  # two cascaded groups
-    "highpass_slow": (lambda: so.Filt(so.Highpass, 20 * so.Hz, order=3), 2),  # slow decay: the chunk length doubles
-}
-I_COMBOS = [(1, F64), (5, F64), (4, F32)]
-CHUNKS = (32, 64, 512, 4096, 20032)  # more than 64 chunks (32, 64), 2 to 64 (512, 4096), one chunk and a single launch (20032)
-_I1 = {"SIGOPS_NO_PLAIN_RSOS": 1}
-I_LADDER = ([("I0", {"SIGOPS_RSOS_MINGROUPS": 1}), ("I1", _I1)] + [("I2_%d" % c, {**_I1, "SIGOPS_SOS_CHUNK": c}) for c in CHUNKS]
-            + [("I3", {"SIGOPS_SOS_ONEPASS": 1}), ("I4", {"SIGOPS_SOS_EXACT": 1}), ("I5", {**_I1, "SIGOPS_SOS_NOALIGN": 1})])
-_I6a = {"SIGOPS_RSOS_MINGROUPS": 1}
-_I6b = {**_I6a, "SIGOPS_NORM_EXACT_FILT": 1}
-N_LADDER = [("I6a", _I6a), ("I6b", _I6b), ("I6c", {**_I6b, "SIGOPS_SOS_NOXSCAN": 1})]
+# ---- 2. the IIR ladder (tables and trees: forms_corpus.py) ------------------------------------------------------------
 I_NAMES = {"I0": "k_rsos", "I1": "k_sos", "I3": "k_sos", "I4": "k_sos_exact", "I5": "k_sos", **{"I2_%d" % c: "k_sos" for c in CHUNKS}}
-I_CASES = [(f, nch, dt) for f in FILTERS for nch, dt in I_COMBOS]
-
-
-def _iid(c):
-    return "%s-%dx%s" % (c[0], c[1], np.dtype(c[2]).name)
-
-
-def filter_tree(case):
-    f, nch, dt = case
-    return so.Signal(noise(3000 + nch, NFRAMES, nch, dt), 44.1 * so.kHz) | FILTERS[f][0]()
 
 
 @functools.lru_cache(maxsize=None)
 def filter_case(case):
     f, nch, dt = case
-    nsec = FILTERS[f][1]
     x = filter_tree(case)
     want = oracle_sink(x)
     assert want.shape == (NFRAMES, nch) and want.dtype == dt and np.isfinite(want).all()
-    rungs = [r for r in I_LADDER if r[0] != "I0" or nsec <= 6]  # (k_rsos takes at most six sections)
-    rows = walk("filter", "filter", x, want, rungs, SOS_SWITCHES, dt)
+    rows = walk("filter", "filter", x, want, filter_rungs(case), SOS_SWITCHES, dt)
     xn = x | so.Normpower
     wantn = oracle_sink(xn)
     assert wantn.shape == want.shape and np.isfinite(wantn).all()

@@ -9,6 +9,9 @@ kernel's summation order is fixed by the frame index, so two builds that launch 
 print the same lines.  The trees: every entry of tests/cases.py's CASES, then one per launch routine of csrc/executor.cpp
 that those do not reach, built as the tests named beside them build theirs (tests/forms_corpus.py, which
 tests/test_gpu_forms.py runs too and holds to the oracle).  Inputs are seeded.
+
+`--ladders`: after those, one line in the same format per (case, rung) of that test's four ladders -- every form of the
+resampler and of the IIR that csrc/stages.cpp chooses between -- sunk into a planar host result as the test sinks them.
 """
 import hashlib
 import json
@@ -21,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sigops_amd as so  # noqa: E402,F401
-from forms_corpus import ResultView, corpus  # noqa: E402  (the trees and the result views: shared with tests/test_gpu_forms.py)
+from forms_corpus import ResultView, corpus, ladders, rung_env  # noqa: E402  (the trees and the result views: shared with tests/test_gpu_forms.py)
 
 
 def fingerprint(tree, **view):
@@ -52,6 +55,14 @@ def main():
             for k, v in old.items():
                 os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
         print(json.dumps({"tree": name, **line}), flush=True)
+    if "--ladders" in sys.argv[1:]:  # then every (case, rung) of test_gpu_forms.py's four ladders, the rung's switches set for the plan's creation
+        for name, build, switches, kv in ladders():
+            with rung_env(switches, kv):
+                try:
+                    line = fingerprint(build(), where="host")
+                except Exception as e:
+                    line = {"error": "%s: %s" % (type(e).__name__, e)}
+            print(json.dumps({"tree": name, **line}), flush=True)
 
 
 if __name__ == "__main__":
