@@ -85,7 +85,8 @@ typedef enum so_kind {
     SO_NODE_SAMPLEAT = 12,/* SampleAt(x, pos): x read at computed positions (no reference counterpart) */
     SO_NODE_COMB = 13,    /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
     SO_NODE_CUMSUM = 14,  /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
-    SO_NODE_MOVING = 15   /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
+    SO_NODE_MOVING = 15,  /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
+    SO_NODE_MOVSUM = 16   /* MovingSum / MovingMean / MovingRMS: sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -290,6 +291,15 @@ typedef enum so_rskind {
  *            tests/moving_ref.py is the definition).  The node has x's length, frame rate, channels AND sample type.
  *            MovingMax(x, w, ahead=a): l0 = w - 1 - a, l1 = a, i0 = 0; MovingMin: i0 = 1.  Not exactly one child, l0 < 0,
  *            l1 < 0 or i0 outside {0, 1} is SO_ERR_INVALID; an integer child SO_ERR_UNSUPPORTED.
+ *  MOVSUM    child 0 = x (Float32 / Float64, any length, infinite too)   l0 = back >= 0, l1 = ahead >= 0, the frames of
+ *            the window before and after frame n   i0 = 0 sum, 1 mean, 2 rms.
+ *            Per channel s[n] = the sum of x[k] (rms: of x[k] * x[k], the product formed in Float64) over
+ *            max(0, n - l0) <= k <= min(N - 1, n + l1), in Float64 over ONE summation tree fixed by the absolute frame
+ *            numbers, l0 and l1 ("Moving sums"; tests/movingsum_ref.py is the definition), so windows, `stream`
+ *            blocks and the whole result agree bit for bit.  With cnt[n] the frames of the clipped window: sum y = s,
+ *            mean y = s / cnt, rms y = sqrt(s / cnt), each operation rounded once.  The node has x's length, frame rate
+ *            and channels and is Float64.  MovingSum(x, w, ahead=a): l0 = w - 1 - a, l1 = a.  Not exactly one child,
+ *            l0 < 0, l1 < 0 or i0 outside {0, 1, 2} is SO_ERR_INVALID; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

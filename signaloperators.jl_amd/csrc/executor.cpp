@@ -100,6 +100,7 @@ static const char* stage_step_name(const Stage& S) {
     case ST_COMB: return "k_comb";
     case ST_CUMSUM: return "k_cumsum";
     case ST_MOVING: return "k_moving";
+    case ST_MOVSUM: return "k_movsum";
     default: return "k_sumsq";
     }
 }
@@ -133,6 +134,8 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return S.need * (int64_t)N.nch * (2 * kid_esz(0) + 8);
     case ST_MOVING:  // the frames read where x lies (the long form's second and third reads and the tile halos left out), one sample of x's type written
         return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
+    case ST_MOVSUM:  // the frames read where x lies (the long form's further reads, the tile halos and lead-ins left out), one Float64 written
+        return (S.in_frames * kid_esz(0) + (S.need - S.base) * 8) * (int64_t)N.nch;
     default: return (S.need - S.base) * N.nch * esz;
     }
 }
@@ -519,6 +522,7 @@ static View stage_in(Plan* P, const Stage& S, int nch, int dtype) {
 // SampleAt, Comb and Cumsum, whose kernels store Float64 only, get 8 bytes for both: their nodes are Float64 (build_nodes),
 // and plan_create lets only a periodic resampler or a filter narrow, so alias_narrow is false where one of them is aliased.
 // Moving stores its node's type, Float32 or Float64, and is aliased only to a result of that type.
+// Movsum stores Float64 like Cumsum: its node is Float64.
 // A member of an RsBatch is never the aliased stage (fuse_plain_sos skips it): k_rsos_batch's members write windows or buffers.
 static View stage_out(Plan* P, int sid, void* outp) {
     const Stage& S = P->stages[sid];
@@ -850,6 +854,33 @@ static int run_moving(Plan* P, const Step& s, void* outp, hipStream_t st) {
     return nl;
 }
 
+static int run_movsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const int xdt = P->nodes[N.kids[0]].dtype;
+    const View in = stage_in(P, S, N.nch, xdt), out = stage_out(P, s.idx, outp);
+    MovsumArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.x_f32 = xdt == SO_F32;
+    a.n_in = S.in_frames;
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.n_out = S.need - S.base;
+    a.off = S.base - S.in_base;
+    a.abs0 = S.in_base;  // the summation tree is fixed by x's own frame numbers
+    a.back = N.nd.l0;
+    a.ahead = N.nd.l1;
+    a.tab = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
+    a.nch = N.nch;
+    a.op = N.nd.i0;
+    const int nl = launch_movsum(a, st);
+    // (one workgroup per tile of kMsumTile frames in grid.x, the channels in grid.y)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Movsum: more than 65535 channels, or 2^31 tiles of 2048 frames or blocks of 1024 frames and more, are not lowered");
+    return nl;
+}
+
 // the resampler in front and this cascade in one launch (k_rsos); `g`: the cascade's geometry as run_sos set it up
 static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View& out, hipStream_t st) {
     const Node& N = P->nodes[S.node];
@@ -1170,6 +1201,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 case ST_COMB: nl = run_comb(P, s, outp, st); break;
                 case ST_CUMSUM: nl = run_cumsum(P, s, outp, st); break;
                 case ST_MOVING: nl = run_moving(P, s, outp, st); break;
+                case ST_MOVSUM: nl = run_movsum(P, s, outp, st); break;
                 case ST_SOS: nl = run_sos(P, s, outp, st); break;
                 case ST_RESAMPLE: nl = run_resample(P, s, outp, st); break;
                 default: nl = run_norm(P, s, outp, st); break;

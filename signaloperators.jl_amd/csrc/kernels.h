@@ -177,4 +177,50 @@ constexpr int64_t moving_scratch(int64_t n_in, int64_t back, int64_t ahead) {
     return moving_is_long(n_in, back, ahead) ? (int64_t)(moving_levels(n_in, back, ahead) + 1) * moving_blocks(n_in) : 0;
 }
 int launch_moving(const MovingArgs& a, hipStream_t st);
+// MovingSum / MovingMean / MovingRMS (k_movsum.hip, -ffp-contract=off): output j in [0, n_out) of a channel is the Float64
+// sum of the input frames [j + off - back, j + off + ahead] clipped to [0, n_in) (rms: of their squares), over ONE summation
+// tree fixed by the ABSOLUTE frame numbers of x -- input frame i is frame abs0 + i of x -- and by back and ahead alone
+// (DESIGN.md "Moving sums"; tests/movingsum_ref.py): what lies outside the signal is -0.0, the additive identity; segments
+// [m S, (m + 1) S) of S = min(kMsumBlock, the greatest power of two <= W - 1) frames; inside one, runs of kMsumRun frames summed
+// left to right (right to left) and an inclusive Kogge-Stone scan over the run totals give the prefix P and the suffix Q; the
+// window is (Q(lo) + M) + P(hi), M the whole segments in between.  W - 1 <= kMsumHalo is one launch (k_movsum_short: the tile,
+// its halo and the lead-in to a multiple of S in LDS, M one segment's total at most); a longer window has S = kMsumBlock and
+// is 2 + levels launches (k_movsum_totals: the total of every aligned block; k_movsum_level: the aligned dyadic nodes over
+// them, node (l, q) = node (l - 1, 2 q) + node (l - 1, 2 q + 1); k_movsum_long: Q and P from the blocks the tile's windows
+// start and end in, M the canonical cover of the blocks in between by maximal aligned nodes, added left to right).  The
+// mean divides by the frames of the clipped window, the rms takes the square root of that quotient.  No workgroup waits
+// for another, no atomics.  Strides in elements.  Returns the number of launches, -1 when the shape cannot be launched.
+constexpr int kMsumRun = 16;      // R: frames of a run
+constexpr int kMsumBlock = 1024;  // B: the longest segment; a block of the long form
+constexpr int kMsumTile = 2048;   // output frames of a workgroup
+constexpr int kMsumHalo = 1024;   // the short form takes W - 1 <= this: its image holds kMsumTile + kMsumHalo + (S - 1) <= 4095 keys
+struct MovsumArgs {
+    const void* x;  // input frame i, channel c at x[i * xfs + c * xcs], i in [0, n_in)
+    int64_t xfs, xcs, n_in;
+    double* y;      // y[j + c * ycs], j in [0, n_out)
+    int64_t ycs, n_out;
+    int64_t off;    // the input frame output 0 is centred on (0 <= off, off + n_out <= n_in)
+    int64_t abs0;   // the frame of x that input frame 0 is (>= 0; the windows reach no frame of x in [0, abs0))
+    int64_t back, ahead;
+    double* tab;    // long form: [levels + 1][nch][nblocks] Float64 (movsum_scratch); unused by the short form
+    int32_t nch, x_f32;
+    int32_t op;     // 0 sum, 1 mean, 2 rms
+};
+constexpr bool movsum_is_long(int64_t back, int64_t ahead) { return back > kMsumHalo || ahead > kMsumHalo || back + ahead > kMsumHalo; }
+// the aligned blocks of x that hold the input frames [abs0, abs0 + n_in), n_in >= 1
+constexpr int64_t movsum_blocks(int64_t abs0, int64_t n_in) { return (abs0 + n_in - 1) / kMsumBlock - abs0 / kMsumBlock + 1; }
+// the levels above the block totals: a cover lies inside the (W - 1) / B whole blocks a window can hold, and a node of
+// more than `blocks` blocks that starts inside them equals its leftmost node of ceil(log2(blocks)) levels (the rest is -0.0)
+constexpr int movsum_levels(int64_t abs0, int64_t n_in, int64_t back, int64_t ahead) {
+    const int64_t cap = (int64_t)1 << 60;
+    const int64_t reach = (back < cap ? back : cap) + (ahead < cap ? ahead : cap);
+    const int64_t mid = reach / kMsumBlock, nb = movsum_blocks(abs0, n_in);
+    int l = 0;
+    while (((int64_t)2 << l) <= mid && ((int64_t)1 << l) < nb) ++l;
+    return l;
+}
+constexpr int64_t movsum_scratch(int64_t abs0, int64_t n_in, int64_t back, int64_t ahead) {
+    return movsum_is_long(back, ahead) ? (int64_t)(movsum_levels(abs0, n_in, back, ahead) + 1) * movsum_blocks(abs0, n_in) : 0;
+}
+int launch_movsum(const MovsumArgs& a, hipStream_t st);
 }  // namespace so

@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -119,7 +119,7 @@ struct Stage {
     bool norm_direct = false; // Normpower of a plain array leaf: the rms is taken over the array where it lies, readers divide its loads
     bool under_norm = false;  // a Normpower consumes this stage (directly or through further stages)
     int64_t norm_df = 0;      // ... the largest frame offset it is read at on such a path (0: every Normpower's region starts at this stage's first frame)
-    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys
+    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys; Movsum's block totals and dyadic nodes, [nch * movsum_scratch(..)] Float64
     int64_t win_off = -1;  // >= 0: the stage writes the RESULT's frames [win_off, win_off + need) itself (window aliasing)
     // input source (after processing): either a materialised buffer or a direct view
     const void* in_ptr = nullptr;  // direct device pointer (nullptr -> in_buf)

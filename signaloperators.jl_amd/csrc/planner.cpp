@@ -303,6 +303,19 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = x.dtype;
             break;
         }
+        case SO_NODE_MOVSUM: {  // sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart; DESIGN.md "Moving sums")
+            const std::string where = "node " + std::to_string(i) + ": Movsum ";
+            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            if (nd.l0 < 0 || nd.l1 < 0)
+                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            if (nd.i0 < 0 || nd.i0 > 2) fail(SO_ERR_INVALID, where + "is a sum (0), a mean (1) or an rms (2), not " + std::to_string(nd.i0));
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
+            N.nch = x.nch;
+            N.dtype = SO_F64;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -917,7 +930,8 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         out.push_back({r, add_expr(e)});
         return out;
     }
-    case SO_NODE_MOVING: {
+    case SO_NODE_MOVING:
+    case SO_NODE_MOVSUM: {
         // a stage: the frames anybody reads, computed from those frames of the child plus `back` before and `ahead` after;
         // the result is a plain buffer for whoever consumes it (process_moving, stages.cpp)
         if (dry) {
@@ -926,7 +940,7 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             out.push_back({r, mk_const(0.0, N.dtype)});
             return out;
         }
-        const int sid = stage_for(ni, ST_MOVING);
+        const int sid = stage_for(ni, N.nd.kind == SO_NODE_MOVSUM ? ST_MOVSUM : ST_MOVING);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

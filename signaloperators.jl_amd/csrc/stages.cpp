@@ -4,7 +4,7 @@
 //
 // Map (routine -- what it decides -- the Stage fields it writes):
 //   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
-//                            process_sample_at, process_comb, process_moving (input: stage_input)
+//                            process_sample_at, process_comb, process_moving (Moving and Movsum) (input: stage_input)
 //   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
 //                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
 //     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
@@ -595,6 +595,10 @@ void Plan::process_comb(int sid) {
 // child's frames [max(0, base - back), min(len, need + ahead)), taken like SampleAt's table (stage_input): in_base is the
 // child frame the input starts at.  The long form owns its block maxima and table besides, every entry written by the
 // execute that reads it (k_moving.hip), so nothing clears them.
+// MovingSum / MovingMean / MovingRMS (ST_MOVSUM) take the same span: their summation tree is fixed by x's own frame numbers,
+// which in_base hands to the kernel, so a window computes the whole result's bits.  The long form's block totals and
+// dyadic nodes cover the aligned blocks that hold an input frame; an entry whose block lies partly outside the input is
+// never part of a cover, which holds whole blocks between a window's first and last frame (k_movsum.hip).
 void Plan::process_moving(int sid) {
     const int ni = stages[sid].node;
     const int xk = nodes[ni].kids[0];
@@ -606,18 +610,24 @@ void Plan::process_moving(int sid) {
     const int64_t c0 = base > back ? base - back : 0;
     int64_t c1 = ahead < BIG - need ? need + ahead : BIG;
     if (!isinf_(nodes[xk].len)) c1 = std::min(c1, nodes[xk].len.n);
-    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": Moving looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
+    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": " + (stages[sid].kind == ST_MOVSUM ? "Movsum" : "Moving") + " looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
     stages[sid].base = base;
     stages[sid].in_base = c0;
     bufs[stages[sid].out_buf].frame0 = base;
     if (c0 > 0) check_frames(xk, c0);
     stage_input(sid, lower(xk, Rect{0, c1 - c0, 0, nch}, Map{1, c0, 1, 0}), c1 - c0, nch, nodes[xk].dtype);
-    const int64_t entries = moving_scratch(c1 - c0, back, ahead);
+    const bool sum = stages[sid].kind == ST_MOVSUM;
+    const int64_t entries = sum ? movsum_scratch(c0, c1 - c0, back, ahead) : moving_scratch(c1 - c0, back, ahead);
     if (entries > 0) {
         const int b = raw_buf((size_t)entries * (size_t)nch * 8);
         stages[sid].aux_buf = b;
     }
-    if (std::getenv("SIGOPS_DEBUG_PLAN"))
+    if (sum && std::getenv("SIGOPS_DEBUG_PLAN"))
+        std::fprintf(stderr, "[sigops] Movsum stage %d: %s over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, %s form (%lld table entries a channel, %d levels), x %s\n", sid,
+                     nodes[ni].nd.i0 == 0 ? "sum" : nodes[ni].nd.i0 == 1 ? "mean" : "rms", (long long)back, (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
+                     entries > 0 ? "long" : "short", (long long)entries, entries > 0 ? movsum_levels(c0, c1 - c0, back, ahead) : 0,
+                     stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+    else if (std::getenv("SIGOPS_DEBUG_PLAN"))
         std::fprintf(stderr, "[sigops] Moving stage %d: %s over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, %s form, x %s\n", sid,
                      nodes[ni].nd.i0 ? "min" : "max", (long long)back, (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
                      entries > 0 ? "long" : "short", stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
@@ -630,7 +640,8 @@ void Plan::process_moving(int sid) {
 // stages[sid] and re-take a `Stage&` after the last such call.  `nodes` is sized once (build_nodes): a `Node&` stays valid.
 void Plan::process_stage(int sid) {
     switch (stages[sid].kind) {
-    case ST_MOVING: return process_moving(sid);
+    case ST_MOVING:
+    case ST_MOVSUM: return process_moving(sid);
     case ST_SAMPLEAT: return process_sample_at(sid);
     case ST_COMB:
     case ST_CUMSUM: return process_comb(sid);

@@ -437,6 +437,10 @@ def _streamable(x):
     if isinstance(x, S.MovingSignal):
         S.error("BlockStream: MovingMax / MovingMin would have to keep the `back` input frames of its window from one push "
                 "to the next and hold `ahead` output frames back, and that is not built; not streamable")
+    if isinstance(x, S.MovingSumSignal):
+        S.error("BlockStream: MovingSum / MovingMean / MovingRMS would have to keep the `back` input frames of its window from one "
+                "push to the next, hold `ahead` output frames back and keep its place in the summation tree, and that is not "
+                "built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

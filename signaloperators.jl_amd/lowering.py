@@ -263,6 +263,9 @@ def _demand(x, n, out, skip=0):
     elif isinstance(x, S.MovingSignal):
         # the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come along
         _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
+    elif isinstance(x, S.MovingSumSignal):
+        # as for MovingSignal: the window of the last frame reaches `ahead` frames further
+        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -559,6 +562,11 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_MOVING)
             r.update(l0=s.back, l1=s.ahead, i0=1 if s.is_min else 0, children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.MovingSumSignal):
+            c = rec(s.signal)
+            r = common(s, K.NODE_MOVSUM)
+            r.update(l0=s.back, l1=s.ahead, i0=s.op, children=(c,))
             idx = lw.add(**r)
         elif isinstance(s, S.CumsumSignal):
             c = rec(s.signal)

@@ -604,6 +604,31 @@ class MovingSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class MovingSumSignal(AbstractSignal):
+    """`MovingSum(x, w)` / `MovingMean(x, w)` / `MovingRMS(x, w)`: per channel the sum (the mean, the root of the mean square)
+    of `x` over the frames `[n - back, n + ahead]`, clipped to the signal, over one fixed summation tree (no reference
+    counterpart; include/sigops.h SO_NODE_MOVSUM, DESIGN.md "Moving sums").  It has the length, frame rate and channels of
+    `x` and is Float64.  `op`: 0 sum, 1 mean, 2 rms."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x, back, ahead, op):
+        self.signal = x
+        self.children = (x,)
+        self.back = int(back)
+        self.ahead = int(ahead)
+        self.op = int(op)
+        self.fs = x.fs
+        self.nch = x.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -981,6 +1006,10 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return MovingSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.is_min)
+    if isinstance(x, MovingSumSignal):  # the same two rules
+        if known:
+            return _resample(x, fs, bs)
+        return MovingSumSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.op)
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1337,6 +1366,50 @@ MovingMin.__doc__ = """`MovingMin(x, w, *, ahead=0, center=False)`, curried `x |
 mirror image of `MovingMax`: the least sample of the clipped window under the same order, so `-0.0` beats `+0.0`, NaN
 propagates, and the result equals `-MovingMax(-x)` bit for bit.  Window, units, result type, `stream`, `BlockStream` and
 shards as for `MovingMax`."""
+
+
+# --------------------------------------------------------------------------
+# MovingSum / MovingMean / MovingRMS: sliding sums (no reference counterpart)
+def _MovingSum(what, op, x, w, ahead, center):
+    m = _Moving(what, False, x, w, ahead, center)  # (the window's rules and refusals, under this construct's name)
+    return MovingSumSignal(m.signal, m.back, m.ahead, op)
+
+
+def _moving_sum_ctor(what, op):
+    def ctor(*args, ahead=None, center=False):
+        if len(args) == 1:
+            w = args[0]
+            return Curried(lambda x: _MovingSum(what, op, x, w, ahead, center))
+        if len(args) != 2:
+            error(f"{what}(x, w) expected")
+        return _MovingSum(what, op, args[0], args[1], ahead, center)
+
+    ctor.__name__ = ctor.__qualname__ = what
+    return ctor
+
+
+MovingSum = _moving_sum_ctor("MovingSum", 0)
+MovingSum.__doc__ = """`MovingSum(x, w, *, ahead=0, center=False)`, curried `x | MovingSum(w, ahead=...)`: the sliding-window sum.  With
+`back = w - 1 - ahead`, frame n of a channel is the sum of `x[k]` over `max(0, n - back) <= k <= min(N - 1, n + ahead)`: the
+window is clipped to the signal, and the result has the length, rate and channels of `x` and is Float64 (a Float32 `x`
+widens exactly).  `w`, `ahead` and `center` as for `MovingMax`: whole frames, a `frames` quantity or a time converted with
+the rate of `x`; `0 <= ahead <= w - 1`; `center=True` is `ahead = (w - 1) // 2`; the default is the causal window.
+Floating-point addition does not associate, so the sum is taken over ONE tree that the absolute frame numbers, `back` and
+`ahead` fix (tests/movingsum_ref.py; DESIGN.md "Moving sums"): runs of 16 frames, a Kogge-Stone scan over the runs of a
+segment of up to 1024 frames, a suffix, whole segments and a prefix joined -- no partial sum is ever subtracted, so nothing
+cancels, and windows, `stream` blocks and the whole sink agree bit for bit where `x` does.  What lies outside the signal
+counts as `-0.0`, the additive identity: a window of only `-0.0` sums to `-0.0`.  The dependence is local: a window or a
+`stream` block computes its own frames from its own range of `x` plus `back` frames before and `ahead` after, and an `x`
+of infinite length is accepted.  `BlockStream` and multi-GPU shards refuse the node."""
+MovingMean = _moving_sum_ctor("MovingMean", 1)
+MovingMean.__doc__ = """`MovingMean(x, w, *, ahead=0, center=False)`, curried `x | MovingMean(w, ...)`: `MovingSum` divided by the number of
+frames of the window that lie inside the signal (one IEEE division by that count as a Float64), so an edge frame is the
+mean of what is there.  Window, units, result type, `stream`, `BlockStream` and shards as for `MovingSum`."""
+MovingRMS = _moving_sum_ctor("MovingRMS", 2)
+MovingRMS.__doc__ = """`MovingRMS(x, w, *, ahead=0, center=False)`, curried `x | MovingRMS(w, ...)`: the root of the mean square over the
+window: the `MovingSum` tree over `x[k] * x[k]` (the product formed in Float64, exact for a Float32 `x`), divided by the
+frames of the clipped window, and the square root of that, each rounded once.  Window, units, result type, `stream`,
+`BlockStream` and shards as for `MovingSum`."""
 
 
 # --------------------------------------------------------------------------

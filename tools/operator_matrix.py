@@ -58,6 +58,14 @@ cases = {
     "movingmax 480 ahead": lambda: so.MovingMax(X, 480, center=True),
     "movingmax 48000": lambda: so.MovingMax(X, 48000),
     "movingmin 480 f32": lambda: so.MovingMin(so.Signal(x.t().to(torch.float32).t(), fs), 480),
+    # `MovingSum(x, w)` / `MovingMean` / `MovingRMS` (include/sigops.h SO_NODE_MOVSUM, csrc/k_movsum.hip): 480 frames is the
+    # one-launch form (the tile, its halo and the lead-in to a multiple of the segment in LDS, two scans); the rms squares at
+    # the load and divides and takes the root at the store; 48000 frames is the long form (block totals, the dyadic nodes'
+    # levels, two images of three blocks a tile and the cover walk); the yardsticks are `copy (Until)` and `movingmax 480`
+    "movingsum 480": lambda: so.MovingSum(X, 480),
+    "movingrms 480": lambda: so.MovingRMS(X, 480),
+    "movingmean 480 ahead": lambda: so.MovingMean(X, 480, center=True),
+    "movingsum 48000": lambda: so.MovingSum(X, 48000),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
     "Amplify(sin)": lambda: X | so.Amplify(tone) | so.Until(n * so.frames),
     "Mix(x, y)": lambda: so.Mix(X, Y),
