@@ -86,7 +86,8 @@ typedef enum so_kind {
     SO_NODE_COMB = 13,    /* Comb / Allpass: a feedback delay line of D frames (no reference counterpart) */
     SO_NODE_CUMSUM = 14,  /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
     SO_NODE_MOVING = 15,  /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
-    SO_NODE_MOVSUM = 16   /* MovingSum / MovingMean / MovingRMS: sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart) */
+    SO_NODE_MOVSUM = 16,  /* MovingSum / MovingMean / MovingRMS: sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart) */
+    SO_NODE_RECUR = 17    /* Recur / OnePole / Smooth / PeakDecay: the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -300,6 +301,19 @@ typedef enum so_rskind {
  *            mean y = s / cnt, rms y = sqrt(s / cnt), each operation rounded once.  The node has x's length, frame rate
  *            and channels and is Float64.  MovingSum(x, w, ahead=a): l0 = w - 1 - a, l1 = a.  Not exactly one child,
  *            l0 < 0, l1 < 0 or i0 outside {0, 1, 2} is SO_ERR_INVALID; an integer child SO_ERR_UNSUPPORTED.
+ *  RECUR     one child: child 0 = b, d0 = the constant a (finite)   two children: child 0 = a, child 1 = b
+ *            b finite, Float32 / Float64; a Float32 / Float64 of 1 channel (every channel of b reads it) or of b's, infinite
+ *            or at least as long as b   i0 = op: 0 affine, 1 max-decay.
+ *            Per channel y[0] = b[0], y[n] = J(a[n], y[n-1], b[n]) in Float64 (Float32 inputs widen exactly), with m = a * v
+ *            rounded once and J(a, v, w) = m + w rounded once more, never fused (op 0), or the greater of m and w, NaN if
+ *            either is (op 1) -- over ONE tree that depends on the frame index only, Cumsum's, on pairs (product of the a,
+ *            value): runs of 16 frames from the first sample itself, an inclusive Kogge-Stone scan over the 64 run totals
+ *            of a tile of 1024 frames, a sequential carry over the 16 tiles of a chunk and over the chunks of 16384 frames
+ *            ("Recur"; tests/recur_ref.py is the definition).  A constant a runs the multiplications a row of it
+ *            would.  The node has b's length, frame rate and channels and is Float64.  Recur(a, b): i0 = 0; OnePole and
+ *            Smooth: i0 = 0 with b = (1 - a) x; PeakDecay(x, r): i0 = 1, a = r, b = x.  i0 outside {0, 1}, a child count
+ *            other than 1 or 2, a non-finite d0 in the one-child form or a channel count of a that is neither 1 nor b's is
+ *            SO_ERR_INVALID; an infinite b or a finite a shorter than b SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

@@ -101,6 +101,7 @@ static const char* stage_step_name(const Stage& S) {
     case ST_CUMSUM: return "k_cumsum";
     case ST_MOVING: return "k_moving";
     case ST_MOVSUM: return "k_movsum";
+    case ST_RECUR: return "k_recur";
     default: return "k_sumsq";
     }
 }
@@ -136,6 +137,11 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
     case ST_MOVSUM:  // the frames read where x lies (the long form's further reads, the tile halos and lead-ins left out), one Float64 written
         return (S.in_frames * kid_esz(0) + (S.need - S.base) * 8) * (int64_t)N.nch;
+    case ST_RECUR: {  // per sample: b read twice where it lies (the totals' pass and the scan's), a row of a twice as Float64, one Float64 written
+        const bool row = N.kids.size() == 2;
+        const int64_t a_rows = !row ? 0 : S.pos_pitch == 0 ? 1 : N.nch;
+        return S.need * ((int64_t)N.nch * (2 * kid_esz(row ? 1 : 0) + 8) + a_rows * 16);
+    }
     default: return (S.need - S.base) * N.nch * esz;
     }
 }
@@ -522,7 +528,7 @@ static View stage_in(Plan* P, const Stage& S, int nch, int dtype) {
 // SampleAt, Comb and Cumsum, whose kernels store Float64 only, get 8 bytes for both: their nodes are Float64 (build_nodes),
 // and plan_create lets only a periodic resampler or a filter narrow, so alias_narrow is false where one of them is aliased.
 // Moving stores its node's type, Float32 or Float64, and is aliased only to a result of that type.
-// Movsum stores Float64 like Cumsum: its node is Float64.
+// Movsum and Recur store Float64 like Cumsum: their nodes are Float64.
 // A member of an RsBatch is never the aliased stage (fuse_plain_sos skips it): k_rsos_batch's members write windows or buffers.
 static View stage_out(Plan* P, int sid, void* outp) {
     const Stage& S = P->stages[sid];
@@ -826,6 +832,40 @@ static int run_cumsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
     const int nl = launch_cumsum(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
     if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Cumsum: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
+    return nl;
+}
+
+static int run_recur(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const bool row = N.kids.size() == 2;
+    const int bdt = P->nodes[N.kids[row ? 1 : 0]].dtype;
+    const View in = stage_in(P, S, N.nch, bdt), out = stage_out(P, s.idx, outp);
+    RecurArgs a{};
+    a.b = in.d;
+    a.bcs = in.pitch;
+    a.bfs = S.x_fstride;
+    a.b_f32 = bdt == SO_F32;
+    if (!row) {
+        a.ac = N.nd.d0;
+    } else if (S.pos_array_node >= 0) {
+        a.a = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
+        a.acs = S.pos_pitch;
+    } else {
+        const Buf& b = P->bufs[S.pos_buf];
+        a.a = (const double*)b.d;
+        a.acs = S.pos_pitch == 0 ? 0 : b.pitch;
+    }
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.n = S.need;
+    a.nch = N.nch;
+    a.op = N.nd.i0;
+    a.tot_pitch = cumsum_totals(S.need);
+    a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
+    const int nl = launch_recur(a, st);
+    // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Recur: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
     return nl;
 }
 
@@ -1202,6 +1242,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 case ST_CUMSUM: nl = run_cumsum(P, s, outp, st); break;
                 case ST_MOVING: nl = run_moving(P, s, outp, st); break;
                 case ST_MOVSUM: nl = run_movsum(P, s, outp, st); break;
+                case ST_RECUR: nl = run_recur(P, s, outp, st); break;
                 case ST_SOS: nl = run_sos(P, s, outp, st); break;
                 case ST_RESAMPLE: nl = run_resample(P, s, outp, st); break;
                 default: nl = run_norm(P, s, outp, st); break;

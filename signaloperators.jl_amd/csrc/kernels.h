@@ -141,6 +141,29 @@ struct CumsumArgs {
 // the chunk totals a channel of n frames needs: one for every chunk that has a chunk behind it
 constexpr int64_t cumsum_totals(int64_t n) { return n <= kCumsumChunk ? 0 : (n - 1) / kCumsumChunk; }
 int launch_cumsum(const CumsumArgs& a, hipStream_t st);
+// Recur / OnePole / Smooth / PeakDecay (k_recur.hip, -ffp-contract=off): per channel the first-order scan
+// y[n] = J(a[n], y[n-1], b[n]), y[0] = b[0], in Float64 over Cumsum's tree (the constants above; DESIGN.md "Recur";
+// tests/recur_ref.py is the definition).  J(a, v, w) with m = a * v rounded once: op 0 m + w (never an FMA), op 1 the
+// greater of m and w, NaN if either is.  An element of the scan is a pair (product of a, value); runs of kCumsumRun frames
+// left to right, a Kogge-Stone scan over the 64 run totals of a tile, sequential carries over the kCumsumTiles tiles of a
+// chunk and over the chunks.  Reduce-then-scan, no workgroup waits for another: k_recur_totals (the chunk-local last pair
+// of every chunk but the last -> tot), k_recur_carry (tot -> the carry C behind every chunk, in place, one workgroup per
+// channel), k_recur_scan (recomputes the chunk, applies C, stores).  A signal of one chunk is one launch.  Strides in
+// elements.  Returns the number of launches, -1 when the shape cannot be launched.
+struct RecurArgs {
+    const void* b;    // element (n, c) at b[n * bfs + c * bcs]
+    int64_t bfs, bcs;
+    const double* a;  // a row of coefficients per channel, a[n + c * acs] (acs 0: one row for every channel); nullptr: the constant ac
+    int64_t acs;
+    double ac;
+    double* y;        // y[n + c * ycs]
+    int64_t ycs;
+    double* tot;      // [nch][tot_pitch][2] scratch, tot_pitch >= cumsum_totals(n): (Q[last], u[last]) of a chunk, then (Q[last], C)
+    int64_t tot_pitch;
+    int64_t n;
+    int32_t nch, b_f32, op;
+};
+int launch_recur(const RecurArgs& a, hipStream_t st);
 // MovingMax / MovingMin (k_moving.hip): output j in [0, n_out) of a channel is the greatest (least) of the input frames
 // [j + off - back, j + off + ahead] clipped to [0, n_in), under the order -Inf < .. < -0.0 < +0.0 < .. < +Inf, NaN if any of
 // them is NaN; the result has the input's type and is a bit copy of that sample.  Compared on a monotone integer key, so any

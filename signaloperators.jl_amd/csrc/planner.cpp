@@ -316,6 +316,30 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = SO_F64;
             break;
         }
+        case SO_NODE_RECUR: {  // the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart; DESIGN.md "Recur")
+            const std::string where = "node " + std::to_string(i) + ": Recur ";
+            if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is affine (0) or max-decay (1), not " + std::to_string(nd.i0));
+            if (N.kids.size() != 1 && N.kids.size() != 2)
+                fail(SO_ERR_INVALID, where + "takes one child, the signal b (the constant a in d0), or two, a and b (" + std::to_string(N.kids.size()) + " given)");
+            const bool row = N.kids.size() == 2;
+            Node& b = kid(row ? 1 : 0);
+            if (!row && !std::isfinite(nd.d0)) fail(SO_ERR_INVALID, where + "takes a finite constant a");
+            if (isinf_(b.len)) fail(SO_ERR_LENGTH, where + "needs a signal b of known, finite length (use `Until`)");
+            if (b.dtype != SO_F32 && b.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal b (integer sample types are not lowered)");
+            if (row) {
+                Node& a = kid(0);
+                if (a.dtype != SO_F32 && a.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal a (integer sample types are not lowered)");
+                if (a.nch != 1 && a.nch != b.nch)
+                    fail(SO_ERR_INVALID, where + "coefficients a have " + std::to_string(a.nch) + " channels: 1 or b's " + std::to_string(b.nch) + " expected");
+                if (!isinf_(a.len) && a.len.n < b.len.n)
+                    fail(SO_ERR_LENGTH, where + "coefficients a have " + std::to_string(a.len.n) + " frames, fewer than b's " + std::to_string(b.len.n));
+            }
+            N.len = b.len;
+            N.nch = b.nch;
+            N.dtype = SO_F64;
+            if (row && !N.short_skip) N.short_skip = b.short_skip;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -916,6 +940,29 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             return out;
         }
         const int sid = stage_for(ni, N.nd.kind == SO_NODE_CUMSUM ? ST_CUMSUM : ST_COMB);
+        use_stage(stages[sid], r, m);
+        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
+        Expr e;
+        e.op = E_LOAD;
+        e.dtype = N.dtype;
+        e.leaf = mk_leafmap(m);
+        e.leaf.fstride = 1;
+        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
+        e.leaf.dtype = N.dtype;
+        e.leaf.buf = stages[sid].out_buf;
+        e.mono = (m.sc == 0);
+        out.push_back({r, add_expr(e)});
+        return out;
+    }
+    case SO_NODE_RECUR: {
+        // a stage like Cumsum's: the recurrence starts at frame 0, so the stage computes the frames [0, need) whoever reads
+        // it, from both inputs over the same frames (process_recur, stages.cpp)
+        if (dry) {
+            for (int k : N.kids) check_frames(k, m.sf ? r.b + m.df : m.df + 1);
+            out.push_back({r, mk_const(0.0, N.dtype)});
+            return out;
+        }
+        const int sid = stage_for(ni, ST_RECUR);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

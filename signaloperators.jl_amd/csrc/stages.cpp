@@ -4,7 +4,7 @@
 //
 // Map (routine -- what it decides -- the Stage fields it writes):
 //   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
-//                            process_sample_at, process_comb, process_moving (Moving and Movsum) (input: stage_input)
+//                            process_sample_at, process_comb, process_moving (Moving and Movsum), process_recur (input: stage_input, second_input)
 //   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
 //                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
 //     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
@@ -536,7 +536,7 @@ void Plan::stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, in
 void Plan::process_sample_at(int sid) {
     const int ni = stages[sid].node;
     const int xk = nodes[ni].kids[0], pk = nodes[ni].kids[1];
-    const int nch = nodes[ni].nch, pch = nodes[pk].nch, xdt = nodes[xk].dtype;
+    const int nch = nodes[ni].nch, xdt = nodes[xk].dtype;
     const int64_t Nx = nodes[xk].len.n;
     const int64_t need = stages[sid].need;
     stages[sid].processed = true;
@@ -546,24 +546,30 @@ void Plan::process_sample_at(int sid) {
     bufs[stages[sid].out_buf].frame0 = base;
     if (base > 0) check_frames(pk, base);
     stage_input(sid, lower(xk, Rect{0, Nx, 0, nch}, Map{1, 0, 1, 0}), Nx, nch, xdt);
-    {
-        const std::vector<Piece> ps = lower(pk, Rect{0, need - base, 0, pch}, Map{1, base, 1, 0});
-        Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
-        if (ps.size() == 1 && plain_load(exprs[ps[0].e], SO_F64, ps[0].r.c1 - ps[0].r.c0, true, true) && exprs[ps[0].e].array_node >= 0) {
-            const Expr& e = exprs[ps[0].e];
-            S.pos_array_node = e.array_node;
-            S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
-            S.pos_offset = leaf_offset(e.leaf);
-            count_array(e.array_node);
-        } else {
-            const int b = new_buf(need - base, pch, SO_F64);
-            const int step = emit_pointwise(ps, b, SO_F64);
-            Stage& S2 = stages[sid];
-            S2.pos_buf = b;
-            S2.pos_pitch = pch == 1 ? 0 : -1;  // -1: pitch of pos_buf
-            S2.pos_offset = 0;
-            S2.pos_pw_step = step;
-        }
+    second_input(sid, pk, base, need - base);
+}
+
+// The second input of a stage -- SampleAt's positions, Recur's coefficients -- over `frames` frames from `base` of child
+// `kid`: a Float64 array with unit frame stride read in place, anything else (a formula, a Float32 array, another stage's
+// buffer) one pointwise step into a Float64 buffer (Stage::pos_*).  One channel serves every channel of the stage (pitch 0).
+void Plan::second_input(int sid, int kid, int64_t base, int64_t frames) {
+    const int pch = nodes[kid].nch;
+    const std::vector<Piece> ps = lower(kid, Rect{0, frames, 0, pch}, Map{1, base, 1, 0});
+    Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
+    if (ps.size() == 1 && plain_load(exprs[ps[0].e], SO_F64, ps[0].r.c1 - ps[0].r.c0, true, true) && exprs[ps[0].e].array_node >= 0) {
+        const Expr& e = exprs[ps[0].e];
+        S.pos_array_node = e.array_node;
+        S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
+        S.pos_offset = leaf_offset(e.leaf);
+        count_array(e.array_node);
+    } else {
+        const int b = new_buf(frames, pch, SO_F64);
+        const int step = emit_pointwise(ps, b, SO_F64);
+        Stage& S2 = stages[sid];
+        S2.pos_buf = b;
+        S2.pos_pitch = pch == 1 ? 0 : -1;  // -1: pitch of pos_buf
+        S2.pos_offset = 0;
+        S2.pos_pw_step = step;
     }
 }
 
@@ -589,6 +595,36 @@ void Plan::process_comb(int sid) {
     if (std::getenv("SIGOPS_DEBUG_PLAN"))
         std::fprintf(stderr, "[sigops] %s stage %d: %s%lld, frames [0,%lld) x %d channels, x %s\n", cumsum ? "Cumsum" : "Comb", sid, cumsum ? "chunk totals a channel " : "D=",
                      (long long)(cumsum ? cumsum_totals(need) : nodes[ni].nd.l0), (long long)need, nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+}
+
+// Recur: Cumsum's rule -- the recurrence starts at frame 0, so the stage computes the frames [0, need) of its buffer (base =
+// 0) whatever window reads it -- with two inputs over those frames: b taken like Cumsum's x (stage_input), and, where a is
+// a signal, the coefficients taken like SampleAt's positions (second_input).  The stage owns two Float64 per (chunk that
+// has a chunk behind it, channel) besides: the chunk's last (Q, u), every entry written by the execute that reads it
+// (k_recur.hip), so nothing clears them.
+void Plan::process_recur(int sid) {
+    const int ni = stages[sid].node;
+    const bool row = nodes[ni].kids.size() == 2;
+    const int bk = nodes[ni].kids[row ? 1 : 0];
+    const int nch = nodes[ni].nch;
+    const int64_t need = stages[sid].need;
+    stages[sid].processed = true;
+    if (need <= 0) return;
+    stages[sid].base = stages[sid].in_base = 0;
+    bufs[stages[sid].out_buf].frame0 = 0;
+    stage_input(sid, lower(bk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[bk].dtype);
+    if (row) second_input(sid, nodes[ni].kids[0], 0, need);
+    if (cumsum_totals(need) > 0) {
+        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 16);
+        stages[sid].aux_buf = b;
+    }
+    if (std::getenv("SIGOPS_DEBUG_PLAN")) {
+        const Stage& S = stages[sid];
+        const std::string a = !row ? "the constant " + std::to_string(nodes[ni].nd.d0)
+                                   : std::string(S.pos_array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.pos_pitch == 0 ? ", one row for every channel" : "");
+        std::fprintf(stderr, "[sigops] Recur stage %d: %s, chunk totals a channel %lld, frames [0,%lld) x %d channels, b %s, a %s\n", sid, nodes[ni].nd.i0 ? "max-decay" : "affine",
+                     (long long)cumsum_totals(need), (long long)need, nch, S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place", a.c_str());
+    }
 }
 
 // MovingMax / MovingMin: the dependence is local, so the stage computes the frames [base, need) anybody reads from the
@@ -645,6 +681,7 @@ void Plan::process_stage(int sid) {
     case ST_SAMPLEAT: return process_sample_at(sid);
     case ST_COMB:
     case ST_CUMSUM: return process_comb(sid);
+    case ST_RECUR: return process_recur(sid);
     case ST_RESAMPLE: return process_resample(sid);
     case ST_SOS: return process_sos(sid);
     default: return process_norm(sid);

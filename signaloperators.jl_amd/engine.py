@@ -441,6 +441,9 @@ def _streamable(x):
         S.error("BlockStream: MovingSum / MovingMean / MovingRMS would have to keep the `back` input frames of its window from one "
                 "push to the next, hold `ahead` output frames back and keep its place in the summation tree, and that is not "
                 "built; not streamable")
+    if isinstance(x, S.RecurSignal):
+        S.error("BlockStream: Recur / OnePole / Smooth / PeakDecay would have to carry its last value (and its place in the "
+                "tree of the scan) from one push to the next, and that is not built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -260,6 +260,10 @@ def _demand(x, n, out, skip=0):
     elif isinstance(x, (S.CombSignal, S.CumsumSignal)):
         # the recurrence (the sum) starts at frame 0: the frames before a window are computed too
         _demand(x.signal, capped(x.signal, n), out, 0)
+    elif isinstance(x, S.RecurSignal):
+        # both inputs from frame 0: the recurrence starts there whatever window reads it
+        for c in x.children:
+            _demand(c, capped(c, n), out, 0)
     elif isinstance(x, S.MovingSignal):
         # the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come along
         _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
@@ -572,6 +576,12 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_CUMSUM)
             r.update(children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.RecurSignal):
+            # one child: b, the constant a in d0; two children: (a, b)
+            kids = tuple(rec(c) for c in s.children)
+            r = common(s, K.NODE_RECUR)
+            r.update(i0=s.op, d0=0.0 if s.a is None else s.a, children=kids)
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

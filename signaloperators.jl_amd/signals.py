@@ -629,6 +629,34 @@ class MovingSumSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class RecurSignal(AbstractSignal):
+    """`Recur(a, b)` / `OnePole` / `Smooth` / `PeakDecay`: per channel the first-order scan `y[n] = J(a[n], y[n-1], b[n])`,
+    `y[0] = b[0]`, over one fixed tree (no reference counterpart; include/sigops.h SO_NODE_RECUR, DESIGN.md "Recur").
+    `op` 0: `J = a y + b`; `op` 1: `J = max(a y, b)`.  The coefficient is the number `a` (then `coef` is None) or the signal
+    `coef` of one channel or of `b`'s.  It has the length, frame rate and channels of `b` and is Float64."""
+
+    evaltrait = "computed"
+
+    def __init__(self, a, b, op):
+        self.signal = b
+        if isinstance(a, AbstractSignal):
+            self.coef, self.a = a, None
+            self.children = (a, b)
+        else:
+            self.coef, self.a = None, float(a)
+            self.children = (b,)
+        self.op = int(op)
+        self.fs = b.fs
+        self.nch = b.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -1010,6 +1038,10 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return MovingSumSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.op)
+    if isinstance(x, RecurSignal):  # Comb's two rules: the recurrence runs over frames, whatever rate they have
+        if known:
+            return _resample(x, fs, bs)
+        return RecurSignal(x.a if x.coef is None else ToFramerate(x.coef, fs, bs), ToFramerate(x.signal, fs, bs), x.op)
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1297,6 +1329,187 @@ def _Integrate(x):
 Integrate = Curried(_Integrate)
 Integrate.__doc__ = """`Integrate(x)`, piped `x | Integrate`: the integral of `x` over time, `Cumsum(x)` times the Float64 constant
 `1.0 / framerate(x)` (one more rounding a sample, through the map path)."""
+
+
+# --------------------------------------------------------------------------
+# Recur / OnePole / Smooth / PeakDecay: first-order scans (no reference counterpart)
+def _Recur(what, op, a, b):
+    """`what` names the construct in a refusal: "Recur", or "OnePole (Recur)" and so on for the wrappers"""
+    b = _assignal(b)
+    n = nframes(b)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal b must have a known, finite length (use `Until`): the recurrence starts at frame 0")
+    if b.dtype not in (F32, F64):
+        error(f"{what}: the signal b must be Float32 or Float64 (use `ToEltype`)")
+    if _real_number(a):
+        if not math.isfinite(a):
+            error(f"{what}: the coefficient a must be a finite number or a signal, not {a!r}")
+        return RecurSignal(float(a), b, op)
+    if isinstance(a, (bool, np.bool_, Quantity, str)) or a is None:
+        error(f"{what}: the coefficient a must be a number or a signal, not {a!r}")
+    a = _assignal(a)
+    if a.dtype not in (F32, F64):
+        error(f"{what}: the coefficient signal a must be Float32 or Float64 (use `ToEltype`)")
+    if a.nch not in (1, b.nch):
+        error(f"{what}: the coefficient signal a has {a.nch} channels; 1 or b's {b.nch} expected")
+    if a.fs is not None and b.fs is not None and a.fs != b.fs:
+        error(f"{what}: the coefficient signal a has a frame rate of {a.fs} Hz and b one of {b.fs} Hz (use `ToFramerate`)")
+    if a.fs is None and b.fs is not None:
+        a = ToFramerate(a, b.fs)
+    elif b.fs is None and a.fs is not None:
+        b = ToFramerate(b, a.fs)
+    na = nframes(a)
+    if na is None or (not isknowninf(na) and na < n):
+        error(f"{what}: the coefficient signal a ({'an unknown number of' if na is None else na} frames) must be infinite or at least as long as b ({n} frames)")
+    return RecurSignal(a, b, op)
+
+
+def Recur(*args):
+    """`Recur(a, b)`, curried `b | Recur(a)`: the first-order linear recurrence `y[n] = a[n] y[n-1] + b[n]`, `y[0] = b[0]`
+    per channel in Float64 -- a smoother whose time constant is a signal, a leaky integrator, a decay envelope with a
+    controlled rate.  `a` is a real number, or a Float32 / Float64 signal of one channel (every channel of `b` reads it) or of
+    `b`'s channel count, infinite or at least as long as `b`.  A parallel scan rounds differently from a loop, so the node
+    fixes ONE tree that depends on the frame index only (Cumsum's: runs of 16 frames, a Kogge-Stone scan over the 64 runs of
+    a tile, sequential carries over the tiles of a chunk and over the chunks, on pairs (product of a, value); DESIGN.md
+    "Recur", tests/recur_ref.py), product and sum rounded on their own: a window, a `stream` block and the whole sink give
+    the same bits, and `Recur(1.0, x)` equals `Cumsum(x)` bit for bit.  A term `b[k]` reaches frame n through at most
+    `(n - k) + 2 (40 + chunks)` rounded operations, against the loop's `2 (n - k)`: the error is of the order of the loop's
+    own, relative to `S[n] = |a[n]| S[n-1] + |b[n]|`.  The node is meant for `|a| <= 1`: where
+    `|a| > 1` over hundreds of frames a product of the a can overflow and `Inf * 0` gives NaN where a loop would stay
+    finite.  There is no initial state: `y[-1]` is absent, not 0.  `b` must have a known, finite length.  `stream` over the
+    node recomputes the frames before every block (as over `Cumsum`); `BlockStream` and multi-GPU shards refuse the node."""
+    if len(args) == 1:
+        a = args[0]
+        return Curried(lambda b: _Recur("Recur", 0, a, b))
+    if len(args) != 2:
+        error("Recur(a, b) expected")
+    return _Recur("Recur", 0, args[0], args[1])
+
+
+def _rate_for(what, x, name):
+    if x.fs is None:
+        error(f"{what}: {name} needs the frame rate of x (use `ToFramerate`, or `Recur` with a coefficient per frame)")
+    return float(x.fs)
+
+
+def _coef_signal(what, name, x, v, fn):
+    """the coefficient sub-tree of a wrapper: the signal `v` at the rate of x, through the traced map `fn`"""
+    fs = _rate_for(what, x, f"{name} given as a signal")
+    v = _assignal(v)
+    if v.dtype not in (F32, F64):
+        error(f"{what}: the signal {name} must be Float32 or Float64 (use `ToEltype`)")
+    if v.fs is not None and v.fs != fs:
+        error(f"{what}: the signal {name} has a frame rate of {v.fs} Hz and x one of {fs} Hz (use `ToFramerate`)")
+    return _OperateOn(_map_code(Elementwise(fn)), [ToFramerate(v, fs)])
+
+
+def _lowpass(what, x, a):
+    """`y[n] = a y[n-1] + (1 - a) x[n]`: unit gain at DC.  A signal `a` scales x through a traced map, as Integrate builds its product"""
+    from .units import frames
+
+    if not isinstance(a, AbstractSignal):
+        return _Recur(what, 0, a, _OperateOn(MUL, [x, NumberSig(1.0 - a)]))
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal x must have a known, finite length (use `Until`): the recurrence starts at frame 0")
+    b = _OperateOn(_map_code(Elementwise(lambda c, v: (1.0 - c) * v)), [a, x])
+    return _Recur(what, 0, a, _Until(b, n * frames))
+
+
+def _OnePole(x, fc):
+    what = "OnePole (Recur)"
+    x = _assignal(x)
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    if isinstance(fc, Quantity) or _real_number(fc):
+        try:
+            hz = U.inHz(fc)
+        except ValueError:
+            error(f"{what}: the cutoff {fc} is not a frequency")
+        if not math.isfinite(hz) or hz < 0:
+            error(f"{what}: the cutoff must be a finite frequency >= 0, not {fc!r}")
+        return _lowpass(what, x, math.exp(-2.0 * math.pi * hz / _rate_for(what, x, "a cutoff in Hz")))
+    k = -2.0 * math.pi / _rate_for(what, x, "a cutoff in Hz")
+    return _lowpass(what, x, _coef_signal(what, "fc", x, fc, lambda f: np.exp(f * k)))
+
+
+def OnePole(*args):
+    """`OnePole(x, fc)`, curried `x | OnePole(fc)`: a one-pole low-pass with unit gain at DC,
+    `y[n] = a y[n-1] + (1 - a) x[n]`, `a = exp(-2 pi fc / framerate)`: `Recur(a, (1 - a) x)`.  `fc` is a frequency (a number
+    of Hz or a quantity; `math.exp` on the host) or a signal of Hz at the rate of `x` (`a` and `(1 - a) x` are then traced
+    maps on the device), of one channel or of `x`'s."""
+    if len(args) == 1:
+        fc = args[0]
+        return Curried(lambda x: _OnePole(x, fc))
+    if len(args) != 2:
+        error("OnePole(x, fc) expected")
+    return _OnePole(args[0], args[1])
+
+
+def _decay(what, name, x, t):
+    """`exp(-1 / (t framerate))` from the time `t` (a number of seconds or a time quantity); a time of 0 gives 0"""
+    if isinstance(t, Quantity) and not U.is_time(t):
+        error(f"{what}: {name} {t} is not a time")
+    sec = U.inseconds_raw(t) if isinstance(t, Quantity) else float(t)
+    if not math.isfinite(sec) or sec < 0:
+        error(f"{what}: {name} must be a finite time >= 0, not {t!r}")
+    fs = _rate_for(what, x, f"{name} given as a time")
+    return 0.0 if sec == 0 else math.exp(-1.0 / (sec * fs))
+
+
+def _Smooth(x, tau):
+    what = "Smooth (Recur)"
+    x = _assignal(x)
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    if isinstance(tau, Quantity) or _real_number(tau):
+        return _lowpass(what, x, _decay(what, "tau", x, tau))
+    k = -1.0 / _rate_for(what, x, "tau")
+    return _lowpass(what, x, _coef_signal(what, "tau", x, tau, lambda t: np.exp(k / t)))
+
+
+def Smooth(*args):
+    """`Smooth(x, tau)`, curried `x | Smooth(tau)`: `OnePole` by its time constant, `a = exp(-1 / (tau framerate))`: the step
+    response reaches `1 - 1/e` after `tau`.  `tau` is a time (a number of seconds or a quantity) or a signal of seconds at
+    the rate of `x`; `tau == 0` gives `a = 0`, `x` itself."""
+    if len(args) == 1:
+        tau = args[0]
+        return Curried(lambda x: _Smooth(x, tau))
+    if len(args) != 2:
+        error("Smooth(x, tau) expected")
+    return _Smooth(args[0], args[1])
+
+
+def _PeakDecay(x, release, r):
+    what = "PeakDecay (Recur)"
+    x = _assignal(x)
+    if (release is None) == (r is None):
+        error(f"{what}: give the release time or `r=`, the factor a frame, one of them")
+    if r is None:
+        if not (isinstance(release, Quantity) or _real_number(release)):
+            error(f"{what}: the release must be a time, not {release!r} (a factor per frame that is a signal goes to `r=`)")
+        r = _decay(what, "the release", x, release)
+    elif _real_number(r) and not 0.0 <= r <= 1.0:
+        error(f"{what}: a constant r must lie in [0, 1], not {r!r}")
+    return _Recur(what, 1, r, x)
+
+
+def PeakDecay(*args, r=None):
+    """`PeakDecay(x, release)`, curried `x | PeakDecay(release)`: the peak follower with instant attack and exponential
+    release, `y[n] = max(x[n], r y[n-1])`, `y[0] = x[0]` -- the companion of `MovingMax` in a limiter's side-chain.
+    `r = exp(-1 / (release framerate))` from the release time, or `r=` directly: a number in [0, 1] or a signal (`Recur`'s
+    rules for `a`).  The product is rounded once; a NaN in `x` or `r` makes the frames after it NaN; over the same tree as
+    `Recur`, so windows, `stream` blocks and the whole sink agree bit for bit."""
+    if len(args) == 0 and r is not None:
+        return Curried(lambda x: _PeakDecay(x, None, r))
+    if len(args) == 1 and r is None:
+        release = args[0]
+        return Curried(lambda x: _PeakDecay(x, release, None))
+    if len(args) == 1:
+        return _PeakDecay(args[0], None, r)
+    if len(args) != 2:
+        error("PeakDecay(x, release) or PeakDecay(x, r=...) expected")
+    return _PeakDecay(args[0], args[1], r)
 
 
 # --------------------------------------------------------------------------

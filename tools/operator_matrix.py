@@ -50,6 +50,14 @@ cases = {
     # per-frame increment (1.37 frames +- 20 %, a different trajectory per channel), `SampleAt` over `Cumsum`
     "cumsum": lambda: so.Cumsum(X),
     "vco": lambda: so.SampleAt(so.Signal(x[:2048], fs), so.Cumsum(so.Signal((1.37 + 0.2 * x.t().clamp(-1.0, 1.0).to(torch.float64)).t(), fs)), wrap=True),
+    # `Recur(a, b)` / `OnePole` / `PeakDecay` (include/sigops.h SO_NODE_RECUR, csrc/k_recur.hip): reduce-then-scan over Cumsum's
+    # tree on pairs; a constant a streams what `cumsum` streams (two reads and one write per sample), a coefficient row per
+    # channel (A, U[0.99, 1)) is read twice too: 40 bytes a sample against 24; `onepole` adds the map that scales x; the
+    # yardsticks are the `cumsum` and `copy (Until)` rows above
+    "recur const": lambda: so.Recur(0.999, X),
+    "recur signal": lambda: so.Recur(A(), X),
+    "onepole": lambda: so.OnePole(X, 1 * so.kHz),
+    "peakdecay": lambda: so.PeakDecay(X, 50 * so.ms),
     # `MovingMax(x, w)` / `MovingMin(x, w)` (include/sigops.h SO_NODE_MOVING, csrc/k_moving.hip): a window of 480 frames is the
     # one-launch form (a tile and its halo in LDS: 1 + 479 / 2048 reads and one write per sample), causal and centred; 48000
     # frames is the long form (block maxima, a sparse table, two blocks recomputed per tile: about three reads and one write);
@@ -127,6 +135,7 @@ cases = {
     "headline, noise leaf": lambda: so.Mix(tone, so.ToChannels(NOISE(), nch)) | so.Until(n * so.frames) | so.Filt(so.Bandstop, 0.5 * so.kHz, 2 * so.kHz) | so.ToFramerate(48 * so.kHz),
 }
 NOISE = lambda: so.Signal(so.randn, fs, rng=so.DeviceRNG(2024, 0))  # noqa: E731
+A = lambda: so.Signal((0.99 + 0.01 * torch.rand((nch, n), dtype=torch.float64, device="cuda")).t(), fs)  # noqa: E731
 # environment of a case while its plan is created (the planner reads its knobs then)
 case_env = {
     "noise expr hipRTC (mono)": {"SIGOPS_RANDN_NOFILL": "1", "SIGOPS_RTC": "1"},
