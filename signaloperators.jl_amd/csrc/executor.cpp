@@ -578,6 +578,10 @@ static void set_rsos_fixup(RsFixup& F, Plan* P, const Stage& S, const RsosItem& 
 }
 // "no non-finite chunk (range) yet" in every word of a SosGeom::bad / RsSos::bad array
 static void arm_bad(void* words, size_t n, hipStream_t st) { HIPCHECK((hipError_t)launch_fill_u32(words, n, 0x7f7f7f7fu, st)); }
+// after an execute that failed nobody knows what its launches left in the words: the next one arms them itself (run_rsos_fused)
+static void disarm_bad(Plan* P) {
+    for (const Stage& S : P->stages) S.bad_armed = false;
+}
 
 // The tuning aids' traces: the cycle stamps workgroup 0 of a launch left (waits for it), printed relative to the earliest, t0.
 static std::vector<long long> read_trace(const long long* d_trace, size_t trace_n, hipStream_t st, long long& t0) {
@@ -623,6 +627,12 @@ static void dump_rsos_trace(const long long* d_trace, size_t trace_n, const RsSo
             }
             std::fprintf(stderr, "\n");
         }
+    for (int w = 0; w < rs.nwaves && w < 16 && !counters; ++w) {  // the prologue of the first group (rsos_stamp_pro's columns)
+        const long long* q = &tr[((size_t)16 * kRsosTraceIters + w) * 8];
+        std::fprintf(stderr, "[rsos-trace-pro] w%02d", w);
+        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %lld", q[k] ? q[k] - t0 : -1);
+        std::fprintf(stderr, "\n");
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -937,9 +947,27 @@ static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View&
     rs.store_lo = S.rs.store_lo + g.store_lo;
     rs.mats = (const double*)P->bufs[S.rsos_mats_buf].d;
     rs.bad = nullptr;
+    const bool fixup = S.rsos_jrel_buf >= 0 && !std::getenv("SIGOPS_RSOS_NO_FIXUP");
+    int rearm = 0;
     if (S.bad_buf >= 0 && rs.nranges >= 1 && !std::getenv("SIGOPS_SOS_NOPOISON")) {
-        rs.bad = (int32_t*)P->bufs[S.bad_buf].d;
-        arm_bad(rs.bad, (size_t)N.nch, st);
+        // Two sets of words.  Direct launches alternate between them: k_rsos_fixup, which every execute ends with, leaves
+        // the other set armed (k_exact.hip), and the fill launch runs only where nobody has done that -- the plan's first
+        // execute, and the one after an execute that failed (disarm_bad).  A captured graph holds fixed arguments and
+        // k_sos_poison arms nothing: those executes use set 0 behind a fill of their own, as before.
+        int32_t* const words = (int32_t*)P->bufs[S.bad_buf].d;
+        const size_t nch = (size_t)N.nch;
+        if (fixup && !P->graph_plan && rs.nch == N.nch && P->bufs[S.bad_buf].bytes >= 2 * nch * 4) {
+            if (!S.bad_armed) {
+                arm_bad(words, 2 * nch, st);
+                S.bad_set = 0;
+            }
+            rs.bad = words + (S.bad_set ? nch : 0);
+            rearm = S.bad_set ? -(int)nch : (int)nch;
+        } else {
+            S.bad_armed = false;
+            rs.bad = words;
+            arm_bad(rs.bad, nch, st);
+        }
     }
     rs.err = kernel_error_word(P);
     static long long* d_rtrace = nullptr;  // SIGOPS_RSOS_TRACE tuning aid
@@ -948,7 +976,7 @@ static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View&
     static int rtrace_seen = 0;
     const char* const rtrace_skip = std::getenv("SIGOPS_RSOS_TRACE_SKIP");
     const bool rtracing = std::getenv("SIGOPS_RSOS_TRACE") != nullptr && rtrace_seen++ >= (rtrace_skip ? std::atoi(rtrace_skip) : 0);
-    const size_t rtrace_n = (size_t)16 * kRsosTraceIters * 8;
+    const size_t rtrace_n = (size_t)(16 * kRsosTraceIters + 16) * 8;  // (+ the prologue's rows: k_rsos.hip rsos_stamp_pro)
     if (rtracing) {
         if (!d_rtrace) HIPCHECK(hipMalloc(&d_rtrace, rtrace_n * 8));
         HIPCHECK(hipMemsetAsync(d_rtrace, 0, rtrace_n * 8, st));
@@ -960,13 +988,18 @@ static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View&
         fail(SO_ERR_RUNTIME, "internal: no fused resampler + IIR instantiation for this geometry");
     if (rtracing) dump_rsos_trace(d_rtrace, rtrace_n, rs, st);
     int nl = 1;
-    if (rs.bad && S.rsos_jrel_buf >= 0 && !std::getenv("SIGOPS_RSOS_NO_FIXUP")) {
+    if (rs.bad && fixup) {
         // behind a non-finite sample the reference stays non-finite: NaN over everything after the first bad
         // range -- and INSIDE that range the block the sample fell into (the block form makes all 16 outputs
         // non-finite, and a group's window is wider than an output's) output by output the reference's way
         RsFixup fx{};
         set_rsos_fixup(fx, P, S, RsosItem{rs, rtab, rjend, yk, global_tables(P, S3)});
+        fx.rearm = rearm;
         nl += launch_rsos_fixup(fx, st);
+        if (rearm != 0) {  // (the next execute's set, armed by this launch)
+            S.bad_set ^= 1;
+            S.bad_armed = true;
+        }
     } else if (rs.bad) {
         SosGeom pg = g;
         pg.n = rs.n_out;
@@ -1182,6 +1215,10 @@ static int run_norm(Plan* P, const Step& s, void* outp, hipStream_t st) {
     return 2;
 }
 
+// Called from plan_execute ONLY, which sets Plan::graph_plan for the call: whether these launches may be captured into the
+// plan's graph or stand next to its replays, and so must take the same arguments every time (run_rsos_fused: which set of
+// `bad` words).  A caller that captures so_plan_execute into a graph of its OWN is not supported: a plan the executor
+// does not replay itself alternates its sets from execute to execute, and a replay would not.
 static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& err) {
     try {
         HIPCHECK(hipSetDevice(P->device));
@@ -1309,6 +1346,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
             P->stats.last_exec_ms = total;
         }
     } catch (const PlanError& e) {
+        disarm_bad(P);
         err = e.msg;
         return e.status;
     }
@@ -1320,9 +1358,13 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
 // pointer on, the whole multi-stream launch sequence is replayed from a captured HIP graph.
 int plan_execute(Plan* P, void* outp, void* stream, std::string& err) {
     DeviceGuard guard(P->device);
-    if (kernel_gave_up(P, err)) return SO_ERR_RUNTIME;
+    if (kernel_gave_up(P, err)) {
+        disarm_bad(P);
+        return SO_ERR_RUNTIME;
+    }
     const bool eligible = P->steps.size() >= 4 && P->out.is_device && P->host_leaves.empty() && !P->profiling &&
                           !std::getenv("SIGOPS_NO_GRAPH") && !std::getenv("SIGOPS_RS_TRACE");
+    P->graph_plan = eligible;
     if (!eligible) {
         P->n_direct++;
         return plan_execute_direct(P, outp, stream, err);

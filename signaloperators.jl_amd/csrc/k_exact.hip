@@ -30,6 +30,13 @@ __device__ __forceinline__ void rsos_fixup_body(const RsFixup& fx) {
     const RsSos& g = fx.g;
     const int ch = blockIdx.y;
     if (ch >= g.nch) return;
+    // The plan keeps TWO sets of words and alternates between them from execute to execute (run_rsos_fused): this launch
+    // reads set A = g.bad and leaves set B = g.bad + rearm armed ("no range yet") for the next execute -- no fill launch
+    // of its own there.  Ordering, all of it the stream's: nothing of THIS execute touches B (its k_rsos wrote A, these
+    // workgroups read A), so the one store below races with nobody; the next execute's k_rsos, which writes B with
+    // atomicMin, starts after this launch has ended; and A is armed again by the next execute's fix-up, two kernel
+    // boundaries behind the last of these reads.  No ticket, no fence.
+    if (fx.rearm != 0 && blockIdx.x == 0 && threadIdx.x == 0) g.bad[ch + fx.rearm] = 0x7f7f7f7f;
     const int r = g.bad[ch];
     if (r < 0 || r >= g.nranges) return;  // (the usual case: the large initial value)
     TO* const y = (TO*)fx.y + (int64_t)ch * g.out_pitch;

@@ -349,6 +349,18 @@ __device__ __forceinline__ void rsos_stamp(long long* trace, int wave, int it, i
     if (trace != nullptr && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && it >= it0 && it < it0 + kRsosTraceIters)
         ((long long SO_GLB*)trace)[(wave * kRsosTraceIters + (it - it0)) * 8 + k] = clock64();
 }
+// ... and of the prologue of workgroup 1's FIRST group (a slot keeps its first stamp; workgroup 0's first group holds range 0,
+// whose warm-up lies in front of the signal: it walks): sixteen rows behind the waves' own, one per wave.  Columns: 0 - 4
+// rsos_wproj_y (entry, first batch landed, last full batch's MFMAs issued, tail batch landed, tile published) or 0 - 2
+// rsos_wproj_chain (entry, all tiles seen, s_0 written); 5 the y wave at its first front; 6 the kernel's entry, 7 the
+// group's roles handed out (rsos_body).  profiles/r09/wproj_prologue_trace.txt.
+__device__ __forceinline__ void rsos_stamp_pro(long long* trace, int k) {
+    if constexpr (!SO_RSOS_TRACE) return;
+    if (trace != nullptr && blockIdx.x == 1 && (threadIdx.x & 63) == 0) {
+        long long SO_GLB* const q = (long long SO_GLB*)trace + ((16 * kRsosTraceIters + (int)(threadIdx.x >> 6)) * 8 + k);
+        if (*q == 0) *q = clock64();
+    }
+}
 
 // who waits for whom (tuning aid, a -DSO_RSOS_COUNT=1 build with SIGOPS_RSOS_TRACE=2): every wave of workgroup 0 counts the
 // polls of each of its waits -- in the spin paths only, nothing in the common path -- and leaves them in its first trace row
@@ -1216,6 +1228,9 @@ __device__ __attribute__((noinline)) void rsos_wproj_y(RsosShared* sh_, double* 
     const SO_LDS DCarrier& C0 = sh->ctl.car[0];
     const int64_t ncg = uni(g.nch) / ct;
     const int gq = lane >> 4, n16 = lane & 15;
+    long long* trace = nullptr;
+    if constexpr (SO_RSOS_TRACE) trace = (long long*)rfl64((int64_t)(uintptr_t)g.trace);
+    rsos_stamp_pro(trace, 0);
     // this lane's row: channel n16 % ct of range r0 + n16 / ct, from the first frame its warm-up reads
     const int64_t r = (G / ncg) * uni(g.rgs) + n16 / ct;
     const int64_t f0 = (r * rfl64(g.pr) - uni(g.wp)) * rfl64(g.M) + uni(g.wj0);
@@ -1247,6 +1262,10 @@ __device__ __attribute__((noinline)) void rsos_wproj_y(RsosShared* sh_, double* 
     const int nfull = c1f > c0 ? (c1f - c0) >> 3 : 0;
     if (nfull > 0) {
         load(c0, aA, bA);
+        if constexpr (SO_RSOS_TRACE) {  // (the traced build waits for its first batch alone: one round trip, seen as such)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            rsos_stamp_pro(trace, 1);
+        }
         for (int n = 0; n < nfull; n += 2) {
             const int c = c0 + 8 * n;
             if (n + 1 < nfull) load(c + 8, aB, bB);
@@ -1255,6 +1274,7 @@ __device__ __attribute__((noinline)) void rsos_wproj_y(RsosShared* sh_, double* 
             if (n + 1 < nfull) mm(aB, bB);
         }
     }
+    rsos_stamp_pro(trace, 2);
     {
         const int c = c0 + 8 * nfull;  // (c1 - c <= 8)
 #pragma unroll
@@ -1270,11 +1290,16 @@ __device__ __attribute__((noinline)) void rsos_wproj_y(RsosShared* sh_, double* 
                 else if (f < K) bA[i][0] = row[8 * cc];  // (never a frame past the span: it may lie outside the array)
             }
         }
+        if constexpr (SO_RSOS_TRACE) {  // (the MFMAs below wait for all of them anyway)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            rsos_stamp_pro(trace, 3);
+        }
         mm(aA, bA);
     }
 #pragma unroll
     for (int v = 0; v < 3; ++v) l.ss[(1 + yi) * 192 + v * 64 + lane] = acc[v];
     flag_st(fl_base + 4 * (kRsosFlagWp + yi), 1);
+    rsos_stamp_pro(trace, 4);
 }
 
 template <int NY>
@@ -1289,6 +1314,9 @@ __device__ __attribute__((noinline)) void rsos_wproj_chain(RsosShared* sh_, doub
     const int ct = uni(g.ct), fuse = uni(g.fuse);
     const int gq = lane >> 4, n16 = lane & 15;
     double s[3] = {0.0, 0.0, 0.0};
+    long long* trace = nullptr;
+    if constexpr (SO_RSOS_TRACE) trace = (long long*)rfl64((int64_t)(uintptr_t)g.trace);
+    rsos_stamp_pro(trace, 0);
     if (fuse >= 0) {  // the sine's share: what does not wait for the y waves first
         const SO_LDS DCarrier& C0 = sh->ctl.car[0];
         const DLeaf leaf0 = leaf_uniform(sh_->ctl.leaves[min(kCtlLeaves - 1, max(0, uni(C0.slot_leaf[0])))]);
@@ -1309,12 +1337,14 @@ __device__ __attribute__((noinline)) void rsos_wproj_chain(RsosShared* sh_, doub
         if (wave_min(f, NY) >= 1) break;
         SO_SPIN_PAUSE(spins, 1, 1 << 22);
     }
+    rsos_stamp_pro(trace, 1);
 #pragma unroll
     for (int yi = 0; yi < NY; ++yi)
 #pragma unroll
         for (int v = 0; v < 3; ++v) s[v] += l.ss[(1 + yi) * 192 + v * 64 + lane];
 #pragma unroll
     for (int v = 0; v < 3; ++v) l.ss[v * 64 + lane] = s[v];
+    rsos_stamp_pro(trace, 2);
 }
 
 // =========================== helper wave ===========================
@@ -1448,7 +1478,10 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
 #define SO_Y_SADDR 1
 #endif
 #ifndef SO_ST_NT
-#define SO_ST_NT ""  // (cache-policy bits of the result stores: measured and not set, see kstage.h SO_LD_NT)
+// cache-policy bits of the Float64 result stores.  Together with the same hint on the staging loads (kstage.h SO_LD_NT) it lost on
+// 12.5 M x 8; on the stores ALONE it gains on every shape measured (profiles/r09/store_policy.txt: headline 0.959 -> 0.951 ms,
+// 12.5 M x 8 0.496 -> 0.493): a result is written once and read by nobody in the launch, the loads keep their lines.
+#define SO_ST_NT " nt"
 #endif
     const bool yfits = SO_Y_SADDR && uni((int)((((int64_t)(ct - 1) * out_pitch + (int64_t)(16 / ct) * grp.prL + 16) * (int64_t)sizeof(TO)) < ((int64_t)1 << 32)));
     int nbs_all;     // block b is stored by every lane of the wave while b < nbs_all (no predicates then)
@@ -1599,6 +1632,7 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         const int wb = pi * M + je - ulo_kw;
         const int need = wb + kw + 16;
         rsos_stamp(trace, wave, b / NY, 0, 40);
+        rsos_stamp_pro(trace, 5);
         int spins = 0;
         if constexpr (SO_RSOS_COUNT) cnt_in_b += avail < need ? 1 : 0;
         while (avail < need && !(debug & 16)) {
@@ -1857,6 +1891,7 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
     extern __shared__ double lds_raw[];
     __shared__ RsosShared sh;
     const int wave = uni(threadIdx.x >> 6);
+    rsos_stamp_pro(g.trace, 6);
     // ---- once per workgroup: arguments, taps, window ends, control block ----
     {
         if (threadIdx.x == 0) {
@@ -1894,6 +1929,7 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
         }
         __syncthreads();
         const bool proj = sh.proj != 0;
+        rsos_stamp_pro(g.trace, 7);
         if (wave == 0) {
             if (!(g.debug & 64)) {
                 if (proj) rsos_wproj_chain<NY>(&sh, lds_raw, G);

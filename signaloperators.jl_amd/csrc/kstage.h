@@ -112,7 +112,8 @@ __device__ __forceinline__ void lds_wait(v2d (&v)[N]) {  // results of lds_ld16 
 // (cache-policy bits of the staging loads, e.g. -DSO_LD_NT='" nt"'.  Measured with the same hint on the fused kernel's result
 //  stores, k_rsos.hip SO_ST_NT: the headline's 3.5 GB stream 0.961 -> 0.947 ms, but the same kernel on 12.5 M x 8 frames 0.457
 //  -> 0.59 and K3's two-array instantiation 0.545 -> 0.60 -- what a loop of executes over 1 - 2 GB keeps in the 256 MB
-//  memory-side cache is worth more than the hint.  Not set.)
+//  memory-side cache is worth more than the hint.  Not set on the loads.  On k_rsos's result stores ALONE the hint gains and
+//  is set: the comment at SO_ST_NT in k_rsos.hip.)
 #ifndef SO_LD_NT
 #define SO_LD_NT ""
 #endif

@@ -144,7 +144,9 @@ struct Stage {
     bool xscan = false;  // pass 2 is the exact block scan (launch_sos_xscan): no 2^-70 cut anywhere
     int batch = -1;      // member of Plan::batches[batch]: its three passes run inside that batch's launches
     int xs_mats_buf = -1, sblk_buf = -1;
-    int bad_buf = -1;    // first non-finite chunk per channel (SosGeom::bad)
+    int bad_buf = -1;    // first non-finite chunk per channel (SosGeom::bad); two sets of words (run_rsos_fused)
+    mutable int bad_set = 0;         // k_rsos on direct launches: the set the next execute uses ...
+    mutable bool bad_armed = false;  // ... which the last execute's fix-up left armed (false: the host arms both sets)
     std::vector<std::vector<double>> xs_mats_host;  // per group: [M][M^kXsBlock]
     std::vector<std::vector<double>> mpow_host;  // per group
     size_t mpow_stride() const {  // doubles between the groups' tables in mpow_buf: the longest group's
@@ -343,6 +345,7 @@ struct Plan {
     const void* last_out = nullptr;
     int64_t array_epoch = 0, graph_epoch = -1, last_epoch = -1;
     bool graph_failed = false;
+    bool graph_plan = false;  // this execute may be captured or replayed (plan_execute): its launches take fixed arguments
     int64_t n_replays = 0, n_captures = 0, n_direct = 0;  // so_plan_counter
     so_stats_t stats{};
     int64_t algo_bytes = 0;

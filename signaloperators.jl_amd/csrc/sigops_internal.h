@@ -441,7 +441,7 @@ struct RsFixup {
     const int* jend;    // [ngroups] window end (newest input of the group's last output), relative to the period's first input
     const int* jrel;    // [L] newest input of output r of the period, relative to its group's window end (<= 0)
     int32_t taps;       // taps per output as the reference multiplies them
-    int32_t pad;
+    int32_t rearm;      // != 0: the launch leaves the words at g.bad + rearm armed for the next execute (k_exact.hip)
     SosCoefs cf;        // the cascade's sections (the per-sample DF2T form)
     RsGlobalTables gsrc;  // the kernel's source, for single frames
     void* y;            // result, in the kernel's output coordinates

@@ -483,7 +483,7 @@ void Plan::sos_chunking(int sid, int64_t need, int nch, int dtype, const std::ve
             stages[sid].sblk_buf = sized_buf(stages[sid].sblk_buf, (size_t)nblk * nch * 16 * 8);
         }
     }
-    if (nchunks > 1 && !stages[sid].onepass && !exact) stages[sid].bad_buf = sized_buf(stages[sid].bad_buf, (size_t)nch * 4);
+    if (nchunks > 1 && !stages[sid].onepass && !exact) stages[sid].bad_buf = sized_buf(stages[sid].bad_buf, (size_t)nch * 8);  // (two sets: run_rsos_fused)
     stages[sid].sg = g;
 }
 
@@ -2657,7 +2657,8 @@ struct RsosFusion : RsosRanges {
 
     void commit_launch() {
         S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
-        if (S2.bad_buf < 0) S2.bad_buf = P.raw_buf((size_t)nch * 4);  // first range per channel that ended in a non-finite state
+        // first range per channel that ended in a non-finite state: two sets of words, used in turn (run_rsos_fused)
+        if (S2.bad_buf < 0) S2.bad_buf = P.raw_buf((size_t)nch * 8);
         S3.fused_away = true;
         if (alt.armed) {  // (K1's copy of `x (op) y` is never made: its step is not in the plan, its buffer holds nothing)
             alt.armed = false;
@@ -2875,7 +2876,7 @@ void Plan::fuse_plain_sos() {
         double cost = 0.0;
         if (!one.fit(i2, 0, g, cost)) continue;
         one.commit(i2, g);
-        if (S2.bad_buf < 0) S2.bad_buf = raw_buf((size_t)g.nch * 4);
+        if (S2.bad_buf < 0) S2.bad_buf = raw_buf((size_t)g.nch * 8);  // (two sets of words: run_rsos_fused)
     }
     // ---- the small ones, together: members that share the kernel's instantiation (waves; the result's type) ----
     const char* const want_s = std::getenv("SIGOPS_RSOS_BATCH");  // 0: never, 1: whenever it fits (tests, measurements), default: by the estimate
