@@ -441,7 +441,9 @@ typedef enum so_counter {
     SO_COUNTER_RSOS_WARMUP_PERIODS = 6, /* warm-up periods in front of every range                                   */
     SO_COUNTER_RSOS_PERIOD_INPUTS = 7,  /* input frames per period                                                   */
     SO_COUNTER_WPROJ_FRAMES = 8,        /* frames a projected warm-up reads                                          */
-    SO_COUNTER_WPROJ_FIRST = 9          /* the first of them, counted from the warm-up's first period (may be < 0)   */
+    SO_COUNTER_WPROJ_FIRST = 9,         /* the first of them, counted from the warm-up's first period (may be < 0)   */
+    SO_COUNTER_RSOS_FOLD = 10 /* 1: the fused resampler + IIR kernel runs its folded block -- the cascade's zero-state response
+                               * folded into the tap table, 4 MFMAs fewer per block (0: the unfolded block, or no such launch) */
 } so_counter_t;
 int64_t so_plan_counter(const so_plan_t* plan, int32_t which);
 
@@ -580,6 +582,15 @@ int32_t so_resample_positions(double fs_in, double fs_out, double rate, int32_t 
 int32_t so_rsos_wproj_matrix(const double* sos, int32_t nsec, double gain, const double* tab, const int32_t* jend,
                              int32_t ngroups, int32_t kw, int64_t m, int32_t wp, double* v, int32_t capacity,
                              int32_t* j0, int32_t* k);
+
+/* Diagnostic, host only: the tables of the fused resampler + IIR kernel's folded block for the cascade `sos` ([nsec][6] rows,
+ * times `gain`, as above) and the tap table tab[ngroups][kw][16].  With T the cascade's zero-state response over a block of 16
+ * samples and D its map from a block's input to the state behind it:  e: [12][16] row-major, E = D . T^-1 with time in natural
+ * order (rows from 2 nsec on are zero);  ftab: [ngroups][kw][16], T . Tap_g^T in the layout of `tab` with entry m of a row the
+ * output at time 2 (m & 3) + ((m >> 2) & 1) + 8 (m >> 3) of the block (the kernel's row order);  *amp = max_i sum_j (|E| |T|)_ij
+ * / max_i sum_j |D|_ij;  *fold = 1 where the planner's gate (amp <= 256) admits the cascade. */
+int32_t so_rsos_fold_tables(const double* sos, int32_t nsec, double gain, const double* tab, int32_t ngroups, int32_t kw,
+                            double* e, double* ftab, double* amp, int32_t* fold);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -251,4 +251,14 @@ int32_t so_rsos_wproj_matrix(const double* sos, int32_t nsec, double gain, const
     return SO_OK;
 }
 
+int32_t so_rsos_fold_tables(const double* sos, int32_t nsec, double gain, const double* tab, int32_t ngroups, int32_t kw,
+                            double* e, double* ftab, double* amp, int32_t* fold) {
+    if (!sos || !tab || !e || !ftab || !amp || !fold || nsec < 1 || nsec > 6 || ngroups < 1 || ngroups > 256 || kw < 1 || kw > 4096)
+        return set_err(SO_ERR_INVALID, "so_rsos_fold_tables: bad arguments");
+    int f = 0;
+    so::rsos_fold_tables_sos(sos, nsec, gain, tab, ngroups, kw, e, ftab, amp, &f);
+    *fold = f;
+    return SO_OK;
+}
+
 }  // extern "C"

@@ -984,7 +984,10 @@ static int run_rsos_fused(Plan* P, const Stage& S, const SosGeom& g, const View&
     }
     const double* rtab = (const double*)P->bufs[S.rsos_tab_buf >= 0 ? S.rsos_tab_buf : S3.tab_buf].d;
     const int* rjend = (const int*)P->bufs[S.rsos_jend_buf >= 0 ? S.rsos_jend_buf : S3.jend_buf].d;
-    if (launch_rsos(rtab, rjend, rs, yk, global_tables(P, S3), S.rsos_grid, st) != 0)
+    // (a folded plan's kernel reads M_g = T . Tap_g^T, behind E and C in `mats`, as its tap table; the fix-up launch recomputes single
+    //  outputs the reference's way, from the taps themselves.  A Float32 result has no folded instantiation)
+    if (rs.out_f32) rs.fold = 0;
+    if (launch_rsos(rs.fold ? rs.mats + rs.fold_off + 7 * 64 : rtab, rjend, rs, yk, global_tables(P, S3), S.rsos_grid, st) != 0)
         fail(SO_ERR_RUNTIME, "internal: no fused resampler + IIR instantiation for this geometry");
     if (rtracing) dump_rsos_trace(d_rtrace, rtrace_n, rs, st);
     int nl = 1;
@@ -1503,8 +1506,13 @@ int64_t plan_counter(const Plan* P, int which) {
     case SO_COUNTER_GRAPH_CAPTURES: return P->n_captures;
     case SO_COUNTER_DIRECT_EXECUTES: return P->n_direct;
     case SO_COUNTER_FUSED_MFMAS_PER_BLOCK: {  // k_rsos: window k-steps + 14 (D . X, X^T T^T, the chain's A^16 . S, S^T C^T)
+        for (const Stage& S : P->stages)    // ... + 10 for a folded plan (E . Z, the chain's A^16 . S, C . S)
+            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.ks + (S.rs.fold ? 10 : 14);
+        return 0;
+    }
+    case SO_COUNTER_RSOS_FOLD: {  // k_rsos: the folded block (RsSos::fold)
         for (const Stage& S : P->stages)
-            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.ks + 14;
+            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.fold;
         return 0;
     }
     case SO_COUNTER_WPROJ: {  // k_rsos: the warm-up of a range as one product where it lies inside the array (RsSos::wproj)

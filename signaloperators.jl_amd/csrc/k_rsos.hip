@@ -49,6 +49,7 @@ namespace so {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef double v2d __attribute__((ext_vector_type(2)));
 
 #define SO_LDS __attribute__((address_space(3)))
 // LDS sequence counters (single writer each) and the data they announce: VOLATILE accesses -- the compiler keeps them in
@@ -1405,9 +1406,17 @@ __device__ __attribute__((noinline)) void rsos_helper(RsosShared* sh_, double* d
 // row = 4 (lane >> 4) + reg where the Float64 instruction's is (lane >> 4) + 4 reg: register v of X, widened, is still k-step v of
 // the products that follow (D . X, X^T T^T: all Float64, like the cascade) -- with the k index of THEIR other operand
 // permuted the same way (Dk, Tk below are read from the matrices' table in that order).
-template <int KS, int NY, int NL, typename TO, int CYC, bool F32M = false, bool HW = false>
+// FOLD (RsSos::fold; Float64 results, 12 and 8 waves): the tap operands are M_g = T . Tap_g^T (the launch's `tab` is that table), so
+// the resampling product is the block's zero-state OUTPUT Z = T . X, row = time, column = sequence: what was X^T T^T -- four MFMAs
+// that filter and transpose -- is gone.  The chain wave's share is E . Z (E = D . T^-1: D . X in exact arithmetic, same slots,
+// same protocol), the result Z + C . S is today's product with its operands swapped, and it is stored untransposed: MFMA row
+// gq + 4 v holds output time 2 gq + (v & 1) + 8 (v >> 1) (rsos_fold_time -- the planner permuted the rows of M_g and C and the
+// columns of E accordingly), i.e. registers 0, 1 and 2, 3 of a lane are two pairs of adjacent outputs of ITS sequence, 64 bytes
+// apart: two 16-byte stores per lane and block, each writing 64 contiguous bytes in each of the 16 rows.
+template <int KS, int NY, int NL, typename TO, int CYC, bool F32M = false, bool HW = false, bool FOLD = false>
 __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dyn, int64_t G_, int yi_) {
     static_assert(!F32M || (sizeof(TO) == 4 && CYC > 0), "the Float32 MFMA form: Float32 results, taps in registers");
+    static_assert(!FOLD || (sizeof(TO) == 8 && !F32M && !HW), "the folded block: Float64 results, no helper wave");
     constexpr int NX = 2 * NY + 1;
     const int lane = threadIdx.x & 63;
     const int wave = uni(threadIdx.x >> 6);
@@ -1439,15 +1448,24 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
                         (!src32 || uni(g.chunk) == 128) && (!uni(g.arr2) || rsos_two_ok(C0, uni(g.chunk)));
     const RsosGroup grp = rsos_group(sh, G, single, (int64_t)(rfl64((int64_t)(uintptr_t)C0.base) >> (src32 ? 2 : 3)), cs0, df0);
     const int gq = lane >> 4, n16 = lane & 15;
-    double Dk[4], Tk[4], Ck[3];
+    double Dk[4], Ck[3];
+    [[maybe_unused]] double Tk[4];
     const int nkc = (uni(g.debug) & 131072) ? 3 : (2 * uni(g.nsec) + 3) / 4;  // k-steps of the state (rsos_chain's NK)
     // (k-step v, lane (gq, n16) holds index 4 v + gq of the contracted dimension; F32M: 4 gq + v -- see above)
+    if constexpr (FOLD) {  // (E in D's place, the row-permuted C, no T)
+        const double SO_GLB* fm = mats + uni(g.fold_off);
 #pragma unroll
-    for (int v = 0; v < 4; ++v) Dk[v] = F32M ? mats[(lane >> 4) * 64 + v * 16 + (lane & 15)] : mats[v * 64 + lane];
+        for (int v = 0; v < 4; ++v) Dk[v] = fm[v * 64 + lane];
 #pragma unroll
-    for (int v = 0; v < 4; ++v) Tk[v] = F32M ? mats[(7 + (lane >> 4)) * 64 + v * 16 + (lane & 15)] : mats[(7 + v) * 64 + lane];
+        for (int v = 0; v < 3; ++v) Ck[v] = fm[(4 + v) * 64 + lane];
+    } else {
 #pragma unroll
-    for (int v = 0; v < 3; ++v) Ck[v] = mats[(11 + v) * 64 + lane];
+        for (int v = 0; v < 4; ++v) Dk[v] = F32M ? mats[(lane >> 4) * 64 + v * 16 + (lane & 15)] : mats[v * 64 + lane];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) Tk[v] = F32M ? mats[(7 + (lane >> 4)) * 64 + v * 16 + (lane & 15)] : mats[(7 + v) * 64 + lane];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) Ck[v] = mats[(11 + v) * 64 + lane];
+    }
     // this lane's B-operand row ...
     int cl;   // its alignment shift + the lane's k offset
     int nb0;  // blocks of this row before the signal's first output: their resampled samples do not exist (the cascade
@@ -1485,7 +1503,31 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
 #endif
     const bool yfits = SO_Y_SADDR && uni((int)((((int64_t)(ct - 1) * out_pitch + (int64_t)(16 / ct) * grp.prL + 16) * (int64_t)sizeof(TO)) < ((int64_t)1 << 32)));
     int nbs_all;     // block b is stored by every lane of the wave while b < nbs_all (no predicates then)
-    {
+    [[maybe_unused]] bool st16 = false;  // FOLD: every lane's stores of a block fall on 16-byte boundaries (wave-uniform)
+    if constexpr (FOLD) {
+        // the lane's sequence n16 = (channel cv, range ri) and the first of its four outputs of a block, time 2 gq: one lane offset,
+        // the second pair of outputs 64 bytes further (an immediate); the scalar base is the group's row 0 at the block's first output
+        const int ri = n16 / ct, cv = n16 % ct;
+        const int64_t ob = grp.ob0 + ri * grp.prL;
+        const int64_t off0 = ((int64_t)cv * out_pitch + (int64_t)ri * grp.prL + 2 * gq) * (int64_t)sizeof(TO);
+        yo0 = (uint32_t)off0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) ystep[v] = 0;
+        const int64_t tl = n_out - ob - 15;  // (the lanes gq = 3 of the sequence hold time 15: 16 b < tl)
+        const int64_t nb = tl <= 0 ? 0 : (tl + 15) / 16;
+        int m = (int)(nb > 0x3fffffff ? 0x3fffffff : nb);
+        // (16 bytes per store only where the row bases are shown to be aligned: blocks start at multiples of 16 outputs and
+        //  2 gq is even, so it is the result's base, its pitch and the range length that decide -- an odd pitch or a window
+        //  that starts at an odd frame leaves some rows at 8 bytes, and the wave then stores 8 bytes per register)
+        int al = (int)((((uint64_t)(uintptr_t)y + (uint64_t)(ybase_e * (int64_t)sizeof(TO) + off0)) & 15) == 0);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            m = min(m, __shfl_xor(m, off, 64));
+            al = min(al, __shfl_xor(al, off, 64));
+        }
+        nbs_all = uni(m);
+        st16 = uni(al) != 0;
+    } else {
         int m = 0x7fffffff;
         int64_t off0 = 0;
 #pragma unroll
@@ -1577,6 +1619,12 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
     };
     // (as many k-steps as the cascade has states / 4: the chain wave writes no more of a state slot -- RsosChain's NK)
     auto back_mfma = [&](const double (&sv)[3], v4d ay) __attribute__((always_inline)) {
+        if constexpr (FOLD) {  // (Y = Z + C . S: the same two registers per k-step, C as the A operand, the state as B)
+            ay = __builtin_amdgcn_mfma_f64_16x16x4f64(Ck[0], sv[0], ay, 0, 0, 0);
+            if (nkc > 1) ay = __builtin_amdgcn_mfma_f64_16x16x4f64(Ck[1], sv[1], ay, 0, 0, 0);
+            if (nkc > 2) ay = __builtin_amdgcn_mfma_f64_16x16x4f64(Ck[2], sv[2], ay, 0, 0, 0);
+            return ay;
+        }
         ay = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[0], Ck[0], ay, 0, 0, 0);
         if (nkc > 1) ay = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[1], Ck[1], ay, 0, 0, 0);
         if (nkc > 2) ay = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[2], Ck[2], ay, 0, 0, 0);
@@ -1592,6 +1640,38 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         //  Float64 store reads behind the asm either: hence `fresh`)
         const uint64_t yb = (uint64_t)rfl64((int64_t)ypend);
         if (fresh && yfits && sizeof(TO) == 8) asm volatile("s_nop 15\n\ts_nop 1" : "+v"(ay[0]), "+v"(ay[1]), "+v"(ay[2]), "+v"(ay[3])::"memory");
+        if constexpr (FOLD) {
+            // register v of lane (gq, n16): output t0 + rsos_fold_time(gq + 4 v) of sequence n16, at byte 8 (v & 1) + 64 (v >> 1)
+            // from the lane's offset
+            const int64_t o0 = grp.ob0 + (int64_t)(n16 / ct) * grp.prL + t0 + 2 * gq;  // (the lane's first output of the block)
+            const bool all = pb_ >= nbl_max && pb_ < nbs_all;  // (the common path: every lane stores, no predicates)
+            if (all && yfits && st16) {
+                const v2d lo = v2d{ay[0], ay[1]}, hi = v2d{ay[2], ay[3]};
+                // (a store of more than 8 bytes reads its data late: the s_nop keeps the next instruction off these registers)
+                // NO `nt` here: an instruction writes HALF a 128-byte line per row, and with the hint the halves were written back
+                // apart -- WRITE_SIZE 2.12 GB against the result's 1.84; plain stores let them meet in L2: 1.83 GB, and 0.6 - 0.9 %
+                // off the kernel (profiles/r10/fold_profiles.txt).  The unfolded block's 128-byte runs keep the hint.
+                asm volatile("global_store_dwordx4 %0, %1, %3\n\tglobal_store_dwordx4 %0, %2, %3 offset:64\n\ts_nop 1" ::"v"(yo0),
+                             "v"(lo), "v"(hi), "s"(yb)
+                             : "memory");
+            } else if (yfits) {  // (rows at 8-byte boundaries; the first blocks of a window's first ranges, the signal's last blocks)
+                if (all || (o0 >= slo && o0 < n_out)) asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(yo0), "v"(ay[0]), "s"(yb) : "memory");
+                if (all || (o0 + 1 >= slo && o0 + 1 < n_out)) asm volatile("global_store_dwordx2 %0, %1, %2 offset:8" ::"v"(yo0), "v"(ay[1]), "s"(yb) : "memory");
+                if (all || (o0 + 8 >= slo && o0 + 8 < n_out)) asm volatile("global_store_dwordx2 %0, %1, %2 offset:64" ::"v"(yo0), "v"(ay[2]), "s"(yb) : "memory");
+                if (all || (o0 + 9 >= slo && o0 + 9 < n_out)) asm volatile("global_store_dwordx2 %0, %1, %2 offset:72" ::"v"(yo0), "v"(ay[3]), "s"(yb) : "memory");
+            } else {
+                // (results whose rows lie more than 4 GB apart: the address per store, as below)
+                int row = n16;
+                asm volatile("" : "+v"(row));
+                TO SO_GLB* const p = y + ((int64_t)(grp.cg * ct + row % ct) * out_pitch + grp.ob0 + (int64_t)(row / ct) * grp.prL + t0 + 2 * gq);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int dt = (v & 1) + 8 * (v >> 1);
+                    if (all || (o0 + dt >= slo && o0 + dt < n_out)) p[dt] = (TO)ay[v];
+                }
+            }
+            return;
+        }
         // (the output this lane's register v holds: its row's first output + the block's offset + the lane's time)
         auto out_index = [&](int v) __attribute__((always_inline)) { return grp.ob0 + (int64_t)((gq + 4 * v) / ct) * grp.prL + t0 + n16; };
         auto put = [&](int v, TO val) __attribute__((always_inline)) {
@@ -1720,7 +1800,10 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
             }
         }
         // ---- resample: X[t][row] = sum_k Tap[t][k] Win[k][row] (LDS returns in order: counted lgkmcnt waits) ----
-        v4d ax = v4d{0.0, 0.0, 0.0, 0.0};
+        // (FOLD: Z = M_g . Win, accumulated in the set the next round's back part adds C . S to and stores from)
+        v4d ax_ = v4d{0.0, 0.0, 0.0, 0.0};
+        v4d& ax = FOLD ? pout : ax_;
+        if constexpr (FOLD) ax = v4d{0.0, 0.0, 0.0, 0.0};
         if constexpr (F32M) {
             // two accumulator chains (the instruction's dependent latency is 40 cycles against 32 of issue), added at the end
             v4f a0 = v4f{0.f, 0.f, 0.f, 0.f}, a1 = v4f{0.f, 0.f, 0.f, 0.f};
@@ -1784,9 +1867,11 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         // (also for a warm-up block, whose result is not stored: 7 % of the blocks; skipping the four products there makes
         //  the set a conditional value, and the register allocator pays for that with four copies behind an MFMA-result
         //  hazard in every block)
-        pout = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[0], Tk[0], v4d{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+        if constexpr (!FOLD) {  // (FOLD: the block's product above is that payload already)
+            pout = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[0], Tk[0], v4d{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
 #pragma unroll
-        for (int v = 1; v < 4; ++v) pout = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[v], Tk[v], pout, 0, 0, 0);
+            for (int v = 1; v < 4; ++v) pout = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[v], Tk[v], pout, 0, 0, 0);
+        }
         if (!HELPABLE || hj < 0) {
 #pragma unroll
             for (int v = 0; v < 3; ++v) l.xs[slot * 192 + v * 64 + lane] = dx[v];
@@ -1880,7 +1965,8 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
 constexpr int rsos_nthreads(int nw) { return (nw == 17 ? 16 : nw) * 64; }
 // (the kernel's body: sequence groups G0, G0 + Gstep, ... of ONE filter -- the whole grid's for k_rsos, a share of it for a member
 //  of k_rsos_batch)
-template <int KS, int NW, typename TO, int CYC>
+// FOLDABLE: the body of k_rsos where the folded block exists (Float64 results, 12 and 8 waves; RsSos::fold selects it per launch)
+template <int KS, int NW, typename TO, int CYC, bool FOLDABLE = false>
 __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const int* __restrict__ jend_g, const RsSos& g, TO* __restrict__ y,
                                           const RsGlobalTables& gsrc, int64_t G0, int64_t Gstep) {
     constexpr bool HW = NW == 17;
@@ -2018,6 +2104,12 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
                     continue;
                 }
             }
+            if constexpr (FOLDABLE && sizeof(TO) == 8 && (NW == 12 || NW == 8)) {
+                if (g.fold) {
+                    rsos_ywave<KS, NY, NL, TO, CYC, false, false, true>(&sh, lds_raw, G, yi);
+                    continue;
+                }
+            }
             rsos_ywave<KS, NY, NL, TO, CYC, false, HW>(&sh, lds_raw, G, yi);
         }
     }
@@ -2026,7 +2118,7 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
 template <int KS, int NW, typename TO, int CYC>
 __global__ __launch_bounds__(rsos_nthreads(NW)) void k_rsos(const double* __restrict__ tab, const int* __restrict__ jend_g, RsSos g,
                                                   TO* __restrict__ y, RsGlobalTables gsrc) {
-    rsos_body<KS, NW, TO, CYC>(tab, jend_g, g, y, gsrc, (int64_t)blockIdx.x, (int64_t)gridDim.x);
+    rsos_body<KS, NW, TO, CYC, true>(tab, jend_g, g, y, gsrc, (int64_t)blockIdx.x, (int64_t)gridDim.x);
 }
 
 // Several filters in ONE launch (config 4: the 64 scenes of an Append, two channels each -- as launches of their own every one

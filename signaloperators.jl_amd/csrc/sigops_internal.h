@@ -422,8 +422,16 @@ struct RsSos {
     long long* trace;     // SIGOPS_RSOS_TRACE: [16 waves][kRsosTraceIters][8] cycle stamps of workgroup 0, or null
     uint32_t* err;        // host-mapped word of the plan: a wait between the kernel's waves that did not end writes 1 here and the
                           // wave ends (the host reports it with the next call on the plan); null: such a wait traps
+    int32_t fold;         // the FOLDED block (Float64 ring and result, 12 / 8 waves; stages.cpp rsos_fold_tables): the y waves resample
+                          // with M_g = T . Tap_g^T, so a block's product is its zero-state output Z = T . X (row = time, not transposed);
+                          // the chain wave gets E . Z with E = D . T^-1 (= D . X), the result is Z + C . S: 20 MFMAs per y-wave block, not 24
+    int32_t fold_off;     // ... its operands in `mats`, from this double on: [4][64] E k-steps, [3][64] C k-steps, [ngroups][ks][64] M_g --
+                          // MFMA row m = gq + 4 v of a block holds output time 2 gq + (v & 1) + 8 (v >> 1) (rsos_fold_time)
 };
 constexpr int kRsosTraceIters = 96;
+// output time (within its block) of MFMA row m of a folded block: registers 0, 1 of a lane hold two adjacent outputs, registers
+// 2, 3 the pair eight outputs later -- two 16-byte stores per lane and block
+constexpr int rsos_fold_time(int m) { return 2 * (m & 3) + ((m >> 2) & 1) + 8 * (m >> 3); }
 
 // One member of a batched k_rsos launch (k_rsos_batch): what launch_rsos would have been given for it
 struct RsosItem {

@@ -2022,23 +2022,27 @@ void Plan::batch_sos_stages() {
 // When an SOS stage is the only reader of a periodic resampler stage, both run as ONE launch: the signal is cut
 // into time ranges, 16 rows (ranges x channels) per workgroup, every range warm-started wp periods early from
 // zero state, the cascade in block state-space form on the matrix cores (see the kernel's header).
-// Values: the resampled samples are K3's (same products, same order); the IIR's differ from the sequential
-// recurrence by the rounding of a different association, ~1e-14 norm-wise for cascades that pass the planner's
-// conditioning probes (the others never get here: they run k_sos_exact).
-// columns of [T C; D A^16]: the DF2T recurrence over one block from a unit input / a unit state
-static void rsos_block_columns(const SosCoefs& cf, std::vector<double>& Tm, std::vector<double>& Cm, std::vector<double>& Dm, std::vector<double>& Am) {
+// Values: in the unfolded block the resampled samples are K3's (same products, same order) and the IIR's differ from the
+// sequential recurrence by the rounding of a different association, ~1e-14 norm-wise for cascades that pass the planner's
+// conditioning probes (the others never get here: they run k_sos_exact).  A FOLDED plan (rsos_fold_tables below) never forms
+// the resampled samples: its products are those of T . Tap^T, the zero-state output of a block, another association again --
+// admitted only where it differs from the unfolded block by no more than that block's own rounding.
+// columns of [T C; D A^16]: the DF2T recurrence over one block from a unit input / a unit state (R: double, or long double for
+// the folded block's tables)
+template <typename R>
+static void rsos_block_columns(const SosCoefs& cf, std::vector<R>& Tm, std::vector<R>& Cm, std::vector<R>& Dm, std::vector<R>& Am) {
     const int ns = cf.nsec, D = 2 * ns, B = 16;
     Tm.assign(B * B, 0.0);
     Cm.assign(B * 12, 0.0);
     Dm.assign(12 * B, 0.0);
     Am.assign(12 * 12, 0.0);
     for (int col = 0; col < B + D; ++col) {
-        std::vector<double> st(D, 0.0);
+        std::vector<R> st(D, 0.0);
         if (col >= B) st[col - B] = 1.0;
         for (int t = 0; t < B; ++t) {
-            double v = col == t ? 1.0 : 0.0;
+            R v = col == t ? 1.0 : 0.0;
             for (int f = 0; f < ns; ++f) {
-                const double xi = v;
+                const R xi = v;
                 v = st[2 * f] + cf.b0[f] * xi;
                 st[2 * f] = st[2 * f + 1] + cf.b1[f] * xi - cf.a1[f] * v;
                 st[2 * f + 1] = cf.b2[f] * xi - cf.a2[f] * v;
@@ -2072,6 +2076,124 @@ static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
             }
         }
     }
+}
+
+// The FOLDED block (k_rsos.hip, rsos_ywave<..., FOLD>).  T is the same 16 x 16 matrix for every block, so the y waves can resample
+// with M_g = T . Tap_g^T and get the block's zero-state output Z = T . X in the place of X: what was X^T . T^T, four MFMAs of the
+// 24 a y wave issues per block, goes.  The chain wave's share of the next state is then E . Z with E = D . T^-1 (T is lower
+// triangular Toeplitz with the cascade's first impulse-response sample on its diagonal) -- D . X in exact arithmetic, the state
+// is still the DF2T state, and A^16, C, the projected warm-up's V and the fix-up launch are what they were.
+// E undoes T inside Z.  That is harmless where the filter's zeros lie away from the region the passband leaves (band-stops,
+// high-passes: |E| |T| is a few ten times |D|) and ruinous for low-passes, whose T all but removes what E has to bring back.  The
+// gate: amp = max_i sum_j (|E| |T|)_ij / max_i sum_j |D|_ij, from the long double matrices, at most kRsosFoldAmp.  A Float64
+// simulation of both block walks against a long double one (4 000 blocks, random X; Butterworth designs):
+//     band-stop 0.5 - 2 kHz @ 48 kHz, order 5   amp 39      plain 7.0e-15   folded vs plain 9.6e-15
+//     high-pass 200 Hz @ 48 kHz, order 7            3.8           1.9e-14                   1.4e-14
+//     band-stop 0.5 - 2 kHz @ 16 kHz, order 5       123           2.0e-15                   1.3e-14
+//     low-pass 20 kHz @ 48 kHz, order 5             604           2.3e-16                   3.1e-14
+//     low-pass 4 kHz @ 16 kHz, order 5              2.3e4         3.0e-16                   3.8e-12
+//     low-pass 5 kHz @ 48 kHz, order 7              9.7e4         3.9e-16                   8.1e-9
+// (amp is not monotone in the error: the threshold sits well below the first bad row.)
+// Rows: MFMA row m of a folded block is output time rsos_fold_time(m) of the block -- the rows of M_g and C and the columns of
+// E are permuted that way, which costs nothing and lets a lane store its four results as two pairs of adjacent outputs.
+constexpr double kRsosFoldAmp = 256.0;
+struct RsosFold {
+    std::vector<double> E;     // [12][16]: E[state][time], natural column order (rows from 2 nsec on: zero)
+    std::vector<double> ftab;  // [ngroups][kw][16]: M_g, lane m = MFMA row m, in the tap table's layout
+    std::vector<double> Cp;    // [16][12]: C[rsos_fold_time(m)][state]
+    double amp = 0.0;
+    bool ok = false;  // amp <= kRsosFoldAmp (and T is invertible)
+};
+static void rsos_fold_tables(const SosCoefs& cf, const double* tab, int ngroups, int kw, RsosFold& F) {
+    typedef long double R;
+    const int B = 16;
+    std::vector<R> Tm, Cm, Dm, Am;
+    rsos_block_columns<R>(cf, Tm, Cm, Dm, Am);
+    F = RsosFold{};
+    F.E.assign(12 * B, 0.0);
+    F.Cp.assign(B * 12, 0.0);
+    F.ftab.assign((size_t)ngroups * kw * 16, 0.0);
+    F.amp = INFINITY;
+    if (!(std::fabs((double)Tm[0]) > 0.0) || !std::isfinite((double)Tm[0])) return;  // (b0 = 0 somewhere: no inverse)
+    // T . Ti = I by forward substitution, row by row
+    std::vector<R> Ti(B * B, 0.0L), E(12 * B, 0.0L);
+    for (int j = 0; j < B; ++j)
+        for (int i = j; i < B; ++i) {
+            R a = i == j ? 1.0L : 0.0L;
+            for (int k = j; k < i; ++k) a -= Tm[i * B + k] * Ti[k * B + j];
+            Ti[i * B + j] = a / Tm[i * B + i];
+        }
+    R dmax = 0.0L, emax = 0.0L;
+    for (int i = 0; i < 12; ++i) {
+        R dsum = 0.0L, esum = 0.0L;
+        for (int j = 0; j < B; ++j) {
+            R a = 0.0L;
+            for (int k = j; k < B; ++k) a += Dm[i * B + k] * Ti[k * B + j];
+            E[i * B + j] = a;
+            dsum += fabsl(Dm[i * B + j]);
+        }
+        for (int j = 0; j < B; ++j) {  // (|E| |T|)_ij
+            R a = 0.0L;
+            for (int k = j; k < B; ++k) a += fabsl(E[i * B + k]) * fabsl(Tm[k * B + j]);
+            esum += a;
+        }
+        dmax = std::max(dmax, dsum);
+        emax = std::max(emax, esum);
+    }
+    F.amp = dmax > 0.0L ? (double)(emax / dmax) : INFINITY;
+    F.ok = std::isfinite(F.amp) && F.amp <= kRsosFoldAmp;
+    for (int i = 0; i < 12 * B; ++i) F.E[i] = (double)E[i];
+    for (int m = 0; m < B; ++m)
+        for (int d = 0; d < 12; ++d) F.Cp[m * 12 + d] = (double)Cm[rsos_fold_time(m) * 12 + d];
+    for (size_t r = 0; r < (size_t)ngroups * kw; ++r) {  // (row r: window slot kk of group g, its 16 outputs' taps)
+        const double* tp = tab + r * 16;
+        for (int m = 0; m < B; ++m) {
+            const int t = rsos_fold_time(m);
+            R a = 0.0L;
+            for (int k = 0; k <= t; ++k) a += Tm[t * B + k] * (R)tp[k];
+            F.ftab[r * 16 + m] = (double)a;
+        }
+    }
+}
+
+// a folded plan's operands behind what `mats` holds (RsSos::fold_off): E and the permuted C as MFMA operands -- Mat[lane & 15][4 v +
+// (lane >> 4)] per k-step v, the contracted index of E . Z being Z's MFMA row --, then M_g, which has the operand form as it is
+static void rsos_fold_operands(const RsosFold& F, std::vector<double>& mats) {
+    const size_t o = mats.size();
+    mats.resize(o + (size_t)7 * 64 + F.ftab.size(), 0.0);
+    for (int lane = 0; lane < 64; ++lane) {
+        const int i = lane & 15, kq = lane >> 4;
+        for (int v = 0; v < 4; ++v) {
+            const int k = 4 * v + kq;
+            mats[o + (size_t)v * 64 + lane] = i < 12 ? F.E[i * 16 + rsos_fold_time(k)] : 0.0;  // E[state i][time of row k]
+            if (v < 3) mats[o + (size_t)(4 + v) * 64 + lane] = F.Cp[i * 12 + k];                // C[time of row i][state k]
+        }
+    }
+    std::copy(F.ftab.begin(), F.ftab.end(), mats.begin() + (ptrdiff_t)(o + 7 * 64));
+}
+
+// (the C-ABI's diagnostic: sections as [nsec][6] rows b0 b1 b2 1 a1 a2)
+static SosCoefs sos_rows_coefs(const double* sos, int nsec, double gain) {
+    SosCoefs cf{};
+    cf.nsec = nsec;
+    cf.gain = gain;
+    for (int f = 0; f < nsec; ++f) {
+        cf.b0[f] = sos[6 * f + 0];
+        cf.b1[f] = sos[6 * f + 1];
+        cf.b2[f] = sos[6 * f + 2];
+        cf.a1[f] = sos[6 * f + 4];
+        cf.a2[f] = sos[6 * f + 5];
+    }
+    return cf;
+}
+void rsos_fold_tables_sos(const double* sos, int nsec, double gain, const double* tab, int ngroups, int kw, double* e, double* ftab, double* amp,
+                          int* fold) {
+    RsosFold F;
+    rsos_fold_tables(sos_rows_coefs(sos, nsec, gain), tab, ngroups, kw, F);
+    std::copy(F.E.begin(), F.E.end(), e);
+    std::copy(F.ftab.begin(), F.ftab.end(), ftab);
+    *amp = F.amp;
+    *fold = F.ok ? 1 : 0;
 }
 
 // The state a range's warm-up leaves, as a matrix (k_rsos.hip, rsos_wproj_*).  The kernel walks the wp warm-up periods of a
@@ -2120,20 +2242,10 @@ static void rsos_wproj_matrix(const SosCoefs& cf, const double* tab, const int* 
     for (size_t i = 0; i < acc.size(); ++i) V[i] = (double)acc[i];
 }
 
-// (the C-ABI's diagnostic: sections as [nsec][6] rows b0 b1 b2 1 a1 a2)
+// (the C-ABI's diagnostic)
 void rsos_wproj_matrix_sos(const double* sos, int nsec, double gain, const double* tab, const int* jend, int ngroups, int kw, int64_t M, int wp,
                            std::vector<double>& V, int& j0, int& K) {
-    SosCoefs cf{};
-    cf.nsec = nsec;
-    cf.gain = gain;
-    for (int f = 0; f < nsec; ++f) {
-        cf.b0[f] = sos[6 * f + 0];
-        cf.b1[f] = sos[6 * f + 1];
-        cf.b2[f] = sos[6 * f + 2];
-        cf.a1[f] = sos[6 * f + 4];
-        cf.a2[f] = sos[6 * f + 5];
-    }
-    rsos_wproj_matrix(cf, tab, jend, ngroups, kw, M, wp, V, j0, K);
+    rsos_wproj_matrix(sos_rows_coefs(sos, nsec, gain), tab, jend, ngroups, kw, M, wp, V, j0, K);
 }
 
 // ---------------------------------------------------------------------------
@@ -2444,7 +2556,22 @@ struct RsosFusion : RsosRanges {
                 wpj = c0.dtype == SO_F64 && c0.array_node >= 0 && (c0.nsteps == 0 || sine);
             }
             const double t_pro = wpj ? 0.013 * (double)(wp * Mp + kwp) : 0.0;
-            const double t_fused = (double)((ngrp + cus - 1) / cus) * ((double)((pr + (wpj ? 0 : wp)) * ngp) * 0.30 * unit_cost * (ks + 14) / 28.0 + t_pro) + 15.0;
+            // (a plan that will run the folded block -- fold_tables() below, from the same facts for groups of eight channels and more,
+            //  whose geometry is the twelve- or eight-wave one -- walks its periods at 0.97 of the pace: the headline's stage 0.948 -
+            //  0.952 -> 0.915 - 0.924 ms, 12.5 M x 8 0.489 - 0.490 -> 0.478 - 0.479, profiles/r10/fold_bench.jsonl; no length sweep was run)
+            double fold_pace = 1.0;
+            if (!std::getenv("SIGOPS_RSOS_NOFOLD") && !std::getenv("SIGOPS_RSOS_NWAVES") && nodes[S2.node].dtype == SO_F64 && !two_arrays && !was_ga && ct >= 8 &&
+                (plain_src ? S3.in_array_node >= 0 && nodes[nodes[S3.node].kids[0]].dtype != SO_F32
+                           : S3.carriers[0].dtype == SO_F64 && S3.carriers[0].array_node >= 0)) {
+                const std::vector<double>& tb = own_tab ? own_taps : S3.tab_host;
+                if (tb.size() == (size_t)ngp * kwp * 16) {
+                    RsosFold F;
+                    rsos_fold_tables(S2.groups[0], tb.data(), ngp, kwp, F);
+                    if (F.ok) fold_pace = 0.97;
+                }
+            }
+            const double t_fused =
+                (double)((ngrp + cus - 1) / cus) * ((double)((pr + (wpj ? 0 : wp)) * ngp) * 0.30 * unit_cost * fold_pace * (ks + 14) / 28.0 + t_pro) + 15.0;
             const double t_two = 8.0e-6 * (double)need * nch + 95.0;
             if (std::getenv("SIGOPS_DEBUG_PLAN"))
                 std::fprintf(stderr, "[sigops] k_rsos estimate: fused %.0f us (%lld groups, %lld + %lld periods), two kernels %.0f us\n", t_fused,
@@ -2655,6 +2782,30 @@ struct RsosFusion : RsosRanges {
         }
     }
 
+    // appends to the filter stage's rsos_mats_host (behind the projection's tables); sets RsSos::fold / fold_off
+    void fold_tables() {
+        // The folded block (rsos_fold_tables above): a Float64 result over a Float64 ring, the twelve- and eight-wave geometries
+        // (any tap form, any fused step: the loader is what it was), and a cascade the gate admits.  A row's first output is a
+        // multiple of 16 -- (range x pr - wp) L with L a multiple of 16, checked here -- so the blocks in front of the signal's
+        // first output are whole blocks and zeroing their Z is zeroing their X.  SIGOPS_RSOS_NOFOLD=1: the unfolded block.
+        // Carrier 0 reads an ARRAY, as for the projection: what K1 materialised for this kernel (a stage buffer) takes the block the
+        // two-array form of the same tree takes -- the sixteen-wave geometry, unfolded -- and their results are compared bit for bit.
+        const std::vector<double>& tb = own_tab ? S2.rsos_tab_host : S3.tab_host;
+        S2.rs.fold = 0;
+        S2.rs.fold_off = 0;
+        if (std::getenv("SIGOPS_RSOS_NOFOLD") || nodes[S2.node].dtype != SO_F64 || g.src32 || g.ring32 || g.x32 || g.f32m || (g.nwaves != 12 && g.nwaves != 8) ||
+            L % 16 != 0 || tb.size() != (size_t)ngp * kwp * 16 || S3.carriers[0].array_node < 0)
+            return;
+        RsosFold F;
+        rsos_fold_tables(S2.groups[0], tb.data(), ngp, kwp, F);
+        if (std::getenv("SIGOPS_DEBUG_PLAN"))
+            std::fprintf(stderr, "[sigops] k_rsos: folded block %s: amp %.3g (gate %.0f)\n", F.ok ? "taken" : "declined", F.amp, kRsosFoldAmp);
+        if (!F.ok) return;
+        S2.rs.fold_off = (int32_t)S2.rsos_mats_host.size();
+        rsos_fold_operands(F, S2.rsos_mats_host);
+        S2.rs.fold = 1;
+    }
+
     void commit_launch() {
         S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
         // first range per channel that ended in a non-finite state: two sets of words, used in turn (run_rsos_fused)
@@ -2708,6 +2859,7 @@ void Plan::fuse_resample_sos() {
         F.rewrite_carriers();
         F.commit();
         F.wproj_tables();
+        F.fold_tables();
         F.commit_launch();
     }
 }

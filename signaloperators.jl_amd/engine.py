@@ -133,13 +133,14 @@ class Plan:
         L = K.lib()
         return {"graph_replays": L.so_plan_counter(self.handle, 0), "graph_captures": L.so_plan_counter(self.handle, 1),
                 "direct_executes": L.so_plan_counter(self.handle, 2), "fused_mfmas_per_block": L.so_plan_counter(self.handle, 3),
-                "wproj": L.so_plan_counter(self.handle, 4)}
+                "wproj": L.so_plan_counter(self.handle, 4), "fold": L.so_plan_counter(self.handle, 10)}
 
     def rsos_geometry(self):
-        """the first fused resampler + IIR launch's ranges (so_plan_counter 5 .. 9): periods per range, warm-up periods, input
-        frames per period, frames a projected warm-up reads and the first of them relative to the warm-up's first input"""
+        """the first fused resampler + IIR launch's ranges (so_plan_counter 5 .. 10): periods per range, warm-up periods, input
+        frames per period, frames a projected warm-up reads and the first of them relative to the warm-up's first input, and
+        whether the launch runs the folded block"""
         L = K.lib()
-        return {k: L.so_plan_counter(self.handle, i) for i, k in enumerate(("pr", "wp", "M", "wproj_frames", "wproj_first"), 5)}
+        return {k: L.so_plan_counter(self.handle, i) for i, k in enumerate(("pr", "wp", "M", "wproj_frames", "wproj_first", "fold"), 5)}
 
     def steps(self):
         """per-step statistics of the last (profiled) execute: so_plan_step_info"""
