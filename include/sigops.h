@@ -87,7 +87,8 @@ typedef enum so_kind {
     SO_NODE_CUMSUM = 14,  /* Cumsum / Integrate: the running sum over one fixed summation tree (no reference counterpart) */
     SO_NODE_MOVING = 15,  /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
     SO_NODE_MOVSUM = 16,  /* MovingSum / MovingMean / MovingRMS: sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart) */
-    SO_NODE_RECUR = 17    /* Recur / OnePole / Smooth / PeakDecay: the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart) */
+    SO_NODE_RECUR = 17,   /* Recur / OnePole / Smooth / PeakDecay: the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart) */
+    SO_NODE_RECUR2 = 18   /* Recur2 / Resonator / Sweep: the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -314,6 +315,23 @@ typedef enum so_rskind {
  *            Smooth: i0 = 0 with b = (1 - a) x; PeakDecay(x, r): i0 = 1, a = r, b = x.  i0 outside {0, 1}, a child count
  *            other than 1 or 2, a non-finite d0 in the one-child form or a channel count of a that is neither 1 nor b's is
  *            SO_ERR_INVALID; an infinite b or a finite a shorter than b SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
+ *  RECUR2    one child: child 0 = b, d0 = the constant a1, d1 = the constant a2 (finite)   three children: child 0 = a1,
+ *            child 1 = a2, child 2 = b
+ *            b finite, Float32 / Float64; a1 and a2 Float32 / Float64, each of 1 channel (every channel of b reads it) or of
+ *            b's, infinite or at least as long as b (a constant next to a signal is a CONST child); every other field 0.
+ *            Per channel y[0] = b[0], y[1] = (a1[1] y[0] + a2[1] (+0.0)) + b[1], y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] in
+ *            Float64 (Float32 inputs widen exactly), every product and every sum rounded once, never fused -- over ONE tree
+ *            that depends on the frame index only, Cumsum's, on elements (M, v), the affine maps s -> M s + v on the state
+ *            s = (y[n], y[n-1]): runs of 16 frames in which the composite advances by a shift, an inclusive Kogge-Stone scan
+ *            of joins over the 64 run totals of a tile of 1024 frames (the joined entries double-doubles, formed by
+ *            error-free transformations in Float64), sequential carries over the 16 tiles of a chunk and over the
+ *            chunks of 16384 frames; the outputs of a run are the recurrence itself walked from the state that
+ *            entered it ("Recur2"; tests/recur2_ref.py is the definition).  Constants run the operations rows of
+ *            them would.  The node has b's length, frame rate and channels and is Float64.  Recur2(a1, a2, b) as it is;
+ *            Resonator(x, fc, bw): a1 = 2 r cos(theta), a2 = -r^2, b = (1 - r^2) sin(theta) x; Sweep: the cookbook biquad's
+ *            feedback in a1, a2 and its feed-forward taps in b.  A child count other than 1 or 3, a non-finite d0 or d1 in
+ *            the one-child form or a channel count of a1 or a2 that is neither 1 nor b's is SO_ERR_INVALID; an infinite b or
+ *            a finite a1 or a2 shorter than b SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

@@ -102,6 +102,7 @@ static const char* stage_step_name(const Stage& S) {
     case ST_MOVING: return "k_moving";
     case ST_MOVSUM: return "k_movsum";
     case ST_RECUR: return "k_recur";
+    case ST_RECUR2: return "k_recur2";
     default: return "k_sumsq";
     }
 }
@@ -139,8 +140,14 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return (S.in_frames * kid_esz(0) + (S.need - S.base) * 8) * (int64_t)N.nch;
     case ST_RECUR: {  // per sample: b read twice where it lies (the totals' pass and the scan's), a row of a twice as Float64, one Float64 written
         const bool row = N.kids.size() == 2;
-        const int64_t a_rows = !row ? 0 : S.pos_pitch == 0 ? 1 : N.nch;
+        const int64_t a_rows = !row ? 0 : S.side[0].pitch == 0 ? 1 : N.nch;
         return S.need * ((int64_t)N.nch * (2 * kid_esz(row ? 1 : 0) + 8) + a_rows * 16);
+    }
+    case ST_RECUR2: {  // per sample: b read twice where it lies, each row of a1 and of a2 twice as Float64, one Float64 written
+        const bool row = N.kids.size() == 3;
+        int64_t a_rows = 0;
+        for (int w = 0; row && w < 2; ++w) a_rows += S.side[w].pitch == 0 ? 1 : N.nch;
+        return S.need * ((int64_t)N.nch * (2 * kid_esz(row ? 2 : 0) + 8) + a_rows * 16);
     }
     default: return (S.need - S.base) * N.nch * esz;
     }
@@ -186,7 +193,7 @@ void Plan::finalize() {
             if (car_has_arr2(c)) stage_host_array(c.array_node2);
         }
         stage_host_array(S.in_array_node);
-        stage_host_array(S.pos_array_node);
+        for (auto& sd : S.side) stage_host_array(sd.array_node);
     }
     if (!out.is_device && out.nframes > 0) {
         Buf b;
@@ -313,7 +320,8 @@ void Plan::finalize() {
             continue;
         }
         if (S.pw_step >= 0) push_pw_step(S.pw_step);
-        if (S.pos_pw_step >= 0) push_pw_step(S.pos_pw_step);
+        for (auto& sd : S.side)
+            if (sd.pw_step >= 0) push_pw_step(sd.pw_step);
         if (S.fused_away) continue;  // (runs inside its consumer's launch)
         Step st{1, sid, stage_step_name(S), 0};
         st.bytes = stage_step_bytes(this, sid);
@@ -390,7 +398,8 @@ void Plan::plan_lanes() {
         } else {
             const Stage& S = stages[st.idx];
             if (S.in_buf >= 0 && S.rsos_src < 0) rd[i].insert(S.in_buf);
-            if (S.pos_buf >= 0) rd[i].insert(S.pos_buf);
+            for (auto& sd : S.side)
+                if (sd.buf >= 0) rd[i].insert(sd.buf);
             carrier_reads(S.rsos_src >= 0 ? stages[S.rsos_src].carriers : S.carriers, rd[i]);
             if (S.win_off >= 0) wr[i].insert(-100 - st.idx);  // its own window of the result
             else wr[i].insert(st.idx == alias_stage ? kFinal : S.out_buf);
@@ -528,7 +537,7 @@ static View stage_in(Plan* P, const Stage& S, int nch, int dtype) {
 // SampleAt, Comb and Cumsum, whose kernels store Float64 only, get 8 bytes for both: their nodes are Float64 (build_nodes),
 // and plan_create lets only a periodic resampler or a filter narrow, so alias_narrow is false where one of them is aliased.
 // Moving stores its node's type, Float32 or Float64, and is aliased only to a result of that type.
-// Movsum and Recur store Float64 like Cumsum: their nodes are Float64.
+// Movsum, Recur and Recur2 store Float64 like Cumsum: their nodes are Float64.
 // A member of an RsBatch is never the aliased stage (fuse_plain_sos skips it): k_rsos_batch's members write windows or buffers.
 static View stage_out(Plan* P, int sid, void* outp) {
     const Stage& S = P->stages[sid];
@@ -776,13 +785,13 @@ static int run_sample_at(Plan* P, const Step& s, void* outp, hipStream_t st) {
     a.xfs = S.x_fstride;
     a.N = S.in_frames;
     a.x_f32 = xdt == SO_F32;
-    if (S.pos_array_node >= 0) {
-        a.pos = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
-        a.pcs = S.pos_pitch;
+    if (S.side[0].array_node >= 0) {
+        a.pos = (const double*)array_base(P, S.side[0].array_node) + S.side[0].offset;
+        a.pcs = S.side[0].pitch;
     } else {
-        const Buf& b = P->bufs[S.pos_buf];
+        const Buf& b = P->bufs[S.side[0].buf];
         a.pos = (const double*)b.d;
-        a.pcs = S.pos_pitch == 0 ? 0 : b.pitch;
+        a.pcs = S.side[0].pitch == 0 ? 0 : b.pitch;
     }
     a.y = (double*)out.d;
     a.ycs = out.pitch;
@@ -858,13 +867,13 @@ static int run_recur(Plan* P, const Step& s, void* outp, hipStream_t st) {
     a.b_f32 = bdt == SO_F32;
     if (!row) {
         a.ac = N.nd.d0;
-    } else if (S.pos_array_node >= 0) {
-        a.a = (const double*)array_base(P, S.pos_array_node) + S.pos_offset;
-        a.acs = S.pos_pitch;
+    } else if (S.side[0].array_node >= 0) {
+        a.a = (const double*)array_base(P, S.side[0].array_node) + S.side[0].offset;
+        a.acs = S.side[0].pitch;
     } else {
-        const Buf& b = P->bufs[S.pos_buf];
+        const Buf& b = P->bufs[S.side[0].buf];
         a.a = (const double*)b.d;
-        a.acs = S.pos_pitch == 0 ? 0 : b.pitch;
+        a.acs = S.side[0].pitch == 0 ? 0 : b.pitch;
     }
     a.y = (double*)out.d;
     a.ycs = out.pitch;
@@ -876,6 +885,41 @@ static int run_recur(Plan* P, const Step& s, void* outp, hipStream_t st) {
     const int nl = launch_recur(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
     if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Recur: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
+    return nl;
+}
+
+static int run_recur2(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const bool row = N.kids.size() == 3;
+    const int bdt = P->nodes[N.kids[row ? 2 : 0]].dtype;
+    const View in = stage_in(P, S, N.nch, bdt), out = stage_out(P, s.idx, outp);
+    Recur2Args a{};
+    a.b = in.d;
+    a.bcs = in.pitch;
+    a.bfs = S.x_fstride;
+    a.b_f32 = bdt == SO_F32;
+    a.ac[0] = N.nd.d0, a.ac[1] = N.nd.d1;
+    for (int w = 0; row && w < 2; ++w) {
+        const Stage::Side& sd = S.side[w];
+        if (sd.array_node >= 0) {
+            a.a[w] = (const double*)array_base(P, sd.array_node) + sd.offset;
+            a.acs[w] = sd.pitch;
+        } else {
+            const Buf& b = P->bufs[sd.buf];
+            a.a[w] = (const double*)b.d;
+            a.acs[w] = sd.pitch == 0 ? 0 : b.pitch;
+        }
+    }
+    a.y = (double*)out.d;
+    a.ycs = out.pitch;
+    a.n = S.need;
+    a.nch = N.nch;
+    a.tot_pitch = cumsum_totals(S.need);
+    a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
+    const int nl = launch_recur2(a, st);
+    // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Recur2: more than 65535 channels, or 2^31 chunks of 16384 frames and more, are not lowered");
     return nl;
 }
 
@@ -1283,6 +1327,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 case ST_MOVING: nl = run_moving(P, s, outp, st); break;
                 case ST_MOVSUM: nl = run_movsum(P, s, outp, st); break;
                 case ST_RECUR: nl = run_recur(P, s, outp, st); break;
+                case ST_RECUR2: nl = run_recur2(P, s, outp, st); break;
                 case ST_SOS: nl = run_sos(P, s, outp, st); break;
                 case ST_RESAMPLE: nl = run_resample(P, s, outp, st); break;
                 default: nl = run_norm(P, s, outp, st); break;

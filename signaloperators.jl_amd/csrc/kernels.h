@@ -164,6 +164,33 @@ struct RecurArgs {
     int32_t nch, b_f32, op;
 };
 int launch_recur(const RecurArgs& a, hipStream_t st);
+// Recur2 / Resonator / Sweep (k_recur2.hip, -ffp-contract=off): per channel the second-order scan
+// y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n], y[0] = b[0], y[1] = (a1[1] y[0] + a2[1] (+0.0)) + b[1], in Float64 over
+// Cumsum's tree (the constants above; DESIGN.md "Recur2"; tests/recur2_ref.py is the definition), every product and every
+// sum rounded on its own.  An element of the scan is (M, v), the affine map s -> M s + v on the state s = (y[n], y[n-1]):
+// six entries.  Inside a run of kCumsumRun frames the composite advances by a shift in Float64 (row 0 <- a1 row 0 + a2
+// row 1, row 1 <- the old row 0); the 64 run totals of a tile go through a Kogge-Stone scan of joins whose entries are
+// double-doubles (error-free transformations in plain Float64 operations, no FMA); a state is carried from tile to tile
+// of a chunk, a composite and then a state from chunk to chunk; the outputs of a run are the recurrence itself walked
+// from the state that entered it.
+// Reduce-then-scan, no workgroup waits for another: k_recur2_totals (the chunk-local composite of every chunk but the last
+// -> tot), k_recur2_carry (tot -> the state that enters the chunk behind, in place of the composite's v, one workgroup per
+// channel), k_recur2_scan (recomputes the chunk, applies the entering state, stores).  A signal of one chunk is one
+// launch.  Strides in elements.  Returns the number of launches, -1 when the shape cannot be launched.
+struct Recur2Args {
+    const void* b;     // element (n, c) at b[n * bfs + c * bcs]
+    int64_t bfs, bcs;
+    const double* a[2];  // a1, a2: a row of coefficients per channel, a[i][n + c * acs[i]] (acs 0: one row for every channel); both nullptr: the constants ac
+    int64_t acs[2];
+    double ac[2];
+    double* y;         // y[n + c * ycs]
+    int64_t ycs;
+    double* tot;       // [nch][tot_pitch][12] scratch, tot_pitch >= cumsum_totals(n): the high words (M00, M01, M10, M11, v0, v1) of a chunk, then the low words; v0, v1 become (s0, s1)
+    int64_t tot_pitch;
+    int64_t n;
+    int32_t nch, b_f32;
+};
+int launch_recur2(const Recur2Args& a, hipStream_t st);
 // MovingMax / MovingMin (k_moving.hip): output j in [0, n_out) of a channel is the greatest (least) of the input frames
 // [j + off - back, j + off + ahead] clipped to [0, n_in), under the order -Inf < .. < -0.0 < +0.0 < .. < +Inf, NaN if any of
 // them is NaN; the result has the input's type and is a bit copy of that sample.  Compared on a monotone integer key, so any

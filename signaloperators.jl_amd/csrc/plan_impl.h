@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM, ST_RECUR };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM, ST_RECUR, ST_RECUR2 };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -119,7 +119,7 @@ struct Stage {
     bool norm_direct = false; // Normpower of a plain array leaf: the rms is taken over the array where it lies, readers divide its loads
     bool under_norm = false;  // a Normpower consumes this stage (directly or through further stages)
     int64_t norm_df = 0;      // ... the largest frame offset it is read at on such a path (0: every Normpower's region starts at this stage's first frame)
-    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys; Movsum's block totals and dyadic nodes, [nch * movsum_scratch(..)] Float64; Recur's chunk totals, [nch][cumsum_totals(need)][2] Float64
+    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys; Movsum's block totals and dyadic nodes, [nch * movsum_scratch(..)] Float64; Recur's chunk totals, [nch][cumsum_totals(need)][2] Float64; Recur2's, [nch][cumsum_totals(need)][12] Float64
     int64_t win_off = -1;  // >= 0: the stage writes the RESULT's frames [win_off, win_off + need) itself (window aliasing)
     // input source (after processing): either a materialised buffer or a direct view
     const void* in_ptr = nullptr;  // direct device pointer (nullptr -> in_buf)
@@ -129,8 +129,11 @@ struct Stage {
     int pw_step = -1;  // pointwise step materialising the input
     // SampleAt: the input above is the table x (all of it); this second one the positions of the frames [base, need)
     // Recur: the input above is b; this second one the coefficients a of the frames [0, need), when a is a signal
-    int pos_buf = -1, pos_array_node = -1, pos_pw_step = -1;
-    int64_t pos_offset = 0, pos_pitch = 0;  // elements (an array read in place); pos_pitch 0: one row for every channel
+    // Recur2: the input above is b; side[0] and side[1] the coefficients a1 and a2 of the frames [0, need), when they are signals
+    struct Side {
+        int buf = -1, array_node = -1, pw_step = -1;
+        int64_t offset = 0, pitch = 0;  // elements (an array read in place); pitch 0: one row for every channel
+    } side[2];
     int64_t x_fstride = 1;                  // the table's frame stride where it lies (an interleaved array is read in place too)
     std::vector<DCarrier> carriers;  // periodic resampler: input expressed as carriers
     int car_buf = -1;
@@ -487,7 +490,8 @@ struct Plan {
     void process_moving(int sid);
     void process_comb(int sid);  // (Comb and Cumsum: the stages that compute [0, need) from one plain input)
     void process_recur(int sid);
-    void second_input(int sid, int kid, int64_t base, int64_t frames);  // (SampleAt's positions, Recur's coefficients: Stage::pos_*)
+    void process_recur2(int sid);
+    void second_input(int sid, int kid, int64_t base, int64_t frames, int which = 0);  // (SampleAt's positions, Recur's and Recur2's coefficients: Stage::side[which])
     void stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype);
     // the resampler: its forms, tried in this order (each returns at once where an earlier one took the stage)
     void process_resample(int sid);

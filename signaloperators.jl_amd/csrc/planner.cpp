@@ -340,6 +340,30 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             if (row && !N.short_skip) N.short_skip = b.short_skip;
             break;
         }
+        case SO_NODE_RECUR2: {  // the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart; DESIGN.md "Recur2")
+            const std::string where = "node " + std::to_string(i) + ": Recur2 ";
+            if (N.kids.size() != 1 && N.kids.size() != 3)
+                fail(SO_ERR_INVALID, where + "takes one child, the signal b (the constants a1 in d0 and a2 in d1), or three, a1, a2 and b (" + std::to_string(N.kids.size()) + " given)");
+            const bool row = N.kids.size() == 3;
+            Node& b = kid(row ? 2 : 0);
+            if (!row && !(std::isfinite(nd.d0) && std::isfinite(nd.d1))) fail(SO_ERR_INVALID, where + "takes finite constants a1 and a2");
+            if (isinf_(b.len)) fail(SO_ERR_LENGTH, where + "needs a signal b of known, finite length (use `Until`)");
+            if (b.dtype != SO_F32 && b.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal b (integer sample types are not lowered)");
+            for (int w = 0; row && w < 2; ++w) {
+                Node& a = kid(w);
+                const std::string name = w ? "a2" : "a1";
+                if (a.dtype != SO_F32 && a.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal " + name + " (integer sample types are not lowered)");
+                if (a.nch != 1 && a.nch != b.nch)
+                    fail(SO_ERR_INVALID, where + "coefficients " + name + " have " + std::to_string(a.nch) + " channels: 1 or b's " + std::to_string(b.nch) + " expected");
+                if (!isinf_(a.len) && a.len.n < b.len.n)
+                    fail(SO_ERR_LENGTH, where + "coefficients " + name + " have " + std::to_string(a.len.n) + " frames, fewer than b's " + std::to_string(b.len.n));
+            }
+            N.len = b.len;
+            N.nch = b.nch;
+            N.dtype = SO_F64;
+            if (row && !N.short_skip) N.short_skip = b.short_skip;
+            break;
+        }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
         }
         // nodes that ask their (first) child for a block whenever they are asked for one themselves
@@ -954,15 +978,16 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         out.push_back({r, add_expr(e)});
         return out;
     }
-    case SO_NODE_RECUR: {
+    case SO_NODE_RECUR:
+    case SO_NODE_RECUR2: {
         // a stage like Cumsum's: the recurrence starts at frame 0, so the stage computes the frames [0, need) whoever reads
-        // it, from both inputs over the same frames (process_recur, stages.cpp)
+        // it, from all its inputs over the same frames (process_recur, process_recur2, stages.cpp)
         if (dry) {
             for (int k : N.kids) check_frames(k, m.sf ? r.b + m.df : m.df + 1);
             out.push_back({r, mk_const(0.0, N.dtype)});
             return out;
         }
-        const int sid = stage_for(ni, ST_RECUR);
+        const int sid = stage_for(ni, N.nd.kind == SO_NODE_RECUR2 ? ST_RECUR2 : ST_RECUR);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;
@@ -1541,7 +1566,7 @@ void Plan::try_window_alias(std::vector<Piece>& rootp) {
         for (auto& L : leaves)
             if (L.buf == b) other = true;
         for (auto& S2 : stages) {
-            if (S2.in_buf == b || S2.pos_buf == b) other = true;
+            if (S2.in_buf == b || S2.side[0].buf == b || S2.side[1].buf == b) other = true;
             for (auto& c : S2.carriers)
                 if (c.buf == b) other = true;
         }
@@ -1671,7 +1696,7 @@ Plan* plan_create(const so_node_t* nodes, int32_t n_nodes, int32_t root, const s
                         if (L.buf == e.leaf.buf) P->alias_stage = -1;
                 if (P->alias_stage >= 0)
                     for (auto& S : P->stages)
-                        if (S.in_buf == e.leaf.buf || S.pos_buf == e.leaf.buf) P->alias_stage = -1;
+                        if (S.in_buf == e.leaf.buf || S.side[0].buf == e.leaf.buf || S.side[1].buf == e.leaf.buf) P->alias_stage = -1;
             }
         }
         const auto t_stg = std::chrono::steady_clock::now();

@@ -4,7 +4,7 @@
 //
 // Map (routine -- what it decides -- the Stage fields it writes):
 //   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
-//                            process_sample_at, process_comb, process_moving (Moving and Movsum), process_recur (input: stage_input, second_input)
+//                            process_sample_at, process_comb, process_moving (Moving and Movsum), process_recur, process_recur2 (input: stage_input, second_input)
 //   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
 //                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
 //     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
@@ -549,27 +549,28 @@ void Plan::process_sample_at(int sid) {
     second_input(sid, pk, base, need - base);
 }
 
-// The second input of a stage -- SampleAt's positions, Recur's coefficients -- over `frames` frames from `base` of child
-// `kid`: a Float64 array with unit frame stride read in place, anything else (a formula, a Float32 array, another stage's
-// buffer) one pointwise step into a Float64 buffer (Stage::pos_*).  One channel serves every channel of the stage (pitch 0).
-void Plan::second_input(int sid, int kid, int64_t base, int64_t frames) {
+// A further input of a stage -- SampleAt's positions, Recur's coefficients, each of Recur2's two -- over `frames` frames from
+// `base` of child `kid`: a Float64 array with unit frame stride read in place, anything else (a formula, a constant, a
+// Float32 array, another stage's buffer) one pointwise step into a Float64 buffer (Stage::side[which]).  One channel serves
+// every channel of the stage (pitch 0).
+void Plan::second_input(int sid, int kid, int64_t base, int64_t frames, int which) {
     const int pch = nodes[kid].nch;
     const std::vector<Piece> ps = lower(kid, Rect{0, frames, 0, pch}, Map{1, base, 1, 0});
     Stage& S = stages[sid];  // (re-taken: lower() may have appended stages)
     if (ps.size() == 1 && plain_load(exprs[ps[0].e], SO_F64, ps[0].r.c1 - ps[0].r.c0, true, true) && exprs[ps[0].e].array_node >= 0) {
         const Expr& e = exprs[ps[0].e];
-        S.pos_array_node = e.array_node;
-        S.pos_pitch = pch == 1 ? 0 : e.leaf.cstride;
-        S.pos_offset = leaf_offset(e.leaf);
+        S.side[which].array_node = e.array_node;
+        S.side[which].pitch = pch == 1 ? 0 : e.leaf.cstride;
+        S.side[which].offset = leaf_offset(e.leaf);
         count_array(e.array_node);
     } else {
         const int b = new_buf(frames, pch, SO_F64);
         const int step = emit_pointwise(ps, b, SO_F64);
         Stage& S2 = stages[sid];
-        S2.pos_buf = b;
-        S2.pos_pitch = pch == 1 ? 0 : -1;  // -1: pitch of pos_buf
-        S2.pos_offset = 0;
-        S2.pos_pw_step = step;
+        S2.side[which].buf = b;
+        S2.side[which].pitch = pch == 1 ? 0 : -1;  // -1: pitch of the buffer
+        S2.side[which].offset = 0;
+        S2.side[which].pw_step = step;
     }
 }
 
@@ -621,9 +622,43 @@ void Plan::process_recur(int sid) {
     if (std::getenv("SIGOPS_DEBUG_PLAN")) {
         const Stage& S = stages[sid];
         const std::string a = !row ? "the constant " + std::to_string(nodes[ni].nd.d0)
-                                   : std::string(S.pos_array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.pos_pitch == 0 ? ", one row for every channel" : "");
+                                   : std::string(S.side[0].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[0].pitch == 0 ? ", one row for every channel" : "");
         std::fprintf(stderr, "[sigops] Recur stage %d: %s, chunk totals a channel %lld, frames [0,%lld) x %d channels, b %s, a %s\n", sid, nodes[ni].nd.i0 ? "max-decay" : "affine",
                      (long long)cumsum_totals(need), (long long)need, nch, S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place", a.c_str());
+    }
+}
+
+// Recur2: Recur's rule with three inputs over the frames [0, need): b taken like Cumsum's x (stage_input), each coefficient
+// signal like Recur's a (second_input, side[0] for a1 and side[1] for a2).  A constant next to a signal arrives as a CONST
+// child and is materialised like any formula: one row of `need` doubles written once and read twice.  The stage owns twelve
+// Float64 per (chunk that has a chunk behind it, channel) besides: the chunk's composite (M, v), six double-doubles, whose
+// v the carry kernel turns into the state that enters the next chunk; every entry read is written by the same execute (k_recur2.hip), so
+// nothing clears them.
+void Plan::process_recur2(int sid) {
+    const int ni = stages[sid].node;
+    const bool row = nodes[ni].kids.size() == 3;
+    const int bk = nodes[ni].kids[row ? 2 : 0];
+    const int nch = nodes[ni].nch;
+    const int64_t need = stages[sid].need;
+    stages[sid].processed = true;
+    if (need <= 0) return;
+    stages[sid].base = stages[sid].in_base = 0;
+    bufs[stages[sid].out_buf].frame0 = 0;
+    stage_input(sid, lower(bk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[bk].dtype);
+    if (row)
+        for (int w = 0; w < 2; ++w) second_input(sid, nodes[ni].kids[w], 0, need, w);
+    if (cumsum_totals(need) > 0) {
+        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 96);
+        stages[sid].aux_buf = b;
+    }
+    if (std::getenv("SIGOPS_DEBUG_PLAN")) {
+        const Stage& S = stages[sid];
+        std::string a[2];
+        for (int w = 0; w < 2; ++w)
+            a[w] = !row ? "the constant " + std::to_string(w ? nodes[ni].nd.d1 : nodes[ni].nd.d0)
+                        : std::string(S.side[w].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[w].pitch == 0 ? ", one row for every channel" : "");
+        std::fprintf(stderr, "[sigops] Recur2 stage %d: chunk totals a channel %lld, frames [0,%lld) x %d channels, b %s, a1 %s, a2 %s\n", sid, (long long)cumsum_totals(need), (long long)need, nch,
+                     S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place", a[0].c_str(), a[1].c_str());
     }
 }
 
@@ -682,6 +717,7 @@ void Plan::process_stage(int sid) {
     case ST_COMB:
     case ST_CUMSUM: return process_comb(sid);
     case ST_RECUR: return process_recur(sid);
+    case ST_RECUR2: return process_recur2(sid);
     case ST_RESAMPLE: return process_resample(sid);
     case ST_SOS: return process_sos(sid);
     default: return process_norm(sid);

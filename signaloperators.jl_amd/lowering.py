@@ -260,8 +260,8 @@ def _demand(x, n, out, skip=0):
     elif isinstance(x, (S.CombSignal, S.CumsumSignal)):
         # the recurrence (the sum) starts at frame 0: the frames before a window are computed too
         _demand(x.signal, capped(x.signal, n), out, 0)
-    elif isinstance(x, S.RecurSignal):
-        # both inputs from frame 0: the recurrence starts there whatever window reads it
+    elif isinstance(x, (S.RecurSignal, S.Recur2Signal)):
+        # every input from frame 0: the recurrence starts there whatever window reads it
         for c in x.children:
             _demand(c, capped(c, n), out, 0)
     elif isinstance(x, S.MovingSignal):
@@ -582,6 +582,12 @@ def lower(x, nframes_out=None, rng=None):
             kids = tuple(rec(c) for c in s.children)
             r = common(s, K.NODE_RECUR)
             r.update(i0=s.op, d0=0.0 if s.a is None else s.a, children=kids)
+            idx = lw.add(**r)
+        elif isinstance(s, S.Recur2Signal):
+            # one child: b, the constants a1 in d0 and a2 in d1; three children: (a1, a2, b)
+            kids = tuple(rec(c) for c in s.children)
+            r = common(s, K.NODE_RECUR2)
+            r.update(d0=s.a1 if s.coefs is None else 0.0, d1=s.a2 if s.coefs is None else 0.0, children=kids)
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

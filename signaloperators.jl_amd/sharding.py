@@ -37,11 +37,12 @@ def _refuse_sample_at(x, what):
 
 
 # nodes whose frames depend on every frame before them: a rank cannot start in the middle, and handing the state on is not built
-_FROM_FRAME_0 = ((S.CombSignal, "Comb / Allpass"), (S.CumsumSignal, "Cumsum / Integrate"), (S.RecurSignal, "Recur / OnePole / Smooth / PeakDecay"))
+_FROM_FRAME_0 = ((S.CombSignal, "Comb / Allpass"), (S.CumsumSignal, "Cumsum / Integrate"), (S.RecurSignal, "Recur / OnePole / Smooth / PeakDecay"),
+                 (S.Recur2Signal, "Recur2 / Resonator / Sweep"))
 
 
 def _refuse_from_frame_0(x, what):
-    """a tree with a Comb, a Cumsum or a Recur node is not sharded: a rank's frames depend on every frame before them"""
+    """a tree with a Comb, a Cumsum, a Recur or a Recur2 node is not sharded: a rank's frames depend on every frame before them"""
     for cls, name in _FROM_FRAME_0:
         if isinstance(x, cls):
             raise S.ErrorException(f"{what}: sharding a tree that contains {name} over several GPUs is not built")

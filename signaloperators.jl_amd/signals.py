@@ -657,6 +657,34 @@ class RecurSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class Recur2Signal(AbstractSignal):
+    """`Recur2(a1, a2, b)` / `Resonator` / `Sweep`: per channel the second-order scan
+    `y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n]`, `y[0] = b[0]`, over one fixed tree (no reference counterpart;
+    include/sigops.h SO_NODE_RECUR2, DESIGN.md "Recur2").  The coefficients are the numbers `a1`, `a2` (then `coefs` is None)
+    or the two signals `coefs`, each of one channel or of `b`'s.  It has the length, frame rate and channels of `b` and is
+    Float64."""
+
+    evaltrait = "computed"
+
+    def __init__(self, a1, a2, b):
+        self.signal = b
+        if isinstance(a1, AbstractSignal):
+            self.coefs, self.a1, self.a2 = (a1, a2), None, None
+            self.children = (a1, a2, b)
+        else:
+            self.coefs, self.a1, self.a2 = None, float(a1), float(a2)
+            self.children = (b,)
+        self.fs = b.fs
+        self.nch = b.nch
+        self.dtype = F64
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
 ADD, MUL, SUB, DIV = "add", "mul", "sub", "div"
 TUPLECAT, GETCHAN, AS1CHANNEL, ASNCHANNELS, TOELTYPE, REVERSECH = (
@@ -1042,6 +1070,12 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return RecurSignal(x.a if x.coef is None else ToFramerate(x.coef, fs, bs), ToFramerate(x.signal, fs, bs), x.op)
+    if isinstance(x, Recur2Signal):  # Recur's two rules
+        if known:
+            return _resample(x, fs, bs)
+        if x.coefs is None:
+            return Recur2Signal(x.a1, x.a2, ToFramerate(x.signal, fs, bs))
+        return Recur2Signal(ToFramerate(x.coefs[0], fs, bs), ToFramerate(x.coefs[1], fs, bs), ToFramerate(x.signal, fs, bs))
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
@@ -1510,6 +1544,228 @@ def PeakDecay(*args, r=None):
     if len(args) != 2:
         error("PeakDecay(x, release) or PeakDecay(x, r=...) expected")
     return _PeakDecay(args[0], args[1], r)
+
+
+# --------------------------------------------------------------------------
+# Recur2 / Resonator / Sweep: second-order scans (no reference counterpart)
+def _Recur2(what, a1, a2, b):
+    """`what` names the construct in a refusal: "Recur2", or "Resonator (Recur2)" and "Sweep (Recur2)" for the wrappers"""
+    b = _assignal(b)
+    n = nframes(b)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal b must have a known, finite length (use `Until`): the recurrence starts at frame 0")
+    if b.dtype not in (F32, F64):
+        error(f"{what}: the signal b must be Float32 or Float64 (use `ToEltype`)")
+    coefs = []
+    for name, a in (("a1", a1), ("a2", a2)):
+        if _real_number(a):
+            if not math.isfinite(a):
+                error(f"{what}: the coefficient {name} must be a finite number or a signal, not {a!r}")
+            coefs.append(float(a))
+            continue
+        if isinstance(a, (bool, np.bool_, Quantity, str)) or a is None:
+            error(f"{what}: the coefficient {name} must be a number or a signal, not {a!r}")
+        a = _assignal(a)
+        if a.dtype not in (F32, F64):
+            error(f"{what}: the coefficient signal {name} must be Float32 or Float64 (use `ToEltype`)")
+        if a.nch not in (1, b.nch):
+            error(f"{what}: the coefficient signal {name} has {a.nch} channels; 1 or b's {b.nch} expected")
+        coefs.append(a)
+    if not any(isinstance(a, AbstractSignal) for a in coefs):
+        return Recur2Signal(coefs[0], coefs[1], b)
+    # one rate for the three: every known rate must be the same one, a missing one is taken from the others
+    fs = b.fs
+    for name, a in zip(("a1", "a2"), coefs):
+        if isinstance(a, AbstractSignal) and a.fs is not None:
+            if fs is not None and a.fs != fs:
+                error(f"{what}: the coefficient signal {name} has a frame rate of {a.fs} Hz and {'b' if b.fs is not None else 'the other coefficient'} one of {fs} Hz (use `ToFramerate`)")
+            fs = a.fs
+    if fs is not None and b.fs is None:
+        b = ToFramerate(b, fs)
+    for k, name in enumerate(("a1", "a2")):
+        a = coefs[k]
+        if not isinstance(a, AbstractSignal):
+            a = NumberSig(a, fs)  # a constant next to a signal: a row of it, written once by a pointwise step
+        elif a.fs is None and fs is not None:
+            a = ToFramerate(a, fs)
+        na = nframes(a)
+        if na is None or (not isknowninf(na) and na < n):
+            error(f"{what}: the coefficient signal {name} ({'an unknown number of' if na is None else na} frames) must be infinite or at least as long as b ({n} frames)")
+        coefs[k] = a
+    return Recur2Signal(coefs[0], coefs[1], b)
+
+
+def Recur2(*args):
+    """`Recur2(a1, a2, b)`, curried `b | Recur2(a1, a2)`: the second-order linear recurrence
+    `y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n]`, `y[0] = b[0]`, `y[1] = (a1[1] y[0] + a2[1] 0) + b[1]` per channel in
+    Float64 -- the recursive half of a filter whose cutoff or resonance moves over time.  Each coefficient is a finite real
+    number, or a Float32 / Float64 signal of one channel (every channel of `b` reads it) or of `b`'s channel count, infinite
+    or at least as long as `b`; a number next to a signal becomes a row of it.  A parallel scan rounds differently from a
+    loop, so the node fixes ONE tree that depends on the frame index only (Cumsum's: runs of 16 frames, a Kogge-Stone scan
+    over the 64 runs of a tile, sequential carries over the tiles of a chunk and over the chunks, on the affine maps
+    `s -> M s + v` of the state `(y[n], y[n-1])`; DESIGN.md "Recur2", tests/recur2_ref.py), every product and sum rounded on
+    its own: a window, a `stream` block and the whole sink give the same bits, and inside a run of 16 frames the outputs are
+    the loop's own operations on the state that entered the run; the composites are joined in double-double arithmetic,
+    which keeps poles close to `z = 1` or `z = -1` within 1e-8 of an extended-precision loop (DESIGN.md gives the figures).
+    The node is meant for stable coefficients: unstable stretches overflow the composites, and an `Inf` that meets a zero
+    of a composite gives NaN.  There is no initial state.  `b` must have a
+    known, finite length.  `stream` over the node recomputes the frames before every block (as over `Cumsum`);
+    `BlockStream` and multi-GPU shards refuse the node."""
+    if len(args) == 2:
+        a1, a2 = args
+        return Curried(lambda b: _Recur2("Recur2", a1, a2, b))
+    if len(args) != 3:
+        error("Recur2(a1, a2, b) expected")
+    return _Recur2("Recur2", args[0], args[1], args[2])
+
+
+def _hz_param(what, name, x, v, lowest=0.0, strict=False):
+    """a parameter of a wrapper: a number (for a frequency a quantity too) checked and returned as a float, or a signal at
+    the rate of x returned as a Float64 signal"""
+    if isinstance(v, Quantity) or _real_number(v):
+        if name == "q":
+            if isinstance(v, Quantity):
+                error(f"{what}: q is a plain number, not {v}")
+            hz = float(v)
+        else:
+            try:
+                hz = U.inHz(v)
+            except ValueError:
+                error(f"{what}: {name} = {v} is not a frequency")
+        if not math.isfinite(hz) or hz < lowest or (strict and hz <= lowest):
+            error(f"{what}: {name} must be a finite {'number' if name == 'q' else 'frequency'} {'>' if strict else '>='} {lowest:g}, not {v!r}")
+        return hz
+    if isinstance(v, (bool, np.bool_, str)) or v is None:
+        error(f"{what}: {name} must be a number or a signal, not {v!r}")
+    fs = _rate_for(what, x, f"{name} given as a signal")
+    v = _assignal(v)
+    if v.dtype not in (F32, F64):
+        error(f"{what}: the signal {name} must be Float32 or Float64 (use `ToEltype`)")
+    if v.nch not in (1, x.nch):
+        error(f"{what}: the signal {name} has {v.nch} channels; 1 or x's {x.nch} expected")
+    if v.fs is not None and v.fs != fs:
+        error(f"{what}: the signal {name} has a frame rate of {v.fs} Hz and x one of {fs} Hz (use `ToFramerate`)")
+    v = ToFramerate(v, fs)
+    return v if v.dtype == F64 else ToEltype(v, F64)
+
+
+def _formulas(what, x, params, fns, taps):
+    """`Recur2` from formulas: `params` are numbers or signals; `fns(*params) -> (a1, a2, c0, ..)` gives the two coefficients
+    and one gain per tap, `taps` being x and its delayed copies; b is the sum of the gains times the taps, left to right.
+    All numbers: `fns` runs on the host with `math`.  A signal among them: one traced map per coefficient and one for b."""
+    from .units import frames
+
+    n = nframes(x)
+    sig = [i for i, v in enumerate(params) if isinstance(v, AbstractSignal)]
+
+    def mix(gains, ts):
+        acc = gains[0] * ts[0]
+        for g, t in zip(gains[1:], ts[1:]):
+            acc = acc + g * t
+        return acc
+
+    if not sig:
+        a1, a2, *gains = fns(math, *params)
+        gains = [np.float64(g) for g in gains]  # (strong Float64: a Float32 x widens before it is multiplied)
+        if len(taps) == 1:
+            b = _OperateOn(MUL, [taps[0], NumberSig(gains[0])])
+        else:
+            b = _OperateOn(_map_code(Elementwise(lambda *ts: mix(gains, ts))), list(taps))
+        return _Recur2(what, a1, a2, b)
+
+    def full(args):
+        vals = list(params)
+        for k, i in enumerate(sig):
+            vals[i] = args[k]
+        return vals
+
+    ps = [params[i] for i in sig]
+    coef = [_OperateOn(_map_code(Elementwise(lambda *s, k=k: fns(np, *full(s))[k])), ps) for k in (0, 1)]
+    b = _OperateOn(_map_code(Elementwise(lambda *s: mix(fns(np, *full(s[: len(sig)]))[2:], s[len(sig):]))), ps + list(taps))
+    return _Recur2(what, coef[0], coef[1], _Until(b, n * frames))
+
+
+def _wrapper_input(what, x):
+    x = _assignal(x)
+    if x.dtype not in (F32, F64):
+        error(f"{what}: the signal x must be Float32 or Float64 (use `ToEltype`)")
+    n = nframes(x)
+    if n is None or isknowninf(n):
+        error(f"{what}: the signal x must have a known, finite length (use `Until`): the recurrence starts at frame 0")
+    return x
+
+
+def _Resonator(x, fc, bw):
+    what = "Resonator (Recur2)"
+    x = _wrapper_input(what, x)
+    fs = _rate_for(what, x, "a frequency in Hz")
+    fc, bw = _hz_param(what, "fc", x, fc), _hz_param(what, "bw", x, bw)
+
+    def fns(m, fc, bw):
+        r = m.exp(-math.pi * bw / fs)
+        th = 2.0 * math.pi * fc / fs
+        return 2.0 * r * m.cos(th), -(r * r), (1.0 - r * r) * m.sin(th)
+
+    return _formulas(what, x, [fc, bw], fns, [x])
+
+
+def Resonator(*args):
+    """`Resonator(x, fc, bw)`, curried `x | Resonator(fc, bw)`: the two-pole resonator at the centre frequency `fc` with the
+    bandwidth `bw`: `Recur2(2 r cos(theta), -r^2, (1 - r^2) sin(theta) x)` with `r = exp(-pi bw / framerate)` and
+    `theta = 2 pi fc / framerate`; its gain at `fc` is about one for narrow bandwidths.  `fc` and `bw` are each a frequency
+    (a number of Hz or a quantity; `math` on the host) or a signal of Hz at the rate of `x`, of one channel or of `x`'s
+    (the coefficients are then traced maps on the device): a resonator whose pitch follows `Cumsum`'s oscillator, a
+    formant glide."""
+    if len(args) == 2:
+        fc, bw = args
+        return Curried(lambda x: _Resonator(x, fc, bw))
+    if len(args) != 3:
+        error("Resonator(x, fc, bw) expected")
+    return _Resonator(args[0], args[1], args[2])
+
+
+def _Sweep(x, kind, fc, q):
+    what = "Sweep (Recur2)"
+    kind = kind if isinstance(kind, type) else type(kind)
+    if kind not in (Lowpass, Highpass, Bandpass):
+        error(f"{what}: the response must be Lowpass, Highpass or Bandpass, not {kind!r}")
+    x = _wrapper_input(what, x)
+    fs = _rate_for(what, x, "a frequency in Hz")
+    fc, q = _hz_param(what, "fc", x, fc), _hz_param(what, "q", x, q, strict=True)
+
+    def fns(m, fc, q):
+        w = 2.0 * math.pi * fc / fs
+        cw = m.cos(w)
+        alpha = m.sin(w) / (2.0 * q)
+        a0 = 1.0 + alpha
+        if kind is Lowpass:
+            b0, b1 = (1.0 - cw) / 2.0, 1.0 - cw
+            b2 = b0
+        elif kind is Highpass:
+            b0, b1 = (1.0 + cw) / 2.0, -(1.0 + cw)
+            b2 = b0
+        else:
+            b0, b1, b2 = alpha, 0.0 * alpha, -alpha
+        return 2.0 * cw / a0, -(1.0 - alpha) / a0, b0 / a0, b1 / a0, b2 / a0
+
+    return _formulas(what, x, [fc, q], fns, [x, _Delay(x, 1), _Delay(x, 2)])
+
+
+def Sweep(*args, q=math.sqrt(0.5)):
+    """`Sweep(x, Lowpass | Highpass | Bandpass, fc, q=sqrt(1/2))`, curried `x | Sweep(Lowpass, fc)`: the audio-EQ-cookbook
+    biquad with a cutoff (and a resonance) that may move -- a swept low-pass, a wah, an auto-filter driven by an envelope.
+    With `w = 2 pi fc / framerate`, `alpha = sin(w) / (2 q)` and `a0 = 1 + alpha` it runs as a direct form I with the
+    coefficients of frame n on all taps: `Recur2(2 cos(w) / a0, -(1 - alpha) / a0, (b0 x[n] + b1 x[n-1] + b2 x[n-2]) / a0)`,
+    the taps `x[n-1]` and `x[n-2]` being `Delay(x, 1)` and `Delay(x, 2)` (bit copies with zeros in front).  `fc` is a
+    frequency or a signal of Hz at the rate of `x`, `q > 0` a number or a signal.  `Bandpass` has a peak gain of 0 dB."""
+    if len(args) == 2:
+        kind, fc = args
+        return Curried(lambda x: _Sweep(x, kind, fc, q))
+    if len(args) == 4:
+        return _Sweep(args[0], args[1], args[2], args[3])
+    if len(args) != 3:
+        error("Sweep(x, response, fc, q=...) expected")
+    return _Sweep(args[0], args[1], args[2], q)
 
 
 # --------------------------------------------------------------------------

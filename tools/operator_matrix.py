@@ -58,6 +58,16 @@ cases = {
     "recur signal": lambda: so.Recur(A(), X),
     "onepole": lambda: so.OnePole(X, 1 * so.kHz),
     "peakdecay": lambda: so.PeakDecay(X, 50 * so.ms),
+    # `Recur2(a1, a2, b)` / `Resonator` / `Sweep` (include/sigops.h SO_NODE_RECUR2, csrc/k_recur2.hip): reduce-then-scan over
+    # Cumsum's tree on the affine maps of the state (y[n], y[n-1]); constants stream what `cumsum` streams (24 bytes a
+    # sample), a row per channel of a1 (A1, a resonator's 2 r cos(theta)) and of a2 (A2, -r^2) is read twice too: 56 bytes a
+    # sample; `resonator` adds the map that scales x, `sweep` an fc signal per channel: two delays (`sample_at`), the three
+    # maps that form a1, a2 and b, then the scan (STEPS=1 prints their times: what fusing the maps into the scan's loads
+    # would save); the yardsticks are the `cumsum`, `recur signal` and `copy (Until)` rows above
+    "recur2 const": lambda: so.Recur2(1.8, -0.9, X),
+    "recur2 signal": lambda: so.Recur2(A1(), A2(), X),
+    "resonator": lambda: so.Resonator(X, 1 * so.kHz, 50 * so.Hz),
+    "sweep": lambda: so.Sweep(X, so.Lowpass, FC(), 2.0),
     # `MovingMax(x, w)` / `MovingMin(x, w)` (include/sigops.h SO_NODE_MOVING, csrc/k_moving.hip): a window of 480 frames is the
     # one-launch form (a tile and its halo in LDS: 1 + 479 / 2048 reads and one write per sample), causal and centred; 48000
     # frames is the long form (block maxima, a sparse table, two blocks recomputed per tile: about three reads and one write);
@@ -136,6 +146,10 @@ cases = {
 }
 NOISE = lambda: so.Signal(so.randn, fs, rng=so.DeviceRNG(2024, 0))  # noqa: E731
 A = lambda: so.Signal((0.99 + 0.01 * torch.rand((nch, n), dtype=torch.float64, device="cuda")).t(), fs)  # noqa: E731
+R2 = lambda: 0.9 + 0.0999 * torch.rand((nch, n), dtype=torch.float64, device="cuda")  # noqa: E731
+A1 = lambda: so.Signal((2.0 * R2() * torch.cos(3.0 * torch.rand((nch, n), dtype=torch.float64, device="cuda"))).t(), fs)  # noqa: E731
+A2 = lambda: so.Signal((-R2() ** 2).t(), fs)  # noqa: E731
+FC = lambda: so.Signal((1000.0 + 800.0 * torch.rand((nch, n), dtype=torch.float64, device="cuda")).t(), fs)  # noqa: E731
 # environment of a case while its plan is created (the planner reads its knobs then)
 case_env = {
     "noise expr hipRTC (mono)": {"SIGOPS_RANDN_NOFILL": "1", "SIGOPS_RTC": "1"},
