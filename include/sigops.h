@@ -88,7 +88,8 @@ typedef enum so_kind {
     SO_NODE_MOVING = 15,  /* MovingMax / MovingMin: sliding-window extrema over [n - l0, n + l1] (no reference counterpart) */
     SO_NODE_MOVSUM = 16,  /* MovingSum / MovingMean / MovingRMS: sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart) */
     SO_NODE_RECUR = 17,   /* Recur / OnePole / Smooth / PeakDecay: the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart) */
-    SO_NODE_RECUR2 = 18   /* Recur2 / Resonator / Sweep: the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart) */
+    SO_NODE_RECUR2 = 18,  /* Recur2 / Resonator / Sweep: the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart) */
+    SO_NODE_MOVRANK = 19  /* MovingMedian / MovingQuantile: the sample of rank floor(d0 (m - 1)) of the window [n - l0, n + l1] (no reference counterpart) */
 } so_kind_t;
 
 /* FUNC opcodes: whitelisted `fn` of Signal(fn;ω,ϕ) (src/functions.jl:53-60) */
@@ -332,6 +333,17 @@ typedef enum so_rskind {
  *            feedback in a1, a2 and its feed-forward taps in b.  A child count other than 1 or 3, a non-finite d0 or d1 in
  *            the one-child form or a channel count of a1 or a2 that is neither 1 nor b's is SO_ERR_INVALID; an infinite b or
  *            a finite a1 or a2 shorter than b SO_ERR_LENGTH; an integer child SO_ERR_UNSUPPORTED.
+ *  MOVRANK   child 0 = x (Float32 / Float64, any length, infinite too)   l0 = back >= 0, l1 = ahead >= 0, the frames of
+ *            the window before and after frame n   d0 = q, a number in [0, 1]; every other field 0.
+ *            Per channel y[n] = a bit copy of the sample of rank floor(q (m - 1)), counted from 0, among the m samples
+ *            x[k], max(0, n - l0) <= k <= min(N - 1, n + l1), ordered -Inf < .. < -0.0 < +0.0 < .. < +Inf (the product ONE
+ *            Float64 multiplication, the floor exact); NaN if any of them is NaN ("Moving ranks";
+ *            tests/movingmedian_ref.py is the definition).  q = 0 is MOVING's minimum, q = 1 its maximum, bit for bit.  The
+ *            node has x's length, frame rate, channels AND sample type.  MovingQuantile(x, w, q, ahead=a): l0 = w - 1 - a,
+ *            l1 = a; MovingMedian: q = 0.5, the lower of the two middle samples of an even count.  Not exactly one child,
+ *            l0 < 0, l1 < 0 or a d0 that is NaN or outside [0, 1] is SO_ERR_INVALID; an integer child, or a window of
+ *            min(l0, frames read) + min(l1, frames read) > 1024 frames beside frame n (one form is built: the tile and its
+ *            halo in LDS), SO_ERR_UNSUPPORTED.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */

@@ -11,7 +11,7 @@ from .signals import (  # noqa: F401
     ArraySig, NumberSig, FuncSig, CutApply, PaddedSignal, AppendSignals, RampSignal,
     MapSignal, FilteredSignal, NormedSignal, FilterFn, RawFilterFn, RawFirFn, ResamplerFn, digitalfilter, ZeroPoleGain, SecondOrderSections, Biquad,
     PolynomialRatio, SampleAt, Delay, SampleAtSignal, Comb, Allpass, CombSignal, Cumsum, Integrate, CumsumSignal,
-    MovingMax, MovingMin, MovingSignal, MovingSum, MovingMean, MovingRMS, MovingSumSignal, Recur, OnePole, Smooth, PeakDecay, RecurSignal, Recur2, Resonator, Sweep, Recur2Signal,
+    MovingMax, MovingMin, MovingSignal, MovingSum, MovingMean, MovingRMS, MovingSumSignal, MovingMedian, MovingQuantile, MovingRankSignal, Recur, OnePole, Smooth, PeakDecay, RecurSignal, Recur2, Resonator, Sweep, Recur2Signal,
 )
 from numpy import sin, cos  # noqa: F401  (Signal(sin), Signal(cos))
 from .engine import sink, sink_into, stream, BlockStream, Plan, Array, process_sink_params, _eager, filt, filt_into  # noqa: F401

@@ -11,7 +11,7 @@ SO_F32, SO_F64, SO_I64 = 0, 1, 2
 SO_LEN_INF, SO_LEN_MISSING, SO_LEN_UNCHECKED = -1, -2, -3
 (NODE_ARRAY, NODE_CONST, NODE_FUNC, NODE_UNTIL, NODE_AFTER, NODE_PAD, NODE_APPEND, NODE_RAMP,
  NODE_MAP, NODE_FILT_SOS, NODE_RESAMPLE, NODE_NORMPOWER, NODE_SAMPLEAT, NODE_COMB, NODE_CUMSUM,
- NODE_MOVING, NODE_MOVSUM, NODE_RECUR, NODE_RECUR2) = range(19)
+ NODE_MOVING, NODE_MOVSUM, NODE_RECUR, NODE_RECUR2, NODE_MOVRANK) = range(20)
 FN = {"sin": 0, "cos": 1, "identity": 2, "randn": 3}
 SO_FN_RANDN = FN["randn"]
 RAMPFN = {"sinramp": 0, "identity": 1, "expr": 2}

@@ -103,6 +103,7 @@ static const char* stage_step_name(const Stage& S) {
     case ST_MOVSUM: return "k_movsum";
     case ST_RECUR: return "k_recur";
     case ST_RECUR2: return "k_recur2";
+    case ST_MOVRANK: return "k_movrank";
     default: return "k_sumsq";
     }
 }
@@ -135,6 +136,8 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
     case ST_CUMSUM:  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
         return S.need * (int64_t)N.nch * (2 * kid_esz(0) + 8);
     case ST_MOVING:  // the frames read where x lies (the long form's second and third reads and the tile halos left out), one sample of x's type written
+        return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
+    case ST_MOVRANK:  // the frames read where x lies (the tile halos left out), one sample of x's type written
         return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
     case ST_MOVSUM:  // the frames read where x lies (the long form's further reads, the tile halos and lead-ins left out), one Float64 written
         return (S.in_frames * kid_esz(0) + (S.need - S.base) * 8) * (int64_t)N.nch;
@@ -948,6 +951,30 @@ static int run_moving(Plan* P, const Step& s, void* outp, hipStream_t st) {
     return nl;
 }
 
+static int run_movrank(Plan* P, const Step& s, void* outp, hipStream_t st) {
+    const Stage& S = P->stages[s.idx];
+    const Node& N = P->nodes[S.node];
+    const View in = stage_in(P, S, N.nch, N.dtype), out = stage_out(P, s.idx, outp);
+    MovrankArgs a{};
+    a.x = in.d;
+    a.xcs = in.pitch;
+    a.xfs = S.x_fstride;
+    a.n_in = S.in_frames;
+    a.y = out.d;
+    a.ycs = out.pitch;
+    a.n_out = S.need - S.base;
+    a.off = S.base - S.in_base;
+    a.back = N.nd.l0;
+    a.ahead = N.nd.l1;
+    a.q = N.nd.d0;
+    a.nch = N.nch;
+    a.f32 = N.dtype == SO_F32;
+    const int nl = launch_movrank(a, st);
+    // (one workgroup per tile of kRankTile frames in grid.x, the channels in grid.y; process_moving refused a longer window)
+    if (nl < 0) fail(SO_ERR_UNSUPPORTED, "Movrank: more than 65535 channels, 2^31 tiles of 2048 frames and more, or a window of more than 1025 frames, are not lowered");
+    return nl;
+}
+
 static int run_movsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
     const Stage& S = P->stages[s.idx];
     const Node& N = P->nodes[S.node];
@@ -1326,6 +1353,7 @@ static int plan_execute_direct(Plan* P, void* outp, void* stream, std::string& e
                 case ST_CUMSUM: nl = run_cumsum(P, s, outp, st); break;
                 case ST_MOVING: nl = run_moving(P, s, outp, st); break;
                 case ST_MOVSUM: nl = run_movsum(P, s, outp, st); break;
+                case ST_MOVRANK: nl = run_movrank(P, s, outp, st); break;
                 case ST_RECUR: nl = run_recur(P, s, outp, st); break;
                 case ST_RECUR2: nl = run_recur2(P, s, outp, st); break;
                 case ST_SOS: nl = run_sos(P, s, outp, st); break;

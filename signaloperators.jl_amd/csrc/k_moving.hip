@@ -39,11 +39,12 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "kkey.h"
 
 namespace so {
 namespace {
 
-constexpr int kMovThreads = 256;
+constexpr int kMovThreads = kKeyThreads;  // (kkey.h: Key, to_key, from_key, pidx, load_key and load_image)
 constexpr int kMovSpan = kMovTile + kMovHalo;      // keys of the LDS image
 constexpr int kMovRun = kMovSpan / kMovThreads;    // neighbouring keys of the image a lane scans in registers
 constexpr int kMovImg = kMovSpan + kMovSpan / kMovRun;  // the image with one key of padding after every run
@@ -51,86 +52,9 @@ constexpr int kMovOut = kMovTile / kMovThreads;    // outputs of a lane
 static_assert((kMovTile & (kMovTile - 1)) == 0, "kMovTile is a power of two");
 static_assert(kMovHalo >= kMovTile - 1 && kMovSpan == 2 * kMovTile, "the long form images two blocks; a longer window never lies inside one");
 static_assert(kMovRun == 16 && (kMovImg + 2 * kMovThreads) * 8 <= 65536, "runs of 16 keys; static LDS of at most 64 KiB");
-// key i of the image lies at img[pidx(i)]: a lane reads its run with a stride of 17 keys from its neighbour's, which
-// spreads a half-wave's 8-byte (4-byte) accesses over all 64 (32) banks; consecutive keys stay consecutive but for the pad
-__device__ __forceinline__ int pidx(int i) { return i + (i >> 4); }
-
-template <typename F>
-struct Key;
-template <>
-struct Key<float> {
-    using K = int32_t;
-    using V = float4;
-    static constexpr int kBits = 32, kVec = 4;
-    static constexpr K kMin = INT32_MIN, kMax = INT32_MAX, kInf = 0x7f800000;
-};
-template <>
-struct Key<double> {
-    using K = int64_t;
-    using V = double2;
-    static constexpr int kBits = 64, kVec = 2;
-    static constexpr K kMin = INT64_MIN, kMax = INT64_MAX, kInf = 0x7ff0000000000000ll;
-};
-
-template <typename F, bool MIN>
-__device__ __forceinline__ typename Key<F>::K to_key(F v) {
-    using T = Key<F>;
-    typename T::K b;
-    __builtin_memcpy(&b, &v, sizeof b);
-    if (MIN) b ^= T::kMin;
-    const typename T::K k = b ^ ((b >> (T::kBits - 1)) & T::kMax);
-    return (b & T::kMax) > T::kInf ? T::kMax : k;
-}
-template <typename F, bool MIN>
-__device__ __forceinline__ F from_key(typename Key<F>::K k) {
-    using T = Key<F>;
-    typename T::K b = k ^ ((k >> (T::kBits - 1)) & T::kMax);
-    if (MIN) b ^= T::kMin;
-    F v;
-    __builtin_memcpy(&v, &b, sizeof v);
-    return v;
-}
 template <typename K>
 __device__ __forceinline__ K kmax(K a, K b) {
     return a > b ? a : b;
-}
-
-// one sample as a key: frame g of the row, the padding key outside [0, n_in); the index is clamped before the address
-template <typename F, bool MIN>
-__device__ __forceinline__ typename Key<F>::K load_key(const F* __restrict__ xr, int64_t xfs, int64_t n_in, int64_t g) {
-    const bool inside = g >= 0 && g < n_in;
-    const int64_t gc = g < 0 ? 0 : g < n_in ? g : n_in - 1;
-    const F v = xr[gc * xfs];
-    return inside ? to_key<F, MIN>(v) : Key<F>::kMin;
-}
-
-// a[pidx(i)] = key of frame g0 + i for i in [0, cnt); `vec`: the row base is 16-byte aligned and the frame stride is 1
-template <typename F, bool MIN>
-__device__ __forceinline__ void load_image(typename Key<F>::K* a, const F* __restrict__ xr, int64_t xfs, int64_t n_in, int64_t g0, int cnt, bool vec) {
-    using T = Key<F>;
-    const int tid = threadIdx.x;
-    if (!vec) {
-        for (int i = tid; i < cnt; i += kMovThreads) a[pidx(i)] = load_key<F, MIN>(xr, xfs, n_in, g0 + i);
-        return;
-    }
-    constexpr int VE = T::kVec;
-    const int64_t ga = g0 - (((g0 % VE) + VE) % VE);  // the aligned group g0 lies in (g0 may be negative)
-    const int ngroups = (int)((g0 + cnt - ga + VE - 1) / VE);
-    for (int q = tid; q < ngroups; q += kMovThreads) {
-        const int64_t gs = ga + (int64_t)q * VE;
-        const int i0 = (int)(gs - g0);
-        if (gs >= 0 && gs + VE <= n_in) {
-            const typename T::V v = *reinterpret_cast<const typename T::V*>(xr + gs);
-            const F* e = reinterpret_cast<const F*>(&v);
-#pragma unroll
-            for (int k = 0; k < VE; ++k)
-                if (i0 + k >= 0 && i0 + k < cnt) a[pidx(i0 + k)] = to_key<F, MIN>(e[k]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < VE; ++k)
-                if (i0 + k >= 0 && i0 + k < cnt) a[pidx(i0 + k)] = load_key<F, MIN>(xr, 1, n_in, gs + k);
-        }
-    }
 }
 
 // The lane's run of the image, img[pidx(16 tid + e)], into registers and back.

@@ -273,4 +273,26 @@ constexpr int64_t movsum_scratch(int64_t abs0, int64_t n_in, int64_t back, int64
     return movsum_is_long(back, ahead) ? (int64_t)(movsum_levels(abs0, n_in, back, ahead) + 1) * movsum_blocks(abs0, n_in) : 0;
 }
 int launch_movsum(const MovsumArgs& a, hipStream_t st);
+// MovingMedian / MovingQuantile (k_movrank.hip, -ffp-contract=off): output j in [0, n_out) of a channel is a bit copy of the
+// sample of rank floor(q (m - 1)), counted from 0, among the m input frames [j + off - back, j + off + ahead] clipped to
+// [0, n_in), under the order -Inf < .. < -0.0 < +0.0 < .. < +Inf (k_moving.hip's integer key); NaN if any of them is NaN; the
+// result has the input's type (DESIGN.md "Moving ranks"; tests/movingmedian_ref.py).  ONE form, one launch (k_movrank): a tile
+// of kRankTile outputs and its halo in LDS, every element of the image counts its own rank in the first window that holds
+// it and updates it from window to window; the element whose rank is the target writes its index.  Takes
+// min(back, n_in) + min(ahead, n_in) <= kRankHalo.  No workgroup waits for another, no atomics.  Strides in elements.
+// Returns the number of launches, -1 when the shape cannot be launched (a longer window among them).
+constexpr int kRankTile = 2048;  // T: output frames of a workgroup
+constexpr int kRankHalo = 1024;  // H: W - 1 <= H; the image holds T + 3 H keys (the tile, its halo and a guard of W - 1 keys on either side)
+struct MovrankArgs {
+    const void* x;  // input frame i, channel c at x[i * xfs + c * xcs], i in [0, n_in)
+    int64_t xfs, xcs, n_in;
+    void* y;        // y[j + c * ycs], j in [0, n_out), of the input's type
+    int64_t ycs, n_out;
+    int64_t off;    // the input frame output 0 is centred on (0 <= off, off + n_out <= n_in)
+    int64_t back, ahead;
+    double q;       // in [0, 1]
+    int32_t nch, f32;
+};
+constexpr bool movrank_fits(int64_t n_in, int64_t back, int64_t ahead) { return moving_clamp(back, n_in) + moving_clamp(ahead, n_in) <= kRankHalo; }
+int launch_movrank(const MovrankArgs& a, hipStream_t st);
 }  // namespace so

@@ -107,7 +107,7 @@ struct Buf {
     int64_t frame0 = 0;     // stage buffers: node frame stored at position 0 (Stage::base)
 };
 
-enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM, ST_RECUR, ST_RECUR2 };
+enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM, ST_RECUR, ST_RECUR2, ST_MOVRANK };
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)

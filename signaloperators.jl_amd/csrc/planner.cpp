@@ -316,6 +316,20 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             N.dtype = SO_F64;
             break;
         }
+        case SO_NODE_MOVRANK: {  // the sample of rank floor(d0 (m - 1)) of the window [n - l0, n + l1] (no reference counterpart; DESIGN.md "Moving ranks")
+            const std::string where = "node " + std::to_string(i) + ": Movrank ";
+            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            Node& x = kid(0);
+            if (nd.l0 < 0 || nd.l1 < 0)
+                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            if (!(nd.d0 >= 0.0 && nd.d0 <= 1.0)) fail(SO_ERR_INVALID, where + "needs a quantile q in [0, 1], not " + std::to_string(nd.d0));
+            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            // (one form is built: process_moving refuses a window that does not fit it, once it knows the frames it reads)
+            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
+            N.nch = x.nch;
+            N.dtype = x.dtype;
+            break;
+        }
         case SO_NODE_RECUR: {  // the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart; DESIGN.md "Recur")
             const std::string where = "node " + std::to_string(i) + ": Recur ";
             if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is affine (0) or max-decay (1), not " + std::to_string(nd.i0));
@@ -1003,7 +1017,8 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         return out;
     }
     case SO_NODE_MOVING:
-    case SO_NODE_MOVSUM: {
+    case SO_NODE_MOVSUM:
+    case SO_NODE_MOVRANK: {
         // a stage: the frames anybody reads, computed from those frames of the child plus `back` before and `ahead` after;
         // the result is a plain buffer for whoever consumes it (process_moving, stages.cpp)
         if (dry) {
@@ -1012,7 +1027,7 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             out.push_back({r, mk_const(0.0, N.dtype)});
             return out;
         }
-        const int sid = stage_for(ni, N.nd.kind == SO_NODE_MOVSUM ? ST_MOVSUM : ST_MOVING);
+        const int sid = stage_for(ni, N.nd.kind == SO_NODE_MOVSUM ? ST_MOVSUM : N.nd.kind == SO_NODE_MOVRANK ? ST_MOVRANK : ST_MOVING);
         use_stage(stages[sid], r, m);
         if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
         Expr e;

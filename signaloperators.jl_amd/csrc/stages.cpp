@@ -4,7 +4,7 @@
 //
 // Map (routine -- what it decides -- the Stage fields it writes):
 //   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
-//                            process_sample_at, process_comb, process_moving (Moving and Movsum), process_recur, process_recur2 (input: stage_input, second_input)
+//                            process_sample_at, process_comb, process_moving (Moving, Movsum and Movrank), process_recur, process_recur2 (input: stage_input, second_input)
 //   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
 //                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
 //     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
@@ -670,6 +670,8 @@ void Plan::process_recur2(int sid) {
 // which in_base hands to the kernel, so a window computes the whole result's bits.  The long form's block totals and
 // dyadic nodes cover the aligned blocks that hold an input frame; an entry whose block lies partly outside the input is
 // never part of a cover, which holds whole blocks between a window's first and last frame (k_movsum.hip).
+// MovingMedian / MovingQuantile (ST_MOVRANK) take the same span and own nothing besides.  ONE form is built (k_movrank.hip:
+// the tile and its halo in LDS), so a window that reaches over more than kRankHalo of the frames the stage reads is refused.
 void Plan::process_moving(int sid) {
     const int ni = stages[sid].node;
     const int xk = nodes[ni].kids[0];
@@ -681,12 +683,23 @@ void Plan::process_moving(int sid) {
     const int64_t c0 = base > back ? base - back : 0;
     int64_t c1 = ahead < BIG - need ? need + ahead : BIG;
     if (!isinf_(nodes[xk].len)) c1 = std::min(c1, nodes[xk].len.n);
-    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": " + (stages[sid].kind == ST_MOVSUM ? "Movsum" : "Moving") + " looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
+    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": " + (stages[sid].kind == ST_MOVSUM ? "Movsum" : stages[sid].kind == ST_MOVRANK ? "Movrank" : "Moving") + " looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
+    const bool rank = stages[sid].kind == ST_MOVRANK;
+    if (rank && !movrank_fits(c1 - c0, back, ahead))
+        fail(SO_ERR_UNSUPPORTED, "node " + std::to_string(ni) + ": Movrank takes a window of at most " + std::to_string(kRankHalo + 1) + " frames (" + std::to_string(moving_clamp(back, c1 - c0)) + " before and " +
+                                     std::to_string(moving_clamp(ahead, c1 - c0)) + " after frame n asked, of the " + std::to_string(c1 - c0) + " frames read): a longer one is not built");
     stages[sid].base = base;
     stages[sid].in_base = c0;
     bufs[stages[sid].out_buf].frame0 = base;
     if (c0 > 0) check_frames(xk, c0);
     stage_input(sid, lower(xk, Rect{0, c1 - c0, 0, nch}, Map{1, c0, 1, 0}), c1 - c0, nch, nodes[xk].dtype);
+    if (rank) {
+        if (std::getenv("SIGOPS_DEBUG_PLAN"))
+            std::fprintf(stderr, "[sigops] Movrank stage %d: rank floor(%.17g (m - 1)) over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, x %s\n", sid, nodes[ni].nd.d0, (long long)back,
+                         (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
+                         stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+        return;
+    }
     const bool sum = stages[sid].kind == ST_MOVSUM;
     const int64_t entries = sum ? movsum_scratch(c0, c1 - c0, back, ahead) : moving_scratch(c1 - c0, back, ahead);
     if (entries > 0) {
@@ -712,7 +725,8 @@ void Plan::process_moving(int sid) {
 void Plan::process_stage(int sid) {
     switch (stages[sid].kind) {
     case ST_MOVING:
-    case ST_MOVSUM: return process_moving(sid);
+    case ST_MOVSUM:
+    case ST_MOVRANK: return process_moving(sid);
     case ST_SAMPLEAT: return process_sample_at(sid);
     case ST_COMB:
     case ST_CUMSUM: return process_comb(sid);

@@ -448,6 +448,9 @@ def _streamable(x):
     if isinstance(x, S.Recur2Signal):
         S.error("BlockStream: Recur2 / Resonator / Sweep would have to carry its last two values (and its place in the tree of "
                 "the scan) from one push to the next, and that is not built; not streamable")
+    if isinstance(x, S.MovingRankSignal):
+        S.error("BlockStream: MovingMedian / MovingQuantile would have to keep the `back` input frames of its window from one "
+                "push to the next and hold `ahead` output frames back, and that is not built; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -270,6 +270,9 @@ def _demand(x, n, out, skip=0):
     elif isinstance(x, S.MovingSumSignal):
         # as for MovingSignal: the window of the last frame reaches `ahead` frames further
         _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
+    elif isinstance(x, S.MovingRankSignal):
+        # as for MovingSignal: the window of the last frame reaches `ahead` frames further
+        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -571,6 +574,11 @@ def lower(x, nframes_out=None, rng=None):
             c = rec(s.signal)
             r = common(s, K.NODE_MOVSUM)
             r.update(l0=s.back, l1=s.ahead, i0=s.op, children=(c,))
+            idx = lw.add(**r)
+        elif isinstance(s, S.MovingRankSignal):
+            c = rec(s.signal)
+            r = common(s, K.NODE_MOVRANK)
+            r.update(l0=s.back, l1=s.ahead, d0=s.q, children=(c,))
             idx = lw.add(**r)
         elif isinstance(s, S.CumsumSignal):
             c = rec(s.signal)

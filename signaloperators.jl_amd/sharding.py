@@ -69,12 +69,22 @@ def _refuse_moving_sum(x, what):
         _refuse_moving_sum(c, what)
 
 
+def _refuse_moving_rank(x, what):
+    """a tree with a MovingMedian / MovingQuantile node is not sharded: a rank's window reaches into its neighbours' frames"""
+    if isinstance(x, S.MovingRankSignal):
+        raise S.ErrorException(f"{what}: sharding a tree that contains MovingMedian / MovingQuantile over several GPUs is not built: a "
+                               "rank would need `back` frames of the rank before it and `ahead` of the one after (a halo exchange)")
+    for c in getattr(x, "children", ()) or ():
+        _refuse_moving_rank(c, what)
+
+
 def shard_append(x, rank, world):
     """-> (sub-signal for this rank or None, first output frame, number of frames)"""
     _refuse_sample_at(x, "shard_append")
     _refuse_from_frame_0(x, "shard_append")
     _refuse_moving(x, "shard_append")
     _refuse_moving_sum(x, "shard_append")
+    _refuse_moving_rank(x, "shard_append")
     if not isinstance(x, S.AppendSignals):
         raise S.ErrorException("shard_append needs an Append(...) root")
     kids = x.signals
@@ -100,6 +110,7 @@ def shard_time(x, rank, world, align=1):
     _refuse_from_frame_0(x, "shard_time")
     _refuse_moving(x, "shard_time")
     _refuse_moving_sum(x, "shard_time")
+    _refuse_moving_rank(x, "shard_time")
     n = S.nframes(x)
     if n is None or S.isknowninf(n):
         raise S.ErrorException("shard_time needs a signal of known, finite length")
@@ -120,6 +131,7 @@ def shard_channels(x, rank, world):
     _refuse_from_frame_0(x, "shard_channels")
     _refuse_moving(x, "shard_channels")
     _refuse_moving_sum(x, "shard_channels")
+    _refuse_moving_rank(x, "shard_channels")
     c0, c1 = block_range(x.nch, rank, world)
     if c1 <= c0:
         return None, c0, c1

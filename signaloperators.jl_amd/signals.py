@@ -629,6 +629,30 @@ class MovingSumSignal(AbstractSignal):
         return self.signal.duration()
 
 
+class MovingRankSignal(AbstractSignal):
+    """`MovingMedian(x, w)` / `MovingQuantile(x, w, q)`: per channel the sample of rank `floor(q (m - 1))` among the `m` samples
+    of `x` over the frames `[n - back, n + ahead]`, clipped to the signal (no reference counterpart; include/sigops.h
+    SO_NODE_MOVRANK, DESIGN.md "Moving ranks").  It has the length, frame rate, channels and sample type of `x`."""
+
+    evaltrait = "computed"
+
+    def __init__(self, x, back, ahead, q):
+        self.signal = x
+        self.children = (x,)
+        self.back = int(back)
+        self.ahead = int(ahead)
+        self.q = float(q)
+        self.fs = x.fs
+        self.nch = x.nch
+        self.dtype = x.dtype
+
+    def nframes_helper(self):
+        return self.signal.nframes_helper()
+
+    def duration(self):
+        return self.signal.duration()
+
+
 class RecurSignal(AbstractSignal):
     """`Recur(a, b)` / `OnePole` / `Smooth` / `PeakDecay`: per channel the first-order scan `y[n] = J(a[n], y[n-1], b[n])`,
     `y[0] = b[0]`, over one fixed tree (no reference counterpart; include/sigops.h SO_NODE_RECUR, DESIGN.md "Recur").
@@ -1066,6 +1090,10 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known:
             return _resample(x, fs, bs)
         return MovingSumSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.op)
+    if isinstance(x, MovingRankSignal):  # the same two rules
+        if known:
+            return _resample(x, fs, bs)
+        return MovingRankSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.q)
     if isinstance(x, RecurSignal):  # Comb's two rules: the recurrence runs over frames, whatever rate they have
         if known:
             return _resample(x, fs, bs)
@@ -1879,6 +1907,68 @@ MovingRMS.__doc__ = """`MovingRMS(x, w, *, ahead=0, center=False)`, curried `x |
 window: the `MovingSum` tree over `x[k] * x[k]` (the product formed in Float64, exact for a Float32 `x`), divided by the
 frames of the clipped window, and the square root of that, each rounded once.  Window, units, result type, `stream`,
 `BlockStream` and shards as for `MovingSum`."""
+
+
+# --------------------------------------------------------------------------
+# MovingMedian / MovingQuantile: sliding rank filters (no reference counterpart)
+MOVING_RANK_HALO = 1024  # csrc/kernels.h kRankHalo: the one form that is built takes a window of at most this many frames + 1
+
+
+def _MovingRank(what, x, w, q, ahead, center):
+    m = _Moving(what, False, x, w, ahead, center)  # (the window's rules and refusals, under this construct's name)
+    if not _real_number(q) or not math.isfinite(q) or not 0.0 <= q <= 1.0:
+        error(f"{what}: the quantile q must be a finite real number in [0, 1], not {q!r}")
+    n = m.signal.nframes_helper()
+    back, ahead = m.back, m.ahead
+    if isinstance(n, (int, np.integer)):  # a known, finite length: a window longer than the signal is the signal
+        back, ahead = min(back, int(n)), min(ahead, int(n))
+    if back + ahead > MOVING_RANK_HALO:
+        error(f"{what}: a window of {m.back + m.ahead + 1} frames is longer than the {MOVING_RANK_HALO + 1} frames that are built "
+              "(one form: a tile and its halo in the device's local memory); a longer one is refused, not computed on the host")
+    return MovingRankSignal(m.signal, m.back, m.ahead, q)
+
+
+def MovingQuantile(*args, ahead=None, center=False):
+    """`MovingQuantile(x, w, q, *, ahead=0, center=False)`, curried `x | MovingQuantile(w, q, ahead=...)`: the sliding-window
+    quantile, a rank filter.  With `back = w - 1 - ahead`, frame n of a channel looks at the `m` samples `x[k]`,
+    `max(0, n - back) <= k <= min(N - 1, n + ahead)` -- the window is clipped to the signal, never padded -- ordered
+    `-Inf < ... < -0.0 < +0.0 < ... < +Inf` (the two zeros are distinct), and is a bit copy of the one of rank
+    `floor(q * (m - 1))`, counted from 0: always a sample of the window, never an interpolation or an average.  The product is
+    one Float64 multiplication and the floor is exact.  `q` is a finite number in [0, 1]: `q = 0` is `MovingMin` and `q = 1`
+    is `MovingMax`, bit for bit; a window of one frame is `x` itself.  The result has the length, rate, channels and sample
+    type of `x` (Float32 stays Float32: nothing is rounded).  A NaN anywhere in the clipped window makes the frame NaN (its
+    payload is unspecified).  `w`, `ahead` and `center` as for `MovingMax`: whole frames, a `frames` quantity or a time
+    converted with the rate of `x`; `0 <= ahead <= w - 1`; `center=True` is `ahead = (w - 1) // 2`; the default is the
+    causal window `[n - w + 1, n]`.  A selection rounds nothing, so windows, `stream` blocks and the whole sink agree bit for
+    bit where `x` does.  The dependence is local: a window or a `stream` block computes its own frames from its own range
+    of `x` plus `back` frames before and `ahead` after, and an `x` of infinite length is accepted.  One form is built, a
+    window of at most 1025 frames (counted after `back` and `ahead` are clipped to the length of `x`): a longer one is
+    refused here and by the planner, never computed on the host.  `BlockStream` and multi-GPU shards refuse the node."""
+    what = "MovingQuantile"
+    if len(args) == 2:
+        w, q = args
+        return Curried(lambda x: _MovingRank(what, x, w, q, ahead, center))
+    if len(args) != 3:
+        error(f"{what}(x, w, q) expected")
+    return _MovingRank(what, args[0], args[1], args[2], ahead, center)
+
+
+def MovingMedian(*args, ahead=None, center=False):
+    """`MovingMedian(x, w, *, ahead=0, center=False)`, curried `x | MovingMedian(w, center=True)`: the sliding-window median,
+    `MovingQuantile` with `q = 0.5`: of the `m` samples of the clipped window the one of rank `(m - 1) // 2` -- the middle
+    sample of an odd count and the LOWER of the two middle samples of an even count.  It is always a sample of the window,
+    never an average: where `m` is even it differs from `np.median`, which averages the two.  With an odd `w` that happens
+    only at the edges of the signal, where the window is clipped to an even count.  A declicker is
+    `x - MovingMedian(x, 5, center=True)` and a threshold; the Hampel identifier takes
+    `MovingMedian(|x - MovingMedian(x, w)|, w)`.  Order, zeros, NaN, window, units, result type, the limit of 1025 frames,
+    `stream`, `BlockStream` and shards as for `MovingQuantile`."""
+    what = "MovingMedian"
+    if len(args) == 1:
+        w = args[0]
+        return Curried(lambda x: _MovingRank(what, x, w, 0.5, ahead, center))
+    if len(args) != 2:
+        error(f"{what}(x, w) expected")
+    return _MovingRank(what, args[0], args[1], 0.5, ahead, center)
 
 
 # --------------------------------------------------------------------------

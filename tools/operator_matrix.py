@@ -84,6 +84,16 @@ cases = {
     "movingrms 480": lambda: so.MovingRMS(X, 480),
     "movingmean 480 ahead": lambda: so.MovingMean(X, 480, center=True),
     "movingsum 48000": lambda: so.MovingSum(X, 48000),
+    # `MovingMedian(x, w)` / `MovingQuantile(x, w, q)` (include/sigops.h SO_NODE_MOVRANK, csrc/k_movrank.hip): one form, a tile of
+    # 2048 frames and its halo in LDS, every element counting its rank from window to window: about 3 (W - 1) LDS reads a
+    # sample times (2048 + W - 1) / 2048, so 5 frames reads and writes each sample once like `movingmax 480`, and the time
+    # grows with the window from there: 101, 480 and 1025 frames (the longest that is built) are bound by the LDS reads; the
+    # Float32 row moves half the bytes; the yardsticks are `copy (Until)` and `movingmax 480`
+    "movingmedian 5 center": lambda: so.MovingMedian(X, 5, center=True),
+    "movingmedian 101 center": lambda: so.MovingMedian(X, 101, center=True),
+    "movingquantile 480 0.1": lambda: so.MovingQuantile(X, 480, 0.1),
+    "movingmedian 1025": lambda: so.MovingMedian(X, 1025),
+    "movingmedian 5 f32": lambda: so.MovingMedian(so.Signal(x.t().to(torch.float32).t(), fs), 5),
     "Amplify(const)": lambda: X | so.Amplify(0.5),
     "Amplify(sin)": lambda: X | so.Amplify(tone) | so.Until(n * so.frames),
     "Mix(x, y)": lambda: so.Mix(X, Y),
