@@ -1127,6 +1127,8 @@ static int run_sos(Plan* P, const Step& s, void* outp, hipStream_t st) {
         launch_sos_onepass(x, out.d, o, S.groups[gi], (const double*)P->bufs[S.one_tabs_buf].d + S.one_tabs_off[gi],
                            (int*)sb.d, (double*)vb.d, N.dtype, st);
         nl += 1;
+        // (behind a NaN the reference stays NaN, the look-back recovers after kt tiles: the tiles' published states tell)
+        if (!std::getenv("SIGOPS_SOS_NOPOISON")) nl += launch_sos_poison_onepass(out.d, (const double*)vb.d, S.groups[gi].nsec, o, N.dtype, st);
     }
     if (S.pre_stage >= 0) {
         const Stage& S3 = P->stages[S.pre_stage];

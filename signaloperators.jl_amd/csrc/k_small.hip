@@ -49,4 +49,38 @@ int launch_sos_poison(void* y, const SosGeom& g, hipStream_t st) {
     return 1;
 }
 
+// The same behind the single-pass form (k_sos_onepass), whose look-back reaches kt tiles: without this a channel came
+// back finite kt tiles behind a NaN (found by tests/test_gpu_forms_nonfinite.py, rung I3).  It needs no words of its own:
+// a tile's published zero-state end state (SosOne: vpub, all of them written once the filter's launch is done) is
+// non-finite exactly when the tile holds a non-finite sample or overflowed -- the per-sample recurrence never recovers,
+// 0 * NaN included.  Every workgroup finds its channel's first such tile; NaN goes over everything behind that tile (the
+// tile itself is the recurrence's own: its scan covers all 64 lanes).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_sos_poison_onepass(T* __restrict__ y, const double* __restrict__ vpub, int D, SosOne g) {
+    const int ch = blockIdx.y;
+    __shared__ int s_first;
+    if (threadIdx.x == 0) s_first = g.ntiles;
+    __syncthreads();
+    for (int t = threadIdx.x; t < g.ntiles - 1; t += kBlock) {  // (nothing is behind the last tile)
+        const double* vp = vpub + ((int64_t)t * g.nch + ch) * D;
+        bool bad = false;
+        for (int i = 0; i < D; ++i) bad |= !isfinite(vp[i]);
+        if (bad) atomicMin(&s_first, t);
+    }
+    __syncthreads();
+    const int kb = s_first;
+    if (kb >= g.ntiles - 1) return;  // (the usual case)
+    const T nan = (T)__longlong_as_double(0x7ff8000000000000ll);
+    for (int64_t f = (int64_t)(kb + 1) * (64 * kSosLc) + (int64_t)blockIdx.x * kBlock + threadIdx.x; f < g.n; f += (int64_t)gridDim.x * kBlock)
+        y[(int64_t)ch * g.out_pitch + f] = nan;
+}
+
+int launch_sos_poison_onepass(void* y, const double* vpub, int nsec, const SosOne& g, int dtype, hipStream_t st) {
+    if (g.ntiles <= 1 || g.n <= 0) return 0;
+    const dim3 grid(8, (unsigned)g.nch);
+    if (dtype == SO_F32) hipLaunchKernelGGL((k_sos_poison_onepass<float>), grid, dim3(kBlock), 0, st, (float*)y, vpub, 2 * nsec, g);
+    else hipLaunchKernelGGL((k_sos_poison_onepass<double>), grid, dim3(kBlock), 0, st, (double*)y, vpub, 2 * nsec, g);
+    return 1;
+}
+
 }  // namespace so

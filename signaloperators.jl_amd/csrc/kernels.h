@@ -64,6 +64,8 @@ int launch_sos_prestate(const void* x, void* y, const double* vper, int64_t nper
 // single-pass SOS IIR (the caller zeroes `sync` on the stream before every launch)
 void launch_sos_onepass(const void* x, void* y, const SosOne& g, const SosCoefs& cf, const double* tabs,
                         int* sync, double* vpub, int dtype, hipStream_t st);
+// NaN behind the first tile of a channel whose published end state (vpub, after launch_sos_onepass) is non-finite
+int launch_sos_poison_onepass(void* y, const double* vpub, int nsec, const SosOne& g, int dtype, hipStream_t st);
 void launch_resample(const void* x, void* y, const double* pfb, const double* dpfb,
                      const RsGeom& g, hipStream_t st);
 // pfbt / dpfbt: polyphase tables transposed to [taps][nphi]

@@ -247,7 +247,11 @@ def stream(x, blocksize, to=None, *, device=0):
     Until(blocksize frames), to)`, which is what the reference's own sink loop -- `sink!(buffer, x,
     block)` with the block it returned last time, src/sink.jl:227-241 -- writes into successive
     buffers.  Results do not depend on `blocksize` (the reference's `blocksize` contract,
-    src/filters.jl:3).  Stateful stages do not start over for every block: a filter starts a decay
+    src/filters.jl:3) -- with one exception: a non-finite sample makes the rest of a filtered channel
+    non-finite in the reference, and a block whose filter starts from rest behind that sample (warm
+    start, below) does not see it: the block is what the reference gives with that sample replaced by
+    0.0.  `SIGOPS_NO_WARM_START=1` filters every block from frame 0 and gives the reference's set
+    ("The reference's set of non-finite outputs").  Stateful stages do not start over for every block: a filter starts a decay
     time before the block and a resampler a few periods before it (warm start), and the
     resampler's DSP.jl phase accumulator resumes from the previous block's end (a rate without a period -- non-integer
     frame rates, x pi -- starts exactly at the block: its stage stages taps + 2 input frames before the block's first

@@ -279,3 +279,109 @@ class ResultView:
             self.res.fill_(float("nan"))
         else:
             self.res[...] = np.nan
+
+
+# ---- the ladders on spoiled inputs (tests/test_forms_nonfinite_host.py, tests/test_gpu_forms_nonfinite.py) ------------------
+# The same seeds and the same `ladder_noise` as above, with a few samples replaced by NaN or +-Inf: a plant is (channel, input
+# frame, value).  No large finite values: whether those overflow depends on the order of operations.  Everything above this
+# line produces what it produced before these names were added (tools/plan_fingerprint.py compares builds with it).
+NAN, INF = np.nan, np.inf
+WINDOW_IN = 40000                # input frames of a window case
+FW_AFTER, FW_UNTIL = 30000, 5001  # the filter window cases: After(30000) | Until(5001)
+FW_CASES = [(f, 5, F64) for f in FILTERS]
+
+
+def spoiled(a, plants):
+    """a copy of `a` (frames x channels) with every plant (channel, frame, value) written into it"""
+    b = a.copy(order="F")
+    for ch, frame, v in plants:
+        b[frame, ch] = v
+    return b
+
+
+def resampler_plants(case):
+    fi, fo, nout, nch, dt, window = case
+    if window:  # far before the window / just before it / inside it / beyond its reach
+        plants = [(0, 100, NAN), (3 if nch > 3 else nch - 2, 11330, INF), (5 if nch >= 6 else nch - 1, 15000, NAN)]
+        return plants + ([(nch - 1, 30000, NAN)] if nch == 8 else [])
+    return edge_plants(NFRAMES, nch)
+
+
+def edge_plants(n, nch):
+    """the first frame of channel 0, the middle and the last frame of the last channel, and one more channel where there are four"""
+    return [(0, 0, NAN), (nch - 1, 10007, INF), (nch - 1, n - 1, NAN)] + ([(3, 4999, -INF)] if nch >= 4 else [])
+
+
+def resampler_tree_spoiled(case):
+    """`resampler_tree(case)` on a spoiled copy of its noise: (tree, plants)"""
+    fi, fo, nout, nch, dt, window = case
+    plants = resampler_plants(case)
+    x = so.Signal(spoiled(ladder_noise(1000 + nch, WINDOW_IN if window else NFRAMES, nch, dt), plants), fi * so.Hz) | so.ToFramerate(fo * so.Hz)
+    if window:
+        x = x | so.After(12345 * so.frames) | so.Until(9001 * so.frames)
+    return x, plants
+
+
+def arbitrary_tree_spoiled(case):
+    """`arbitrary_tree(case)` on a spoiled copy of its noise: (tree, plants)"""
+    fi, fo, nout, nch, dt = case
+    plants = edge_plants(40000, nch)
+    return so.Signal(spoiled(ladder_noise(2000 + nch, 40000, nch, dt), plants), fi * so.Hz) | so.ToFramerate(fo * so.Hz), plants
+
+
+def filter_plants(case):
+    """frames 4095 and 4096 are a chunk's end and start for the chunk lengths 32, 64, 512 and 4096"""
+    f, nch, dt = case
+    return {5: [(0, 0, NAN), (1, 4095, INF), (3, 4096, -INF), (4, NFRAMES - 1, NAN)],
+            4: [(0, 4095, NAN), (2, 4096, INF), (3, NFRAMES - 1, NAN)],
+            1: [(0, 12319, NAN)]}[nch]
+
+
+def filter_data_spoiled(case):
+    f, nch, dt = case
+    return spoiled(ladder_noise(3000 + nch, NFRAMES, nch, dt), filter_plants(case))
+
+
+def filter_tree_spoiled(case):
+    """`filter_tree(case)` on a spoiled copy of its noise: (tree, plants)"""
+    return so.Signal(filter_data_spoiled(case), 44.1 * so.kHz) | FILTERS[case[0]][0](), filter_plants(case)
+
+
+FW_PLANTS = [(0, 100, NAN), (1, 29990, INF), (3, 32000, NAN)]  # a decay time and more before the window / just before it / inside it
+
+
+def filter_window_data(case, plants=FW_PLANTS):
+    f, nch, dt = case
+    return spoiled(ladder_noise(4000 + nch, WINDOW_IN, nch, dt), plants)
+
+
+def filter_window_tree(case, plants=FW_PLANTS, window=True):
+    """a filter of the ladder on 40 000 frames behind After(30000) | Until(5001) (window=False: the whole filtered signal):
+    (tree, plants)"""
+    x = so.Signal(filter_window_data(case, plants), 44.1 * so.kHz) | FILTERS[case[0]][0]()
+    if window:
+        x = x | so.After(FW_AFTER * so.frames) | so.Until(FW_UNTIL * so.frames)
+    return x, plants
+
+
+OVERFLOW_CASE = (8000, 16000, 40002, 8, F64, False)  # rung R0: k_resample_periodic, two outputs per period
+
+
+def overflow_tree(half=False):
+    """the 8 -> 16 kHz case with a NaN at every fourth input frame of channel 5 (half: of its first half only): more (tile, group)
+    entries than the periodic resampler's list holds (csrc/sigops_internal.h kRsNfCap).  (tree, plants)"""
+    plants = [(5, k, NAN) for k in range(0, NFRAMES // 2 if half else NFRAMES, 4)]
+    return so.Signal(spoiled(ladder_noise(1000 + 8, NFRAMES, 8, F64), plants), 8000 * so.Hz) | so.ToFramerate(16000 * so.Hz), plants
+
+
+def rs_nf_cap():
+    """kRsNfCap as the kernels have it"""
+    import re
+
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "signaloperators.jl_amd", "csrc", "sigops_internal.h")).read()
+    return int(re.search(r"constexpr uint32_t kRsNfCap = (\d+);", text).group(1))
+
+
+def forgotten(plants):
+    """the plants with every one at frame 100 replaced by 0.0: what a filter started from rest behind that frame sees of it"""
+    return [(ch, frame, 0.0 if frame == 100 else v) for ch, frame, v in plants]
