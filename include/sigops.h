@@ -266,6 +266,19 @@ typedef enum so_rskind {
  *            channels, and is Float64: frame n, channel c is NumPy's np.interp(p, arange(N), x[:, c], left,
  *            right) -- np.interp(p, arange(N), x[:, c], period=N) under wrap -- bit for bit (DESIGN.md,
  *            "SampleAt").  One child or three, or a pos of another channel count, is SO_ERR_INVALID.
+ *            i1 = the interpolation: 0 linear (the above; i2, p0, s0, d2 are 0), 1 cubic (Catmull-Rom over
+ *            x[j-1 .. j+2], j = floor(p); i2, p0, s0, d2 are 0), 2 windowed sinc: i2 = K, the taps, even, 4 .. 64;
+ *            p0 = const double[(2 * 512 + 1) * K], s0 = that count: the 513 rows h[phase][tap] of the 512-phase
+ *            tap table followed by the 512 rows dh[phase] = h[phase + 1] - h[phase], every entry finite; the
+ *            plan copies them to the device once (counted in scratch_bytes).  d2 = cutoff, the pass-band edge the
+ *            table was designed for as a fraction of the table's Nyquist (printed by SIGOPS_DEBUG_PLAN, never
+ *            read otherwise: the table is the filter).  With t = p - j and u = 512 t: phase = floor(u),
+ *            alpha = u - phase, tap k = h[phase][k] + alpha * dh[phase][k], and frame n is the sum over k = 0 ..
+ *            K-1, left to right from the first product, of tap k * x[j - K/2 + 1 + k].  Both kinds clamp the
+ *            index into [0, N) (modulo N under wrap), give left / right / NaN where linear does, and round every
+ *            operation on its own (tests/sampleat_interp_ref.py is the definition; DESIGN.md "SampleAt").  An
+ *            unknown i1, an odd or out-of-range i2, a p0 / s0 that does not match, a non-finite table entry, or
+ *            i2 / p0 / s0 set for another kind is SO_ERR_INVALID.
  *  COMB      child 0 = x (finite, Float32 / Float64)   l0 = D >= 1, the delay in frames   d0=b0 d1=bD d2=a (finite).
  *            Per channel, with xd = x[n-D] and yd = y[n-D] where n >= D and +0.0 before that,
  *                y[n] = (b0 * x[n] + bD * xd) + a * yd

@@ -96,7 +96,7 @@ static const char* stage_step_name(const Stage& S) {
         if (S.rows) return "k_resample_rows";
         if (S.tiled) return S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled";
         return "k_resample";
-    case ST_SAMPLEAT: return "k_sample_at";
+    case ST_SAMPLEAT: return S.sa_kind == 1 ? "k_sample_at_cubic" : S.sa_kind == 2 ? "k_sample_at_sinc" : "k_sample_at";
     case ST_COMB: return "k_comb";
     case ST_CUMSUM: return "k_cumsum";
     case ST_MOVING: return "k_moving";
@@ -129,8 +129,10 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return (S.need - S.base) * S.sg.nch * (esz + osz);
     case ST_RESAMPLE:  // (arr2: a second array of the source's type read)
         return (S.rg.n_in * (src_esz(S) + (S.rp.arr2 ? src_esz(S) : 0)) + S.rg.n_out * osz) * S.rg.nch;
-    case ST_SAMPLEAT:  // per frame: a position read, two table samples read where they lie, a Float64 written
-        return (S.need - S.base) * ((int64_t)P->nodes[N.kids[1]].nch * 8 + (int64_t)N.nch * (2 * kid_esz(0) + 8));
+    case ST_SAMPLEAT: {  // per frame: a position read, the table samples of its support read where they lie (2, 4 or K), a Float64 written
+        const int64_t taps = S.sa_kind == 1 ? 4 : S.sa_kind == 2 ? N.nd.i2 : 2;
+        return (S.need - S.base) * ((int64_t)P->nodes[N.kids[1]].nch * 8 + (int64_t)N.nch * (taps * kid_esz(0) + 8));
+    }
     case ST_COMB:  // per sample: one read where x lies, one Float64 written
         return S.need * (int64_t)N.nch * (kid_esz(0) + 8);
     case ST_CUMSUM:  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
@@ -805,7 +807,17 @@ static int run_sample_at(Plan* P, const Step& s, void* outp, hipStream_t st) {
     a.nch = N.nch;
     a.relative = N.nd.i0 & 1;
     a.wrap = (N.nd.i0 >> 1) & 1;
-    const int nl = launch_sample_at(a, st);
+    int nl;
+    if (N.nd.i1 == 0) {
+        nl = launch_sample_at(a, st);
+    } else {
+        SampleAtFirArgs f{};
+        f.a = a;
+        f.kind = N.nd.i1;
+        f.K = N.nd.i1 == 2 ? N.nd.i2 : 4;
+        f.tab = S.sa_tab_buf >= 0 ? (const double*)P->bufs[S.sa_tab_buf].d : nullptr;
+        nl = launch_sample_at_fir(f, st);
+    }
     if (nl < 0) fail(SO_ERR_UNSUPPORTED, "SampleAt: more than 65535 channels or 2^39 frames are not lowered");
     return nl;
 }

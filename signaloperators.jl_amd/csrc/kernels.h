@@ -105,6 +105,17 @@ struct SampleAtArgs {
     int32_t nch, x_f32, relative, wrap;
 };
 int launch_sample_at(const SampleAtArgs& a, hipStream_t st);
+// SampleAt's cubic and windowed-sinc reads (k_sample_at_fir.hip, -ffp-contract=off): the same rows, strides and modes;
+// kind 1 = Catmull-Rom, 2 = K taps of the 512-phase table `tab` (the 513 rows h, then the 512 rows dh, K doubles each, in
+// device memory).  Returns the number of launches, -1 when the shape cannot be launched.
+constexpr int kSampleAtPhases = 512;
+struct SampleAtFirArgs {
+    SampleAtArgs a;
+    const double* tab;
+    int32_t kind, K;
+};
+int launch_sample_at_fir(const SampleAtFirArgs& f, hipStream_t st);
+bool sample_at_fir_uses_lds(const SampleAtFirArgs& f);  // (the sinc kernel's form with the tap table in LDS: K <= 16, a large result)
 // Comb / Allpass (k_comb.hip, -ffp-contract=off): per channel y[n] = (b0 * x[n] + bD * x[n - D]) + a * y[n - D], n in [0, n),
 // x and y before frame 0 taken as +0.0, every product and sum rounded on its own; a term whose coefficient is exactly 0.0
 // is left out.  One lane per (residue n mod D, channel) walks its class in order.  Strides in elements.  Returns the

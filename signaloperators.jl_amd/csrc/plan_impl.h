@@ -135,6 +135,8 @@ struct Stage {
         int64_t offset = 0, pitch = 0;  // elements (an array read in place); pitch 0: one row for every channel
     } side[2];
     int64_t x_fstride = 1;                  // the table's frame stride where it lies (an interleaved array is read in place too)
+    int sa_kind = 0;                        // SampleAt: the node's i1 (0 linear, 1 cubic, 2 sinc)
+    int sa_tab_buf = -1;                    // SampleAt, sinc: the device copy of the node's tap table (Plan::tables; copied once, upload_tables)
     std::vector<DCarrier> carriers;  // periodic resampler: input expressed as carriers
     int car_buf = -1;
     int ctl_buf = -1;  // device copy of the RsCtl control block

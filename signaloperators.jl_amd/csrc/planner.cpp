@@ -260,6 +260,18 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             if (pos.nch != 1 && pos.nch != x.nch)
                 fail(SO_ERR_INVALID, where + "positions have " + std::to_string(pos.nch) + " channels: 1 or the table's " + std::to_string(x.nch) + " expected");
             if (nd.i0 & ~3) fail(SO_ERR_INVALID, where + "unknown flags " + std::to_string(nd.i0));
+            if (nd.i1 < 0 || nd.i1 > 2) fail(SO_ERR_INVALID, where + "unknown interpolation " + std::to_string(nd.i1) + " (0 linear, 1 cubic, 2 sinc)");
+            if (nd.i1 != 2) {
+                if (nd.i2 || nd.p0 || nd.s0) fail(SO_ERR_INVALID, where + "takes taps and a tap table with the sinc interpolation only");
+            } else {
+                if (nd.i2 < 4 || nd.i2 > 64 || (nd.i2 & 1)) fail(SO_ERR_INVALID, where + "needs an even number of taps from 4 to 64 (" + std::to_string(nd.i2) + " given)");
+                const int64_t want = (int64_t)(2 * kSampleAtPhases + 1) * nd.i2;
+                if (!nd.p0 || nd.s0 != want)
+                    fail(SO_ERR_INVALID, where + "needs a tap table of (2 * 512 + 1) * " + std::to_string(nd.i2) + " = " + std::to_string(want) + " doubles (" + (nd.p0 ? std::to_string(nd.s0) : std::string("none")) + " given)");
+                const double* tab = (const double*)nd.p0;
+                for (int64_t k = 0; k < want; ++k)
+                    if (!std::isfinite(tab[k])) fail(SO_ERR_INVALID, where + "tap table entry " + std::to_string(k) + " is not finite");
+            }
             N.len = pos.len;
             N.nch = x.nch;
             N.dtype = SO_F64;

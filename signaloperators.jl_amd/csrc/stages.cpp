@@ -547,6 +547,15 @@ void Plan::process_sample_at(int sid) {
     if (base > 0) check_frames(pk, base);
     stage_input(sid, lower(xk, Rect{0, Nx, 0, nch}, Map{1, 0, 1, 0}), Nx, nch, xdt);
     second_input(sid, pk, base, need - base);
+    const so_node_t& nd = nodes[ni].nd;
+    stages[sid].sa_kind = nd.i1;
+    if (nd.i1 == 2) {  // the sinc kind's tap table: a constant the plan copies to the device once, like an SO_EOP_INTERP table
+        const size_t n = (size_t)nd.s0;
+        tables.push_back(InterpTable{(const double*)nd.p0, n, raw_buf(n * 8)});
+        stages[sid].sa_tab_buf = tables.back().buf;
+        if (std::getenv("SIGOPS_DEBUG_PLAN"))
+            std::fprintf(stderr, "[sigops] SampleAt node %d: sinc, %d taps, cutoff %g, a table of %zu doubles\n", ni, nd.i2, nd.d2, n);
+    }
 }
 
 // A further input of a stage -- SampleAt's positions, Recur's coefficients, each of Recur2's two -- over `frames` frames from

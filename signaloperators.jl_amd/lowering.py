@@ -559,6 +559,12 @@ def lower(x, nframes_out=None, rng=None):
             kids = (rec(s.signal), rec(s.pos))
             r = common(s, K.NODE_SAMPLEAT)
             r.update(i0=(1 if s.relative else 0) | (2 if s.wrap else 0), d0=s.left, d1=s.right, children=kids)
+            if s.interp != "linear":  # ("linear": the node as it always was, i1 = 0)
+                r["i1"] = S.SAMPLEAT_INTERP.index(s.interp)
+            if s.interp == "sinc":  # the rows of h, then the rows of dh (include/sigops.h)
+                tab = np.concatenate([a.ravel() for a in S.sampleat_taps(s.taps, s.cutoff)])
+                lw.keep.append(tab)
+                r.update(i2=s.taps, p0=tab.ctypes.data, s0=int(tab.size), d2=s.cutoff)
             idx = lw.add(**r)
         elif isinstance(s, S.CombSignal):
             c = rec(s.signal)

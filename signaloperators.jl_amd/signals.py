@@ -509,13 +509,17 @@ class FilteredSignal(WrappedSignal):
 
 
 class SampleAtSignal(AbstractSignal):
-    """`SampleAt(x, pos)`: the table `x` read at the positions the signal `pos` gives, with linear interpolation (no
-    reference counterpart; include/sigops.h SO_NODE_SAMPLEAT, DESIGN.md "SampleAt").  It has the length and frame rate
-    of `pos`, the channels of `x`, and is Float64 like `np.interp`."""
+    """`SampleAt(x, pos)`: the table `x` read at the positions the signal `pos` gives, with linear interpolation --
+    `interp="cubic"`: Catmull-Rom; `interp="sinc"`: `taps` taps of a Kaiser-windowed sinc with its pass-band edge at
+    `cutoff` of the table's Nyquist -- (no reference counterpart; include/sigops.h SO_NODE_SAMPLEAT, DESIGN.md
+    "SampleAt").  It has the length and frame rate of `pos`, the channels of `x`, and is Float64 like `np.interp`."""
 
     evaltrait = "computed"
 
-    def __init__(self, x, pos, left=0.0, right=0.0, relative=False, wrap=False):
+    def __init__(self, x, pos, left=0.0, right=0.0, relative=False, wrap=False, interp="linear", taps=0, cutoff=0.0):
+        self.interp = interp  # "linear" | "cubic" | "sinc"
+        self.taps = int(taps)  # sinc only (0 otherwise)
+        self.cutoff = float(cutoff)  # sinc only (0.0 otherwise)
         self.signal = x
         self.pos = pos
         self.children = (x, pos)
@@ -1071,7 +1075,7 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         # rate is not consulted); a result that has a rate is resampled like any computed signal
         if known:
             return _resample(x, fs, bs)
-        return SampleAtSignal(x.signal, ToFramerate(x.pos, fs, bs), x.left, x.right, x.relative, x.wrap)
+        return SampleAtSignal(x.signal, ToFramerate(x.pos, fs, bs), x.left, x.right, x.relative, x.wrap, x.interp, x.taps, x.cutoff)
     if isinstance(x, CombSignal):
         # the delay is a number of frames (a time was converted with the rate x had): a missing rate goes to x, a
         # result that has a rate is resampled like any computed signal
@@ -1218,7 +1222,56 @@ def _real_number(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
 
 
-def _SampleAt(x, pos, left=0.0, right=0.0, relative=False, wrap=False):
+SAMPLEAT_INTERP = ("linear", "cubic", "sinc")  # the node's i1
+SAMPLEAT_PHASES = 512
+
+
+def sampleat_beta(taps):
+    """the Kaiser window's shape for `taps` taps (DESIGN.md "SampleAt"): 96 dB of stop-band attenuation from 16 taps on,
+    5.0 (about 54 dB) for the short kernels, whose main lobe would otherwise swallow the pass band"""
+    return 0.1102 * (96 - 8.7) if taps >= 16 else 5.0
+
+
+def sampleat_taps(taps, cutoff):
+    """the tap tables of `SampleAt(..., interp="sinc")`: `h`, 513 rows (phase 0 .. 512 of 512) of `taps` Float64, and
+    `dh[ph] = h[ph + 1] - h[ph]`, 512 rows.  Row ph, tap k lies d = ph/512 - (k - taps/2 + 1) frames from the position:
+    h = cutoff sinc(cutoff d) kaiser(d / (taps/2)), each row divided by its sum; with cutoff == 1 rows 0 and 512 are the
+    exact unit impulses.  (tests/sampleat_interp_ref.py restates this; the device receives the bytes.)"""
+    K, P = int(taps), SAMPLEAT_PHASES
+    c = np.float64(cutoff)
+    d = np.arange(P + 1, dtype=np.float64)[:, None] / np.float64(P) - (np.arange(K, dtype=np.float64)[None, :] - np.float64(K // 2 - 1))
+    w = d / np.float64(K // 2)
+    beta = np.float64(sampleat_beta(K))
+    h = c * np.sinc(c * d) * (np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - w * w))) / np.i0(beta))
+    h = h / h.sum(axis=1)[:, None]
+    if c == 1.0:
+        h[0] = 0.0
+        h[0, K // 2 - 1] = 1.0
+        h[P] = 0.0
+        h[P, K // 2] = 1.0
+    return np.ascontiguousarray(h), np.ascontiguousarray(h[1:] - h[:-1])
+
+
+def _sampleat_kind(what, interp, taps, cutoff):
+    """(interp, taps, cutoff) checked: `taps` and `cutoff` belong to "sinc" alone (None: not given)"""
+    if interp not in SAMPLEAT_INTERP:
+        error(f'{what}: interp must be "linear", "cubic" or "sinc", not {interp!r}')
+    if interp != "sinc":
+        for name, v in (("taps", taps), ("cutoff", cutoff)):
+            if v is not None:
+                error(f'{what}: {name} is an argument of interp="sinc" only (interp={interp!r} given)')
+        return interp, 0, 0.0
+    taps = 16 if taps is None else taps
+    cutoff = 1.0 if cutoff is None else cutoff
+    if isinstance(taps, (bool, np.bool_)) or not isinstance(taps, (int, np.integer)) or taps < 4 or taps > 64 or taps % 2:
+        error(f"{what}: taps must be an even integer from 4 to 64, not {taps!r}")
+    if not _real_number(cutoff) or not (0.0 < cutoff <= 1.0):
+        error(f"{what}: cutoff must be a number in (0, 1], a fraction of the table's Nyquist, not {cutoff!r}")
+    return interp, int(taps), float(cutoff)
+
+
+def _SampleAt(x, pos, left=0.0, right=0.0, relative=False, wrap=False, interp="linear", taps=None, cutoff=None, what="SampleAt"):
+    interp, taps, cutoff = _sampleat_kind(what, interp, taps, cutoff)
     x = _assignal(x)
     n = nframes(x)
     if n is None or isknowninf(n):
@@ -1237,14 +1290,20 @@ def _SampleAt(x, pos, left=0.0, right=0.0, relative=False, wrap=False):
         error("SampleAt: the positions must be Float32 or Float64 (use `ToEltype`)")
     if pos.nch not in (1, x.nch):
         error(f"SampleAt: the positions have {pos.nch} channels; 1 or the table's {x.nch} expected")
-    return SampleAtSignal(x, pos, left, right, relative, wrap)
+    return SampleAtSignal(x, pos, left, right, relative, wrap, interp, taps, cutoff)
 
 
-def SampleAt(*args, left=0.0, right=0.0, relative=False, wrap=False):
+_NOT_GIVEN = object()
+
+
+def SampleAt(*args, left=0.0, right=0.0, relative=False, wrap=False, interp="linear", taps=_NOT_GIVEN, cutoff=_NOT_GIVEN):
     """`SampleAt(x, pos)`, curried `x | SampleAt(pos)`: frame n, channel c of the result is
     `np.interp(p, arange(N), x[:, c], left, right)` -- `np.interp(p, arange(N), x[:, c], period=N)` with `wrap` -- at
-    `p = pos[n, c]` (`n + pos[n, c]` with `relative`): positions count the frames of `x` from 0."""
-    kw = dict(left=left, right=right, relative=relative, wrap=wrap)
+    `p = pos[n, c]` (`n + pos[n, c]` with `relative`): positions count the frames of `x` from 0.  `interp="cubic"` reads
+    through a Catmull-Rom polynomial, `interp="sinc"` through `taps` (16; even, 4 .. 64) taps of a Kaiser-windowed sinc
+    whose pass band ends at `cutoff` (1.0; in (0, 1]) of the table's Nyquist -- `1 / v` for a read at speed v > 1."""
+    kw = dict(left=left, right=right, relative=relative, wrap=wrap, interp=interp,
+              taps=None if taps is _NOT_GIVEN else taps, cutoff=None if cutoff is _NOT_GIVEN else cutoff)
     if len(args) == 1:
         pos = args[0]
         return Curried(lambda x: _SampleAt(x, pos, **kw))
@@ -1253,8 +1312,10 @@ def SampleAt(*args, left=0.0, right=0.0, relative=False, wrap=False):
     return _SampleAt(args[0], args[1], **kw)
 
 
-def _Delay(x, d):
+def _Delay(x, d, interp="linear", taps=None, cutoff=None):
     from .units import frames
+
+    _sampleat_kind("Delay", interp, taps, cutoff)
 
     x = _assignal(x)
     n = nframes(x)
@@ -1276,19 +1337,21 @@ def _Delay(x, d):
         if x.fs is not None:
             d = ToFramerate(d, x.fs)
         pos = _OperateOn(SUB, [d])
-    y = _SampleAt(x, pos, relative=True)
+    y = _SampleAt(x, pos, relative=True, interp=interp, taps=taps, cutoff=cutoff, what="Delay")
     return _Until(_Pad(y, zero), n * frames)
 
 
-def Delay(*args):
+def Delay(*args, interp="linear", taps=_NOT_GIVEN, cutoff=_NOT_GIVEN):
     """`Delay(x, d)`, curried `x | Delay(d)`: `x` delayed by `d` frames (a number or a signal; a time quantity is
-    converted with the rate of `x`), zeros before its first frame: `SampleAt(x, -d, relative=True)` over the frames of `x`."""
+    converted with the rate of `x`), zeros before its first frame: `SampleAt(x, -d, relative=True)` over the frames of `x`,
+    with `SampleAt`'s `interp`, `taps` and `cutoff`."""
+    kw = dict(interp=interp, taps=None if taps is _NOT_GIVEN else taps, cutoff=None if cutoff is _NOT_GIVEN else cutoff)
     if len(args) == 1:
         d = args[0]
-        return Curried(lambda x: _Delay(x, d))
+        return Curried(lambda x: _Delay(x, d, **kw))
     if len(args) != 2:
         error("Delay(x, d) expected")
-    return _Delay(args[0], args[1])
+    return _Delay(args[0], args[1], **kw)
 
 
 # --------------------------------------------------------------------------

@@ -138,6 +138,14 @@ cases = {
     "sampleat vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True),
     "sampleat random": lambda: so.SampleAt(X, POS("random")),
     "sampleat wrap 2048": lambda: so.SampleAt(so.Signal(x[:2048], fs), POS("wavetable"), wrap=True),
+    # `interp="cubic" | "sinc"` (csrc/k_sample_at_fir.hip): the same positions read through four points or through K taps of
+    # the 512-phase table (K = 16 from LDS, K = 64 from L2); the yardstick of a row is the linear row of its position pattern
+    "sampleat cubic identity": lambda: so.SampleAt(X, POS("identity"), relative=True, interp="cubic"),
+    "sampleat cubic vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True, interp="cubic"),
+    "sampleat sinc16 vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True, interp="sinc"),
+    "sampleat sinc16 random": lambda: so.SampleAt(X, POS("random"), interp="sinc"),
+    "sampleat sinc64 vibrato": lambda: so.SampleAt(X, POS("vibrato"), relative=True, interp="sinc", taps=64),
+    "wavetable cubic": lambda: so.SampleAt(so.Signal(x[:2048], fs), POS("wavetable"), wrap=True, interp="cubic"),
     # `Comb(x, d, g)` / `Allpass(x, d, g)` (include/sigops.h SO_NODE_COMB, csrc/k_comb.hip): a lane per (frame mod D,
     # channel) -- an echo of 4800 frames fills the chip, a delay of 48 frames is 48 lanes a channel (the documented slow
     # corner); the yardstick is the `copy (Until)` row at the top, one read and one write per sample
