@@ -10,7 +10,7 @@ from .signals import (  # noqa: F401
     ToFramerate, ToChannels, ToEltype, Format, Uniform,
     ArraySig, NumberSig, FuncSig, CutApply, PaddedSignal, AppendSignals, RampSignal,
     MapSignal, FilteredSignal, NormedSignal, FilterFn, RawFilterFn, RawFirFn, ResamplerFn, digitalfilter, ZeroPoleGain, SecondOrderSections, Biquad,
-    PolynomialRatio, SampleAt, Delay, SampleAtSignal, Comb, Allpass, CombSignal, Cumsum, Integrate, CumsumSignal,
+    PolynomialRatio, StageSignal, SampleAt, Delay, SampleAtSignal, Comb, Allpass, CombSignal, Cumsum, Integrate, CumsumSignal,
     MovingMax, MovingMin, MovingSignal, MovingSum, MovingMean, MovingRMS, MovingSumSignal, MovingMedian, MovingQuantile, MovingRankSignal, Recur, OnePole, Smooth, PeakDecay, RecurSignal, Recur2, Resonator, Sweep, Recur2Signal,
 )
 from numpy import sin, cos  # noqa: F401  (Signal(sin), Signal(cos))

@@ -97,15 +97,10 @@ static const char* stage_step_name(const Stage& S) {
         if (S.tiled) return S.arbk ? "k_resample_arb" : S.rt.pair ? "k_resample_tiled2" : "k_resample_tiled";
         return "k_resample";
     case ST_SAMPLEAT: return S.sa_kind == 1 ? "k_sample_at_cubic" : S.sa_kind == 2 ? "k_sample_at_sinc" : "k_sample_at";
-    case ST_COMB: return "k_comb";
-    case ST_CUMSUM: return "k_cumsum";
-    case ST_MOVING: return "k_moving";
-    case ST_MOVSUM: return "k_movsum";
-    case ST_RECUR: return "k_recur";
-    case ST_RECUR2: return "k_recur2";
-    case ST_MOVRANK: return "k_movrank";
-    default: return "k_sumsq";
     }
+    for (const StageNodeKind& k : kStageNodes)
+        if (k.stage == S.kind) return k.step;
+    return "k_sumsq";
 }
 
 // Algorithmic bytes of a stage: the samples it reads in the type they have WHERE THEY LIE (a Float32 array under a Float64

@@ -108,6 +108,37 @@ struct Buf {
 };
 
 enum { ST_SOS, ST_RESAMPLE, ST_NORM, ST_SAMPLEAT, ST_COMB, ST_CUMSUM, ST_MOVING, ST_MOVSUM, ST_RECUR, ST_RECUR2, ST_MOVRANK };
+// The device-only stage nodes, one row each: the node kind, the name messages print, the kind of its stage, the name its step
+// goes by (SampleAt's interpolating forms have names of their own: stage_step_name, executor.cpp) and what a dry run of the
+// frames [0, hi) asks of its children (Plan::lower_stage_node, planner.cpp).
+enum {
+    SD_TABLE_AND_POSITIONS,  // child 0 whole, child 1 up to hi
+    SD_FIRST_CHILD,          // child 0 up to hi
+    SD_EVERY_CHILD,          // every child up to hi
+    SD_FIRST_CHILD_AHEAD,    // child 0 up to hi + l1
+};
+struct StageNodeKind {
+    int node;
+    const char* name;
+    int stage;
+    const char* step;
+    int demand;
+};
+constexpr StageNodeKind kStageNodes[] = {
+    {SO_NODE_SAMPLEAT, "SampleAt", ST_SAMPLEAT, "k_sample_at", SD_TABLE_AND_POSITIONS},
+    {SO_NODE_COMB, "Comb", ST_COMB, "k_comb", SD_FIRST_CHILD},
+    {SO_NODE_CUMSUM, "Cumsum", ST_CUMSUM, "k_cumsum", SD_FIRST_CHILD},
+    {SO_NODE_MOVING, "Moving", ST_MOVING, "k_moving", SD_FIRST_CHILD_AHEAD},
+    {SO_NODE_MOVSUM, "Movsum", ST_MOVSUM, "k_movsum", SD_FIRST_CHILD_AHEAD},
+    {SO_NODE_MOVRANK, "Movrank", ST_MOVRANK, "k_movrank", SD_FIRST_CHILD_AHEAD},
+    {SO_NODE_RECUR, "Recur", ST_RECUR, "k_recur", SD_EVERY_CHILD},
+    {SO_NODE_RECUR2, "Recur2", ST_RECUR2, "k_recur2", SD_EVERY_CHILD},
+};
+constexpr const StageNodeKind* stage_node_kind(int node) {
+    for (const StageNodeKind& k : kStageNodes)
+        if (k.node == node) return &k;
+    return nullptr;
+}
 struct Stage {
     int kind, node;
     int64_t need = 0;  // output frames [0,need)
@@ -483,6 +514,8 @@ struct Plan {
     // to `dtype` at the end (-1: left as the program leaves it)
     int prog_expr(const so_node_t& nd, const so_eop_t* prog, int len, const std::vector<int>& args, int dtype);
     int stage_for(int ni, int kind);
+    int stage_load(int sid, const Map& m);  // (the E_LOAD of a stage's output buffer)
+    std::vector<Piece> lower_stage_node(const StageNodeKind& k, int ni, Rect r, Map m);
     void use_stage(Stage& S, const Rect& r, const Map& m);
     int in_norm = 0;  // > 0: lowering below a Normpower (stages created or used here are marked Stage::under_norm)
     int dry = 0;  // > 0: lower() only looks for the errors evaluating those frames raises (no stages, no buffers)
@@ -490,9 +523,7 @@ struct Plan {
     void process_stage(int sid);  // (stages.cpp: the dispatch to one routine per stage kind)
     void process_sample_at(int sid);
     void process_moving(int sid);
-    void process_comb(int sid);  // (Comb and Cumsum: the stages that compute [0, need) from one plain input)
-    void process_recur(int sid);
-    void process_recur2(int sid);
+    void process_from_frame_0(int sid);  // (Comb, Cumsum, Recur and Recur2: the stages that compute [0, need))
     void second_input(int sid, int kid, int64_t base, int64_t frames, int which = 0);  // (SampleAt's positions, Recur's and Recur2's coefficients: Stage::side[which])
     void stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype);
     // the resampler: its forms, tried in this order (each returns at once where an earlier one took the stage)

@@ -94,6 +94,47 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             if ((int)N.kids.size() <= j) fail(SO_ERR_INVALID, "node " + std::to_string(i) + ": missing child");
             return nodes[N.kids[j]];
         };
+        // what the device-only stage nodes check, in one vocabulary (every text names the node and the child as before)
+        const StageNodeKind* sk = stage_node_kind(nd.kind);
+        const std::string where = sk ? "node " + std::to_string(i) + ": " + sk->name + " " : std::string();
+        auto takes = [&](size_t k, size_t or_k, const char* what) {
+            if (N.kids.size() != k && N.kids.size() != or_k) fail(SO_ERR_INVALID, where + "takes " + what + " (" + std::to_string(N.kids.size()) + " given)");
+        };
+        auto floats = [&](const Node& c, const std::string& name) {
+            if (c.dtype != SO_F32 && c.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 " + name + " (integer sample types are not lowered)");
+        };
+        auto finite = [&](const Node& c, const char* name) {
+            if (isinf_(c.len)) fail(SO_ERR_LENGTH, where + "needs a " + name + " of known, finite length (use `Until`)");
+        };
+        auto window = [&] {
+            if (nd.l0 < 0 || nd.l1 < 0)
+                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+        };
+        auto shaped = [&](const Node& len, const Node& chans, int dtype) {  // (an infinite child of a Moving node: the window is clipped at the front only)
+            N.len = len.len;
+            N.nch = chans.nch;
+            N.dtype = dtype;
+        };
+        // Recur and Recur2 once their child count is known: b is the last child, before it one row of coefficients per
+        // order (a, or a1 and a2) when they are signals; the constants are checked when they are not
+        auto scan = [&](bool constants_finite, const char* constants) {
+            const int rows = (int)N.kids.size() - 1;
+            Node& b = kid(rows);
+            if (!rows && !constants_finite) fail(SO_ERR_INVALID, where + "takes " + constants);
+            finite(b, "signal b");
+            floats(b, "signal b");
+            for (int w = 0; w < rows; ++w) {
+                Node& a = kid(w);
+                const std::string name = rows == 1 ? "a" : w ? "a2" : "a1";
+                floats(a, "signal " + name);
+                if (a.nch != 1 && a.nch != b.nch)
+                    fail(SO_ERR_INVALID, where + "coefficients " + name + " have " + std::to_string(a.nch) + " channels: 1 or b's " + std::to_string(b.nch) + " expected");
+                if (!isinf_(a.len) && a.len.n < b.len.n)
+                    fail(SO_ERR_LENGTH, where + "coefficients " + name + " have " + std::to_string(a.len.n) + " frames, fewer than b's " + std::to_string(b.len.n));
+            }
+            shaped(b, b, SO_F64);
+            if (rows && !N.short_skip) N.short_skip = b.short_skip;
+        };
         switch (nd.kind) {
         case SO_NODE_ARRAY:
             if (nd.dtype != SO_F32 && nd.dtype != SO_F64)
@@ -249,13 +290,12 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             break;
         }
         case SO_NODE_SAMPLEAT: {  // x read at the positions pos gives (no reference counterpart; DESIGN.md "SampleAt")
-            const std::string where = "node " + std::to_string(i) + ": SampleAt ";
-            if (N.kids.size() != 2) fail(SO_ERR_INVALID, where + "takes two children, the table x and the positions pos (" + std::to_string(N.kids.size()) + " given)");
+            takes(2, 2, "two children, the table x and the positions pos");
             Node& x = kid(0);
             Node& pos = kid(1);
-            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a table x of known, finite length (use `Until`)");
+            finite(x, "table x");
             if (x.len.n < 1) fail(SO_ERR_LENGTH, where + "needs a table x of at least one frame");
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 table x (integer sample types are not lowered)");
+            floats(x, "table x");
             if (pos.dtype != SO_F32 && pos.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "takes Float32 or Float64 positions");
             if (pos.nch != 1 && pos.nch != x.nch)
                 fail(SO_ERR_INVALID, where + "positions have " + std::to_string(pos.nch) + " channels: 1 or the table's " + std::to_string(x.nch) + " expected");
@@ -272,122 +312,65 @@ void Plan::build_nodes(const so_node_t* in, int n) {
                 for (int64_t k = 0; k < want; ++k)
                     if (!std::isfinite(tab[k])) fail(SO_ERR_INVALID, where + "tap table entry " + std::to_string(k) + " is not finite");
             }
-            N.len = pos.len;
-            N.nch = x.nch;
-            N.dtype = SO_F64;
+            shaped(pos, x, SO_F64);
             if (pos.short_skip) N.short_skip = pos.short_skip;
             break;
         }
         case SO_NODE_COMB: {  // a feedback delay line of l0 frames (no reference counterpart; DESIGN.md "Comb")
-            const std::string where = "node " + std::to_string(i) + ": Comb ";
-            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            takes(1, 1, "one child, the signal x");
             Node& x = kid(0);
             if (nd.l0 < 1) fail(SO_ERR_INVALID, where + "needs a delay of at least one frame (" + std::to_string(nd.l0) + " given)");
             if (!std::isfinite(nd.d0) || !std::isfinite(nd.d1) || !std::isfinite(nd.d2)) fail(SO_ERR_INVALID, where + "takes finite coefficients b0, bD and a");
-            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a signal x of known, finite length (use `Until`)");
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
-            N.len = x.len;
-            N.nch = x.nch;
-            N.dtype = SO_F64;
+            finite(x, "signal x");
+            floats(x, "signal x");
+            shaped(x, x, SO_F64);
             break;
         }
         case SO_NODE_CUMSUM: {  // the running sum over one fixed summation tree (no reference counterpart; DESIGN.md "Cumsum")
-            const std::string where = "node " + std::to_string(i) + ": Cumsum ";
-            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            takes(1, 1, "one child, the signal x");
             Node& x = kid(0);
-            if (isinf_(x.len)) fail(SO_ERR_LENGTH, where + "needs a signal x of known, finite length (use `Until`)");
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
-            N.len = x.len;
-            N.nch = x.nch;
-            N.dtype = SO_F64;
+            finite(x, "signal x");
+            floats(x, "signal x");
+            shaped(x, x, SO_F64);
             break;
         }
         case SO_NODE_MOVING: {  // sliding-window extrema over [n - l0, n + l1] (no reference counterpart; DESIGN.md "Moving extrema")
-            const std::string where = "node " + std::to_string(i) + ": Moving ";
-            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            takes(1, 1, "one child, the signal x");
             Node& x = kid(0);
-            if (nd.l0 < 0 || nd.l1 < 0)
-                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            window();
             if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is a maximum (0) or a minimum (1), not " + std::to_string(nd.i0));
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
-            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
-            N.nch = x.nch;
-            N.dtype = x.dtype;
+            floats(x, "signal x");
+            shaped(x, x, x.dtype);
             break;
         }
         case SO_NODE_MOVSUM: {  // sliding sums over [n - l0, n + l1], one fixed summation tree (no reference counterpart; DESIGN.md "Moving sums")
-            const std::string where = "node " + std::to_string(i) + ": Movsum ";
-            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            takes(1, 1, "one child, the signal x");
             Node& x = kid(0);
-            if (nd.l0 < 0 || nd.l1 < 0)
-                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            window();
             if (nd.i0 < 0 || nd.i0 > 2) fail(SO_ERR_INVALID, where + "is a sum (0), a mean (1) or an rms (2), not " + std::to_string(nd.i0));
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
-            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
-            N.nch = x.nch;
-            N.dtype = SO_F64;
+            floats(x, "signal x");
+            shaped(x, x, SO_F64);
             break;
         }
         case SO_NODE_MOVRANK: {  // the sample of rank floor(d0 (m - 1)) of the window [n - l0, n + l1] (no reference counterpart; DESIGN.md "Moving ranks")
-            const std::string where = "node " + std::to_string(i) + ": Movrank ";
-            if (N.kids.size() != 1) fail(SO_ERR_INVALID, where + "takes one child, the signal x (" + std::to_string(N.kids.size()) + " given)");
+            takes(1, 1, "one child, the signal x");
             Node& x = kid(0);
-            if (nd.l0 < 0 || nd.l1 < 0)
-                fail(SO_ERR_INVALID, where + "needs a window of back >= 0 and ahead >= 0 frames (" + std::to_string(nd.l0) + " and " + std::to_string(nd.l1) + " given)");
+            window();
             if (!(nd.d0 >= 0.0 && nd.d0 <= 1.0)) fail(SO_ERR_INVALID, where + "needs a quantile q in [0, 1], not " + std::to_string(nd.d0));
-            if (x.dtype != SO_F32 && x.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal x (integer sample types are not lowered)");
+            floats(x, "signal x");
             // (one form is built: process_moving refuses a window that does not fit it, once it knows the frames it reads)
-            N.len = x.len;  // (an infinite x: the window is clipped at the front only)
-            N.nch = x.nch;
-            N.dtype = x.dtype;
+            shaped(x, x, x.dtype);
             break;
         }
         case SO_NODE_RECUR: {  // the first-order scan y[n] = J(a[n], y[n-1], b[n]) over one fixed tree (no reference counterpart; DESIGN.md "Recur")
-            const std::string where = "node " + std::to_string(i) + ": Recur ";
             if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is affine (0) or max-decay (1), not " + std::to_string(nd.i0));
-            if (N.kids.size() != 1 && N.kids.size() != 2)
-                fail(SO_ERR_INVALID, where + "takes one child, the signal b (the constant a in d0), or two, a and b (" + std::to_string(N.kids.size()) + " given)");
-            const bool row = N.kids.size() == 2;
-            Node& b = kid(row ? 1 : 0);
-            if (!row && !std::isfinite(nd.d0)) fail(SO_ERR_INVALID, where + "takes a finite constant a");
-            if (isinf_(b.len)) fail(SO_ERR_LENGTH, where + "needs a signal b of known, finite length (use `Until`)");
-            if (b.dtype != SO_F32 && b.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal b (integer sample types are not lowered)");
-            if (row) {
-                Node& a = kid(0);
-                if (a.dtype != SO_F32 && a.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal a (integer sample types are not lowered)");
-                if (a.nch != 1 && a.nch != b.nch)
-                    fail(SO_ERR_INVALID, where + "coefficients a have " + std::to_string(a.nch) + " channels: 1 or b's " + std::to_string(b.nch) + " expected");
-                if (!isinf_(a.len) && a.len.n < b.len.n)
-                    fail(SO_ERR_LENGTH, where + "coefficients a have " + std::to_string(a.len.n) + " frames, fewer than b's " + std::to_string(b.len.n));
-            }
-            N.len = b.len;
-            N.nch = b.nch;
-            N.dtype = SO_F64;
-            if (row && !N.short_skip) N.short_skip = b.short_skip;
+            takes(1, 2, "one child, the signal b (the constant a in d0), or two, a and b");
+            scan(std::isfinite(nd.d0), "a finite constant a");
             break;
         }
         case SO_NODE_RECUR2: {  // the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart; DESIGN.md "Recur2")
-            const std::string where = "node " + std::to_string(i) + ": Recur2 ";
-            if (N.kids.size() != 1 && N.kids.size() != 3)
-                fail(SO_ERR_INVALID, where + "takes one child, the signal b (the constants a1 in d0 and a2 in d1), or three, a1, a2 and b (" + std::to_string(N.kids.size()) + " given)");
-            const bool row = N.kids.size() == 3;
-            Node& b = kid(row ? 2 : 0);
-            if (!row && !(std::isfinite(nd.d0) && std::isfinite(nd.d1))) fail(SO_ERR_INVALID, where + "takes finite constants a1 and a2");
-            if (isinf_(b.len)) fail(SO_ERR_LENGTH, where + "needs a signal b of known, finite length (use `Until`)");
-            if (b.dtype != SO_F32 && b.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal b (integer sample types are not lowered)");
-            for (int w = 0; row && w < 2; ++w) {
-                Node& a = kid(w);
-                const std::string name = w ? "a2" : "a1";
-                if (a.dtype != SO_F32 && a.dtype != SO_F64) fail(SO_ERR_UNSUPPORTED, where + "reads a Float32 or Float64 signal " + name + " (integer sample types are not lowered)");
-                if (a.nch != 1 && a.nch != b.nch)
-                    fail(SO_ERR_INVALID, where + "coefficients " + name + " have " + std::to_string(a.nch) + " channels: 1 or b's " + std::to_string(b.nch) + " expected");
-                if (!isinf_(a.len) && a.len.n < b.len.n)
-                    fail(SO_ERR_LENGTH, where + "coefficients " + name + " have " + std::to_string(a.len.n) + " frames, fewer than b's " + std::to_string(b.len.n));
-            }
-            N.len = b.len;
-            N.nch = b.nch;
-            N.dtype = SO_F64;
-            if (row && !N.short_skip) N.short_skip = b.short_skip;
+            takes(1, 3, "one child, the signal b (the constants a1 in d0 and a2 in d1), or three, a1, a2 and b");
+            scan(std::isfinite(nd.d0) && std::isfinite(nd.d1), "finite constants a1 and a2");
             break;
         }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
@@ -652,6 +635,51 @@ int Plan::prog_expr(const so_node_t& nd, const so_eop_t* prog, int len, const st
     if (dtype == SO_F32 && exprs[e].dtype != SO_F32) e = mk_un(E_ROUND32, e, SO_F32);
     else if (dtype == SO_F64 && exprs[e].dtype != SO_F64) e = mk_un(E_RETYPE, e, SO_F64);
     return e;
+}
+
+// the output buffer of a stage as whoever consumes it reads it
+int Plan::stage_load(int sid, const Map& m) {
+    const Node& N = nodes[stages[sid].node];
+    Expr e;
+    e.op = E_LOAD;
+    e.dtype = N.dtype;
+    e.leaf = mk_leafmap(m);
+    e.leaf.fstride = 1;
+    e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
+    e.leaf.dtype = N.dtype;
+    e.leaf.buf = stages[sid].out_buf;
+    e.mono = (m.sc == 0);
+    return add_expr(e);
+}
+
+// A device-only stage node (kStageNodes, plan_impl.h): a stage computes its frames from what its rule asks of the children --
+// the table whole and the positions of the frames anybody reads; the child from frame 0, where a recurrence or a sum starts
+// whoever reads it (every child, when the coefficients are signals); the child's frames plus `back` before and `ahead`
+// after -- and the result is a plain buffer for whoever consumes it (process_stage, stages.cpp).
+std::vector<Piece> Plan::lower_stage_node(const StageNodeKind& k, int ni, Rect r, Map m) {
+    Node& N = nodes[ni];
+    std::vector<Piece> out;
+    if (dry) {
+        const int64_t hi = m.sf ? r.b + m.df : m.df + 1;
+        switch (k.demand) {
+        case SD_TABLE_AND_POSITIONS:
+            check_frames(N.kids[0], nodes[N.kids[0]].len.n);
+            check_frames(N.kids[1], hi);
+            break;
+        case SD_FIRST_CHILD: check_frames(N.kids[0], hi); break;
+        case SD_EVERY_CHILD:
+            for (int c : N.kids) check_frames(c, hi);
+            break;
+        case SD_FIRST_CHILD_AHEAD: check_frames(N.kids[0], hi < BIG - N.nd.l1 ? hi + N.nd.l1 : BIG); break;
+        }
+        out.push_back({r, mk_const(0.0, N.dtype)});
+        return out;
+    }
+    const int sid = stage_for(ni, k.stage);
+    use_stage(stages[sid], r, m);
+    if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
+    out.push_back({r, stage_load(sid, m)});
+    return out;
 }
 
 std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
@@ -928,16 +956,7 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
             }
             return ps;
         }
-        Expr e;
-        e.op = E_LOAD;
-        e.dtype = N.dtype;
-        e.leaf = mk_leafmap(m);
-        e.leaf.fstride = 1;
-        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
-        e.leaf.dtype = N.dtype;
-        e.leaf.buf = stages[sid].out_buf;
-        e.mono = (m.sc == 0);
-        int le = add_expr(e);
+        int le = stage_load(sid, m);
         if (kind == ST_NORM) {  // vals ./= rms   (reference src/filters.jl:304-305)
             Expr s;
             s.op = E_SCALAR;
@@ -955,105 +974,9 @@ std::vector<Piece> Plan::lower(int ni, Rect r, Map m) {
         out.push_back({r, le});
         return out;
     }
-    case SO_NODE_SAMPLEAT: {
-        // a stage: the table below it is materialised whole (or read in place), the positions over the frames anybody
-        // reads; the result is a plain buffer for whoever consumes it (process_sample_at, stages.cpp)
-        const Node& X = nodes[N.kids[0]];
-        if (dry) {
-            check_frames(N.kids[0], X.len.n);
-            check_frames(N.kids[1], m.sf ? r.b + m.df : m.df + 1);
-            out.push_back({r, mk_const(0.0, N.dtype)});
-            return out;
-        }
-        const int sid = stage_for(ni, ST_SAMPLEAT);
-        use_stage(stages[sid], r, m);
-        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
-        Expr e;
-        e.op = E_LOAD;
-        e.dtype = N.dtype;
-        e.leaf = mk_leafmap(m);
-        e.leaf.fstride = 1;
-        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
-        e.leaf.dtype = N.dtype;
-        e.leaf.buf = stages[sid].out_buf;
-        e.mono = (m.sc == 0);
-        out.push_back({r, add_expr(e)});
-        return out;
-    }
-    case SO_NODE_COMB:
-    case SO_NODE_CUMSUM: {
-        // a stage: the recurrence (the sum) starts at frame 0, so the stage computes the frames [0, need) whoever reads it
-        // and a window reads its slice of that buffer (process_comb, stages.cpp)
-        if (dry) {
-            check_frames(N.kids[0], m.sf ? r.b + m.df : m.df + 1);
-            out.push_back({r, mk_const(0.0, N.dtype)});
-            return out;
-        }
-        const int sid = stage_for(ni, N.nd.kind == SO_NODE_CUMSUM ? ST_CUMSUM : ST_COMB);
-        use_stage(stages[sid], r, m);
-        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
-        Expr e;
-        e.op = E_LOAD;
-        e.dtype = N.dtype;
-        e.leaf = mk_leafmap(m);
-        e.leaf.fstride = 1;
-        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
-        e.leaf.dtype = N.dtype;
-        e.leaf.buf = stages[sid].out_buf;
-        e.mono = (m.sc == 0);
-        out.push_back({r, add_expr(e)});
-        return out;
-    }
-    case SO_NODE_RECUR:
-    case SO_NODE_RECUR2: {
-        // a stage like Cumsum's: the recurrence starts at frame 0, so the stage computes the frames [0, need) whoever reads
-        // it, from all its inputs over the same frames (process_recur, process_recur2, stages.cpp)
-        if (dry) {
-            for (int k : N.kids) check_frames(k, m.sf ? r.b + m.df : m.df + 1);
-            out.push_back({r, mk_const(0.0, N.dtype)});
-            return out;
-        }
-        const int sid = stage_for(ni, N.nd.kind == SO_NODE_RECUR2 ? ST_RECUR2 : ST_RECUR);
-        use_stage(stages[sid], r, m);
-        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
-        Expr e;
-        e.op = E_LOAD;
-        e.dtype = N.dtype;
-        e.leaf = mk_leafmap(m);
-        e.leaf.fstride = 1;
-        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
-        e.leaf.dtype = N.dtype;
-        e.leaf.buf = stages[sid].out_buf;
-        e.mono = (m.sc == 0);
-        out.push_back({r, add_expr(e)});
-        return out;
-    }
-    case SO_NODE_MOVING:
-    case SO_NODE_MOVSUM:
-    case SO_NODE_MOVRANK: {
-        // a stage: the frames anybody reads, computed from those frames of the child plus `back` before and `ahead` after;
-        // the result is a plain buffer for whoever consumes it (process_moving, stages.cpp)
-        if (dry) {
-            const int64_t hi = m.sf ? r.b + m.df : m.df + 1;
-            check_frames(N.kids[0], hi < BIG - N.nd.l1 ? hi + N.nd.l1 : BIG);
-            out.push_back({r, mk_const(0.0, N.dtype)});
-            return out;
-        }
-        const int sid = stage_for(ni, N.nd.kind == SO_NODE_MOVSUM ? ST_MOVSUM : N.nd.kind == SO_NODE_MOVRANK ? ST_MOVRANK : ST_MOVING);
-        use_stage(stages[sid], r, m);
-        if (stages[sid].out_buf < 0) stages[sid].out_buf = new_buf(0, N.nch, N.dtype);  // sized in finalize()
-        Expr e;
-        e.op = E_LOAD;
-        e.dtype = N.dtype;
-        e.leaf = mk_leafmap(m);
-        e.leaf.fstride = 1;
-        e.leaf.cstride = -1;  // = pitch of the buffer, patched in finalize()
-        e.leaf.dtype = N.dtype;
-        e.leaf.buf = stages[sid].out_buf;
-        e.mono = (m.sc == 0);
-        out.push_back({r, add_expr(e)});
-        return out;
-    }
+    default:
+        if (const StageNodeKind* k = stage_node_kind(nd.kind)) return lower_stage_node(*k, ni, r, m);
+        break;
     }
     fail(SO_ERR_INVALID, "unknown node kind");
 }

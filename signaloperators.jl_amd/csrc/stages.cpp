@@ -3,8 +3,8 @@
 // IIR's state pass into the resampler in front of it.
 //
 // Map (routine -- what it decides -- the Stage fields it writes):
-//   process_stage            dispatch by Stage::kind to the routines below; SampleAt, Comb / Cumsum and Moving have
-//                            process_sample_at, process_comb, process_moving (Moving, Movsum and Movrank), process_recur, process_recur2 (input: stage_input, second_input)
+//   process_stage            dispatch by Stage::kind to the routines below; the device-only stage nodes have process_sample_at,
+//                            process_from_frame_0 (Comb, Cumsum, Recur, Recur2) and process_moving (Moving, Movsum, Movrank) (input: stage_input, second_input)
 //   process_resample         rs_geometry, rs_warm_start (base, in_base; RsGeom m0 / j0), rs_input_frames, rs_polyphase_tables
 //                            (pfb / dpfb), the accumulator's positions (fix_host, fix_buf), then the forms in order:
 //     plan_rs_periodic         32-row, then 16-row tiles of k_resample_periodic -- periodic, rp, tab / jend, per_j / per_p / per_a, rs_jrel
@@ -505,6 +505,11 @@ static bool plain_load(const Expr& e, int dtype, int nch, bool unit_stride, bool
 // element offset of a plain array leaf's first element: df frames and dc channels into the array
 static int64_t leaf_offset(const DLeaf& l) { return l.df * l.fstride + l.dc * std::max<int64_t>(l.cstride, 0); }
 
+// how stage_input took a stage's input (SIGOPS_DEBUG_PLAN)
+static const char* how_read(const Stage& S) {
+    return S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place";
+}
+
 // The input of stage `sid`, `frames` x `nch` of `dtype`, lowered to `ps`: read where it lies when it is plain, materialised by
 // one pointwise step otherwise (Stage::in_array_node / in_buf / x_fstride / in_pitch / in_offset / pw_step).
 void Plan::stage_input(int sid, const std::vector<Piece>& ps, int64_t frames, int nch, int dtype) {
@@ -583,13 +588,19 @@ void Plan::second_input(int sid, int kid, int64_t base, int64_t frames, int whic
     }
 }
 
-// Comb and Cumsum: the recurrence (the sum) starts at frame 0, so the stage computes the frames [0, need) of its buffer
-// (base = 0) whatever window reads it.  The child is demanded over the same frames and taken like SampleAt's table
-// (stage_input).  Cumsum owns one Float64 per (chunk that has a chunk behind it, channel) besides: the chunk totals, every
-// entry written by the execute that reads it (k_cumsum.hip), so nothing clears them.
-void Plan::process_comb(int sid) {
-    const int ni = stages[sid].node;
-    const int xk = nodes[ni].kids[0];
+// Comb, Cumsum, Recur and Recur2: the recurrence (the sum) starts at frame 0, so the stage computes the frames [0, need) of
+// its buffer (base = 0) whatever window reads it.  The last child -- x, or b -- is demanded over the same frames and taken
+// like SampleAt's table (stage_input); the children before it, the coefficient signals a of Recur and a1, a2 of Recur2, like
+// SampleAt's positions (second_input, side[0] and side[1]).  A constant next to a signal arrives as a CONST child and is
+// materialised like any formula: one row of `need` doubles written once and read twice.  All but Comb own totals per (chunk
+// that has a chunk behind it, channel) besides: Cumsum's chunk total, one Float64; Recur's last (Q, u) of the chunk, two;
+// Recur2's composite (M, v) of the chunk, six double-doubles, whose v the carry kernel turns into the state that enters the
+// next chunk.  Every entry read is written by the same execute (k_cumsum.hip, k_recur.hip, k_recur2.hip), so nothing clears
+// them.
+void Plan::process_from_frame_0(int sid) {
+    const int ni = stages[sid].node, kind = stages[sid].kind;
+    const int rows = (int)nodes[ni].kids.size() - 1;
+    const int xk = nodes[ni].kids[rows];
     const int nch = nodes[ni].nch;
     const int64_t need = stages[sid].need;
     stages[sid].processed = true;
@@ -597,77 +608,24 @@ void Plan::process_comb(int sid) {
     stages[sid].base = stages[sid].in_base = 0;
     bufs[stages[sid].out_buf].frame0 = 0;
     stage_input(sid, lower(xk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[xk].dtype);
-    const bool cumsum = stages[sid].kind == ST_CUMSUM;
-    if (cumsum && cumsum_totals(need) > 0) {
-        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 8);
-        stages[sid].aux_buf = b;
-    }
-    if (std::getenv("SIGOPS_DEBUG_PLAN"))
-        std::fprintf(stderr, "[sigops] %s stage %d: %s%lld, frames [0,%lld) x %d channels, x %s\n", cumsum ? "Cumsum" : "Comb", sid, cumsum ? "chunk totals a channel " : "D=",
-                     (long long)(cumsum ? cumsum_totals(need) : nodes[ni].nd.l0), (long long)need, nch, stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
-}
-
-// Recur: Cumsum's rule -- the recurrence starts at frame 0, so the stage computes the frames [0, need) of its buffer (base =
-// 0) whatever window reads it -- with two inputs over those frames: b taken like Cumsum's x (stage_input), and, where a is
-// a signal, the coefficients taken like SampleAt's positions (second_input).  The stage owns two Float64 per (chunk that
-// has a chunk behind it, channel) besides: the chunk's last (Q, u), every entry written by the execute that reads it
-// (k_recur.hip), so nothing clears them.
-void Plan::process_recur(int sid) {
-    const int ni = stages[sid].node;
-    const bool row = nodes[ni].kids.size() == 2;
-    const int bk = nodes[ni].kids[row ? 1 : 0];
-    const int nch = nodes[ni].nch;
-    const int64_t need = stages[sid].need;
-    stages[sid].processed = true;
-    if (need <= 0) return;
-    stages[sid].base = stages[sid].in_base = 0;
-    bufs[stages[sid].out_buf].frame0 = 0;
-    stage_input(sid, lower(bk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[bk].dtype);
-    if (row) second_input(sid, nodes[ni].kids[0], 0, need);
-    if (cumsum_totals(need) > 0) {
-        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 16);
+    for (int w = 0; w < rows; ++w) second_input(sid, nodes[ni].kids[w], 0, need, w);
+    const size_t entry = kind == ST_CUMSUM ? 8 : kind == ST_RECUR ? 16 : kind == ST_RECUR2 ? 96 : 0;
+    if (entry && cumsum_totals(need) > 0) {
+        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * entry);
         stages[sid].aux_buf = b;
     }
     if (std::getenv("SIGOPS_DEBUG_PLAN")) {
         const Stage& S = stages[sid];
-        const std::string a = !row ? "the constant " + std::to_string(nodes[ni].nd.d0)
-                                   : std::string(S.side[0].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[0].pitch == 0 ? ", one row for every channel" : "");
-        std::fprintf(stderr, "[sigops] Recur stage %d: %s, chunk totals a channel %lld, frames [0,%lld) x %d channels, b %s, a %s\n", sid, nodes[ni].nd.i0 ? "max-decay" : "affine",
-                     (long long)cumsum_totals(need), (long long)need, nch, S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place", a.c_str());
-    }
-}
-
-// Recur2: Recur's rule with three inputs over the frames [0, need): b taken like Cumsum's x (stage_input), each coefficient
-// signal like Recur's a (second_input, side[0] for a1 and side[1] for a2).  A constant next to a signal arrives as a CONST
-// child and is materialised like any formula: one row of `need` doubles written once and read twice.  The stage owns twelve
-// Float64 per (chunk that has a chunk behind it, channel) besides: the chunk's composite (M, v), six double-doubles, whose
-// v the carry kernel turns into the state that enters the next chunk; every entry read is written by the same execute (k_recur2.hip), so
-// nothing clears them.
-void Plan::process_recur2(int sid) {
-    const int ni = stages[sid].node;
-    const bool row = nodes[ni].kids.size() == 3;
-    const int bk = nodes[ni].kids[row ? 2 : 0];
-    const int nch = nodes[ni].nch;
-    const int64_t need = stages[sid].need;
-    stages[sid].processed = true;
-    if (need <= 0) return;
-    stages[sid].base = stages[sid].in_base = 0;
-    bufs[stages[sid].out_buf].frame0 = 0;
-    stage_input(sid, lower(bk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[bk].dtype);
-    if (row)
-        for (int w = 0; w < 2; ++w) second_input(sid, nodes[ni].kids[w], 0, need, w);
-    if (cumsum_totals(need) > 0) {
-        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * 96);
-        stages[sid].aux_buf = b;
-    }
-    if (std::getenv("SIGOPS_DEBUG_PLAN")) {
-        const Stage& S = stages[sid];
-        std::string a[2];
-        for (int w = 0; w < 2; ++w)
-            a[w] = !row ? "the constant " + std::to_string(w ? nodes[ni].nd.d1 : nodes[ni].nd.d0)
-                        : std::string(S.side[w].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[w].pitch == 0 ? ", one row for every channel" : "");
-        std::fprintf(stderr, "[sigops] Recur2 stage %d: chunk totals a channel %lld, frames [0,%lld) x %d channels, b %s, a1 %s, a2 %s\n", sid, (long long)cumsum_totals(need), (long long)need, nch,
-                     S.pw_step >= 0 ? "materialised by a pointwise step" : S.in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place", a[0].c_str(), a[1].c_str());
+        const so_node_t& nd = nodes[ni].nd;
+        const int order = kind == ST_RECUR ? 1 : kind == ST_RECUR2 ? 2 : 0;
+        std::string what = kind == ST_COMB ? "D=" + std::to_string(nd.l0) : "chunk totals a channel " + std::to_string(cumsum_totals(need));
+        if (kind == ST_RECUR) what = std::string(nd.i0 ? "max-decay, " : "affine, ") + what;
+        std::string inputs = std::string(order ? "b " : "x ") + how_read(S);
+        for (int w = 0; w < order; ++w)
+            inputs += std::string(order == 1 ? ", a " : w ? ", a2 " : ", a1 ") +
+                      (!rows ? "the constant " + std::to_string(w ? nd.d1 : nd.d0)
+                             : std::string(S.side[w].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[w].pitch == 0 ? ", one row for every channel" : ""));
+        std::fprintf(stderr, "[sigops] %s stage %d: %s, frames [0,%lld) x %d channels, %s\n", stage_node_kind(nd.kind)->name, sid, what.c_str(), (long long)need, nch, inputs.c_str());
     }
 }
 
@@ -692,7 +650,7 @@ void Plan::process_moving(int sid) {
     const int64_t c0 = base > back ? base - back : 0;
     int64_t c1 = ahead < BIG - need ? need + ahead : BIG;
     if (!isinf_(nodes[xk].len)) c1 = std::min(c1, nodes[xk].len.n);
-    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": " + (stages[sid].kind == ST_MOVSUM ? "Movsum" : stages[sid].kind == ST_MOVRANK ? "Movrank" : "Moving") + " looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
+    if (c1 >= BIG) fail(SO_ERR_LENGTH, "node " + std::to_string(ni) + ": " + stage_node_kind(nodes[ni].nd.kind)->name + " looks " + std::to_string(ahead) + " frames ahead in a signal of infinite length: too many to compute");
     const bool rank = stages[sid].kind == ST_MOVRANK;
     if (rank && !movrank_fits(c1 - c0, back, ahead))
         fail(SO_ERR_UNSUPPORTED, "node " + std::to_string(ni) + ": Movrank takes a window of at most " + std::to_string(kRankHalo + 1) + " frames (" + std::to_string(moving_clamp(back, c1 - c0)) + " before and " +
@@ -706,7 +664,7 @@ void Plan::process_moving(int sid) {
         if (std::getenv("SIGOPS_DEBUG_PLAN"))
             std::fprintf(stderr, "[sigops] Movrank stage %d: rank floor(%.17g (m - 1)) over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, x %s\n", sid, nodes[ni].nd.d0, (long long)back,
                          (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
-                         stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+                         how_read(stages[sid]));
         return;
     }
     const bool sum = stages[sid].kind == ST_MOVSUM;
@@ -719,14 +677,15 @@ void Plan::process_moving(int sid) {
         std::fprintf(stderr, "[sigops] Movsum stage %d: %s over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, %s form (%lld table entries a channel, %d levels), x %s\n", sid,
                      nodes[ni].nd.i0 == 0 ? "sum" : nodes[ni].nd.i0 == 1 ? "mean" : "rms", (long long)back, (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
                      entries > 0 ? "long" : "short", (long long)entries, entries > 0 ? movsum_levels(c0, c1 - c0, back, ahead) : 0,
-                     stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+                     how_read(stages[sid]));
     else if (std::getenv("SIGOPS_DEBUG_PLAN"))
         std::fprintf(stderr, "[sigops] Moving stage %d: %s over [n-%lld, n+%lld], frames [%lld,%lld) from x's [%lld,%lld) x %d channels, %s form, x %s\n", sid,
                      nodes[ni].nd.i0 ? "min" : "max", (long long)back, (long long)ahead, (long long)base, (long long)need, (long long)c0, (long long)c1, nch,
-                     entries > 0 ? "long" : "short", stages[sid].pw_step >= 0 ? "materialised by a pointwise step" : stages[sid].in_array_node >= 0 ? "an array read in place" : "a stage buffer read in place");
+                     entries > 0 ? "long" : "short", how_read(stages[sid]));
 }
 
-// One routine per stage kind.  Each decides the frames its stage computes and consumes (StageSpan), its form and tables,
+// One routine per stage kind; the device-only stage nodes (kStageNodes, plan_impl.h) share three: process_sample_at,
+// process_from_frame_0 (Comb, Cumsum, Recur, Recur2) and process_moving (Moving, Movsum, Movrank).  Each decides the frames its stage computes and consumes (StageSpan), its form and tables,
 // and then binds its input: lower_input, the reference's block-granular check_frames, and the source -- read in place
 // (direct_source), fused into the kernel's loads (carriers, a sine), or materialised by one pointwise step.
 // `stages`, `bufs` and `exprs` may grow while a child is lowered or a pointwise step is emitted: the routines index
@@ -738,9 +697,9 @@ void Plan::process_stage(int sid) {
     case ST_MOVRANK: return process_moving(sid);
     case ST_SAMPLEAT: return process_sample_at(sid);
     case ST_COMB:
-    case ST_CUMSUM: return process_comb(sid);
-    case ST_RECUR: return process_recur(sid);
-    case ST_RECUR2: return process_recur2(sid);
+    case ST_CUMSUM:
+    case ST_RECUR:
+    case ST_RECUR2: return process_from_frame_0(sid);
     case ST_RESAMPLE: return process_resample(sid);
     case ST_SOS: return process_sos(sid);
     default: return process_norm(sid);

@@ -430,31 +430,8 @@ def _streamable(x):
                 "stream does not know yet; not streamable")
     if isinstance(x, S.PaddedSignal) and any(x.pad is p for p in (S.lastframe, S.cycle, S.mirror)):  # (identity: a pad may be an ndarray)
         S.error("BlockStream: lastframe / cycle / mirror padding indexes the end of the input; not streamable")
-    if isinstance(x, S.SampleAtSignal):
-        S.error("BlockStream: SampleAt reads its table at any position, and a stream keeps only a tail of its input "
-                "resident; not streamable")
-    if isinstance(x, S.CombSignal):
-        S.error("BlockStream: Comb / Allpass would have to carry the D frames of its delay line from one push to the "
-                "next, and that is not built; not streamable")
-    if isinstance(x, S.CumsumSignal):
-        S.error("BlockStream: Cumsum / Integrate would have to carry its running sum (and its place in the summation "
-                "tree) from one push to the next, and that is not built; not streamable")
-    if isinstance(x, S.MovingSignal):
-        S.error("BlockStream: MovingMax / MovingMin would have to keep the `back` input frames of its window from one push "
-                "to the next and hold `ahead` output frames back, and that is not built; not streamable")
-    if isinstance(x, S.MovingSumSignal):
-        S.error("BlockStream: MovingSum / MovingMean / MovingRMS would have to keep the `back` input frames of its window from one "
-                "push to the next, hold `ahead` output frames back and keep its place in the summation tree, and that is not "
-                "built; not streamable")
-    if isinstance(x, S.RecurSignal):
-        S.error("BlockStream: Recur / OnePole / Smooth / PeakDecay would have to carry its last value (and its place in the "
-                "tree of the scan) from one push to the next, and that is not built; not streamable")
-    if isinstance(x, S.Recur2Signal):
-        S.error("BlockStream: Recur2 / Resonator / Sweep would have to carry its last two values (and its place in the tree of "
-                "the scan) from one push to the next, and that is not built; not streamable")
-    if isinstance(x, S.MovingRankSignal):
-        S.error("BlockStream: MovingMedian / MovingQuantile would have to keep the `back` input frames of its window from one "
-                "push to the next and hold `ahead` output frames back, and that is not built; not streamable")
+    if isinstance(x, S.StageSignal):
+        S.error(f"BlockStream: {x.family} {x.not_streamable}; not streamable")
     for c in getattr(x, "children", ()) or ():
         _streamable(c)
 

@@ -253,26 +253,9 @@ def _demand(x, n, out, skip=0):
         _demand(x.signal, capped(x.signal, m), out, 0)
     elif isinstance(x, S.NormedSignal):
         _demand(x.signal, S.nframes(x.signal), out, 0)
-    elif isinstance(x, S.SampleAtSignal):
-        # the table whole (any frame of it may be read), the positions for the frames the sink reaches
-        _demand(x.signal, S.nframes(x.signal), out, 0)
-        _demand(x.pos, capped(x.pos, n), out, skip)
-    elif isinstance(x, (S.CombSignal, S.CumsumSignal)):
-        # the recurrence (the sum) starts at frame 0: the frames before a window are computed too
-        _demand(x.signal, capped(x.signal, n), out, 0)
-    elif isinstance(x, (S.RecurSignal, S.Recur2Signal)):
-        # every input from frame 0: the recurrence starts there whatever window reads it
-        for c in x.children:
-            _demand(c, capped(c, n), out, 0)
-    elif isinstance(x, S.MovingSignal):
-        # the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come along
-        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
-    elif isinstance(x, S.MovingSumSignal):
-        # as for MovingSignal: the window of the last frame reaches `ahead` frames further
-        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
-    elif isinstance(x, S.MovingRankSignal):
-        # as for MovingSignal: the window of the last frame reaches `ahead` frames further
-        _demand(x.signal, capped(x.signal, n + x.ahead), out, 0)
+    elif isinstance(x, S.StageSignal):
+        for c, m, sk in x.demand(n, skip):
+            _demand(c, S.nframes(c) if m is None else capped(c, m), out, sk)
     elif isinstance(x, S.RampSignal):
         return
 
@@ -555,53 +538,15 @@ def lower(x, nframes_out=None, rng=None):
             r = common(s, K.NODE_NORMPOWER)
             r.update(children=(c,))
             idx = lw.add(**r)
-        elif isinstance(s, S.SampleAtSignal):
-            kids = (rec(s.signal), rec(s.pos))
-            r = common(s, K.NODE_SAMPLEAT)
-            r.update(i0=(1 if s.relative else 0) | (2 if s.wrap else 0), d0=s.left, d1=s.right, children=kids)
-            if s.interp != "linear":  # ("linear": the node as it always was, i1 = 0)
-                r["i1"] = S.SAMPLEAT_INTERP.index(s.interp)
-            if s.interp == "sinc":  # the rows of h, then the rows of dh (include/sigops.h)
-                tab = np.concatenate([a.ravel() for a in S.sampleat_taps(s.taps, s.cutoff)])
-                lw.keep.append(tab)
-                r.update(i2=s.taps, p0=tab.ctypes.data, s0=int(tab.size), d2=s.cutoff)
-            idx = lw.add(**r)
-        elif isinstance(s, S.CombSignal):
-            c = rec(s.signal)
-            r = common(s, K.NODE_COMB)
-            r.update(l0=s.delay, d0=s.b0, d1=s.bD, d2=s.a, children=(c,))
-            idx = lw.add(**r)
-        elif isinstance(s, S.MovingSignal):
-            c = rec(s.signal)
-            r = common(s, K.NODE_MOVING)
-            r.update(l0=s.back, l1=s.ahead, i0=1 if s.is_min else 0, children=(c,))
-            idx = lw.add(**r)
-        elif isinstance(s, S.MovingSumSignal):
-            c = rec(s.signal)
-            r = common(s, K.NODE_MOVSUM)
-            r.update(l0=s.back, l1=s.ahead, i0=s.op, children=(c,))
-            idx = lw.add(**r)
-        elif isinstance(s, S.MovingRankSignal):
-            c = rec(s.signal)
-            r = common(s, K.NODE_MOVRANK)
-            r.update(l0=s.back, l1=s.ahead, d0=s.q, children=(c,))
-            idx = lw.add(**r)
-        elif isinstance(s, S.CumsumSignal):
-            c = rec(s.signal)
-            r = common(s, K.NODE_CUMSUM)
-            r.update(children=(c,))
-            idx = lw.add(**r)
-        elif isinstance(s, S.RecurSignal):
-            # one child: b, the constant a in d0; two children: (a, b)
+        elif isinstance(s, S.StageSignal):
             kids = tuple(rec(c) for c in s.children)
-            r = common(s, K.NODE_RECUR)
-            r.update(i0=s.op, d0=0.0 if s.a is None else s.a, children=kids)
-            idx = lw.add(**r)
-        elif isinstance(s, S.Recur2Signal):
-            # one child: b, the constants a1 in d0 and a2 in d1; three children: (a1, a2, b)
-            kids = tuple(rec(c) for c in s.children)
-            r = common(s, K.NODE_RECUR2)
-            r.update(d0=s.a1 if s.coefs is None else 0.0, d1=s.a2 if s.coefs is None else 0.0, children=kids)
+            r = common(s, getattr(K, "NODE_" + s.node))
+            for k, v in s.fields().items():
+                if isinstance(v, np.ndarray):  # a table: the node points at it
+                    lw.keep.append(v)
+                    v = v.ctypes.data
+                r[k] = v
+            r["children"] = kids
             idx = lw.add(**r)
         else:
             S.error(f"Value is not a signal: {s!r}")

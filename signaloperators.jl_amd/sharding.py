@@ -28,63 +28,32 @@ def block_range(n, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def _refuse_sample_at(x, what):
-    """a tree with a SampleAt node is not sharded: every rank would need the whole table, and that is not built"""
-    if isinstance(x, S.SampleAtSignal):
-        raise S.ErrorException(f"{what}: sharding a tree that contains SampleAt over several GPUs is not built")
+def _stage_nodes(x, out):
+    """the device-only stage nodes of a tree, parents before children"""
+    if isinstance(x, S.StageSignal):
+        out.append(x)
     for c in getattr(x, "children", ()) or ():
-        _refuse_sample_at(c, what)
+        _stage_nodes(c, out)
+    return out
 
 
 # nodes whose frames depend on every frame before them: a rank cannot start in the middle, and handing the state on is not built
-_FROM_FRAME_0 = ((S.CombSignal, "Comb / Allpass"), (S.CumsumSignal, "Cumsum / Integrate"), (S.RecurSignal, "Recur / OnePole / Smooth / PeakDecay"),
-                 (S.Recur2Signal, "Recur2 / Resonator / Sweep"))
+_FROM_FRAME_0 = tuple((c, c.family) for c in S.StageSignal.__subclasses__() if c.shard_order == 1)
 
 
-def _refuse_from_frame_0(x, what):
-    """a tree with a Comb, a Cumsum, a Recur or a Recur2 node is not sharded: a rank's frames depend on every frame before them"""
-    for cls, name in _FROM_FRAME_0:
-        if isinstance(x, cls):
-            raise S.ErrorException(f"{what}: sharding a tree that contains {name} over several GPUs is not built")
-    for c in getattr(x, "children", ()) or ():
-        _refuse_from_frame_0(c, what)
-
-
-def _refuse_moving(x, what):
-    """a tree with a MovingMax / MovingMin node is not sharded: a rank's window reaches into its neighbours' frames"""
-    if isinstance(x, S.MovingSignal):
-        raise S.ErrorException(f"{what}: sharding a tree that contains MovingMax / MovingMin over several GPUs is not built: a rank "
-                               "would need `back` frames of the rank before it and `ahead` of the one after (a halo exchange)")
-    for c in getattr(x, "children", ()) or ():
-        _refuse_moving(c, what)
-
-
-def _refuse_moving_sum(x, what):
-    """a tree with a MovingSum / MovingMean / MovingRMS node is not sharded: a rank's window reaches into its neighbours' frames"""
-    if isinstance(x, S.MovingSumSignal):
-        raise S.ErrorException(f"{what}: sharding a tree that contains MovingSum / MovingMean / MovingRMS over several GPUs is not built: a "
-                               "rank would need `back` frames of the rank before it and `ahead` of the one after (a halo exchange), "
-                               "summed over the whole signal's tree")
-    for c in getattr(x, "children", ()) or ():
-        _refuse_moving_sum(c, what)
-
-
-def _refuse_moving_rank(x, what):
-    """a tree with a MovingMedian / MovingQuantile node is not sharded: a rank's window reaches into its neighbours' frames"""
-    if isinstance(x, S.MovingRankSignal):
-        raise S.ErrorException(f"{what}: sharding a tree that contains MovingMedian / MovingQuantile over several GPUs is not built: a "
-                               "rank would need `back` frames of the rank before it and `ahead` of the one after (a halo exchange)")
-    for c in getattr(x, "children", ()) or ():
-        _refuse_moving_rank(c, what)
+def _refuse_stage_nodes(x, what):
+    """a tree with a device-only stage node is not sharded: every rank would need the whole table (SampleAt), a rank's
+    frames depend on every frame before them (`_FROM_FRAME_0`), or its window reaches into its neighbours' frames (the
+    Moving families).  Of several families the one of the lowest `shard_order` is named, the first met among equals."""
+    found = _stage_nodes(x, [])
+    if found:
+        s = min(found, key=lambda s: s.shard_order)
+        raise S.ErrorException(f"{what}: sharding a tree that contains {s.family} over several GPUs is not built{s.shard_tail}")
 
 
 def shard_append(x, rank, world):
     """-> (sub-signal for this rank or None, first output frame, number of frames)"""
-    _refuse_sample_at(x, "shard_append")
-    _refuse_from_frame_0(x, "shard_append")
-    _refuse_moving(x, "shard_append")
-    _refuse_moving_sum(x, "shard_append")
-    _refuse_moving_rank(x, "shard_append")
+    _refuse_stage_nodes(x, "shard_append")
     if not isinstance(x, S.AppendSignals):
         raise S.ErrorException("shard_append needs an Append(...) root")
     kids = x.signals
@@ -106,11 +75,7 @@ def shard_time(x, rank, world, align=1):
     from .units import frames
 
     x = S._assignal(x)
-    _refuse_sample_at(x, "shard_time")
-    _refuse_from_frame_0(x, "shard_time")
-    _refuse_moving(x, "shard_time")
-    _refuse_moving_sum(x, "shard_time")
-    _refuse_moving_rank(x, "shard_time")
+    _refuse_stage_nodes(x, "shard_time")
     n = S.nframes(x)
     if n is None or S.isknowninf(n):
         raise S.ErrorException("shard_time needs a signal of known, finite length")
@@ -127,11 +92,7 @@ def shard_time(x, rank, world, align=1):
 def shard_channels(x, rank, world):
     """channel slab [c0,c1) of a signal whose channels are independent"""
     x = S._assignal(x)
-    _refuse_sample_at(x, "shard_channels")
-    _refuse_from_frame_0(x, "shard_channels")
-    _refuse_moving(x, "shard_channels")
-    _refuse_moving_sum(x, "shard_channels")
-    _refuse_moving_rank(x, "shard_channels")
+    _refuse_stage_nodes(x, "shard_channels")
     c0, c1 = block_range(x.nch, rank, world)
     if c1 <= c0:
         return None, c0, c1

@@ -508,13 +508,66 @@ class FilteredSignal(WrappedSignal):
         return self.signal.duration()
 
 
-class SampleAtSignal(AbstractSignal):
+def _need_x(self, n, skip):
+    """demand rule: `x` up to frame n, from frame 0 (the recurrence, the sum, starts there: the frames before a window are
+    computed too)"""
+    return [(self.signal, n, 0)]
+
+
+def _need_every_child(self, n, skip):
+    """demand rule: every input up to frame n, from frame 0 (the recurrence starts there whatever window reads it)"""
+    return [(c, n, 0) for c in self.children]
+
+
+def _need_x_ahead(self, n, skip):
+    """demand rule: the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come
+    along"""
+    return [(self.signal, n + self.ahead, 0)]
+
+
+class StageSignal(AbstractSignal):
+    """A node the device computes in a stage of its own and nothing else knows how to compute (no reference counterpart;
+    DESIGN.md "Where a device-only node lives").  `ToFramerate`, `lowering._demand`, `lowering.lower`, `engine._streamable`
+    and `sharding` each treat all of them in one branch, from what a subclass declares:
+
+    * `family`: the name refusals print;
+    * `rebuild(f)`: the node of the same class and parameters with `f` applied to every child that takes a missing frame
+      rate (a rate the node has is resampled like any computed signal's);
+    * `demand(n, skip)`: `(child, frames, skip)` for every child the first `n` frames read -- `frames` is capped at the
+      child's length, `None` is the child whole;
+    * `node` and `fields()`: the `SO_NODE_*` kind by name and the node's `i* / l* / d* / p* / s*` fields (include/sigops.h;
+      an array stands for the pointer to it and is kept alive by the lowering);
+    * `not_streamable`: why a `BlockStream` refuses it; `shard_order`, `shard_tail`: where its multi-GPU refusal stands
+      among those of a tree that holds several families (lowest first, the first one met among equals), and what the
+      refusal adds after "is not built"."""
+
+    evaltrait = "computed"
+    shard_tail = ""
+
+    def _like(self, timed, nch, dtype):
+        """the length, duration and frame rate of the child `timed`"""
+        self._timed = timed
+        self.fs = timed.fs
+        self.nch = nch
+        self.dtype = dtype
+
+    def nframes_helper(self):
+        return self._timed.nframes_helper()
+
+    def duration(self):
+        return self._timed.duration()
+
+
+class SampleAtSignal(StageSignal):
     """`SampleAt(x, pos)`: the table `x` read at the positions the signal `pos` gives, with linear interpolation --
     `interp="cubic"`: Catmull-Rom; `interp="sinc"`: `taps` taps of a Kaiser-windowed sinc with its pass-band edge at
     `cutoff` of the table's Nyquist -- (no reference counterpart; include/sigops.h SO_NODE_SAMPLEAT, DESIGN.md
     "SampleAt").  It has the length and frame rate of `pos`, the channels of `x`, and is Float64 like `np.interp`."""
 
-    evaltrait = "computed"
+    family = "SampleAt"
+    node = "SAMPLEAT"
+    not_streamable = "reads its table at any position, and a stream keeps only a tail of its input resident"
+    shard_order = 0
 
     def __init__(self, x, pos, left=0.0, right=0.0, relative=False, wrap=False, interp="linear", taps=0, cutoff=0.0):
         self.interp = interp  # "linear" | "cubic" | "sinc"
@@ -527,23 +580,37 @@ class SampleAtSignal(AbstractSignal):
         self.right = float(right)
         self.relative = bool(relative)
         self.wrap = bool(wrap)
-        self.fs = pos.fs
-        self.nch = x.nch
-        self.dtype = F64
+        self._like(pos, x.nch, F64)
 
-    def nframes_helper(self):
-        return self.pos.nframes_helper()
+    def rebuild(self, f):
+        # a rate the positions do not have yet is theirs to take (never the table's: it is a table of frames, its own
+        # rate is not consulted)
+        return SampleAtSignal(self.signal, f(self.pos), self.left, self.right, self.relative, self.wrap, self.interp, self.taps, self.cutoff)
 
-    def duration(self):
-        return self.pos.duration()
+    def demand(self, n, skip):
+        # the table whole (any frame of it may be read), the positions for the frames the sink reaches
+        return [(self.signal, None, 0), (self.pos, n, skip)]
+
+    def fields(self):
+        r = dict(i0=(1 if self.relative else 0) | (2 if self.wrap else 0), d0=self.left, d1=self.right)
+        if self.interp != "linear":  # ("linear": the node as it always was, i1 = 0)
+            r["i1"] = SAMPLEAT_INTERP.index(self.interp)
+        if self.interp == "sinc":  # the rows of h, then the rows of dh (include/sigops.h)
+            tab = np.concatenate([a.ravel() for a in sampleat_taps(self.taps, self.cutoff)])
+            r.update(i2=self.taps, p0=tab, s0=int(tab.size), d2=self.cutoff)
+        return r
 
 
-class CombSignal(AbstractSignal):
+class CombSignal(StageSignal):
     """`Comb(x, d, g)` / `Allpass(x, d, g)`: a feedback delay line of `delay` frames over `x`,
     `y[n] = (b0 x[n] + bD x[n - D]) + a y[n - D]` (no reference counterpart; include/sigops.h SO_NODE_COMB, DESIGN.md
     "Comb").  It has the length, frame rate and channels of `x` and is Float64."""
 
-    evaltrait = "computed"
+    family = "Comb / Allpass"
+    node = "COMB"
+    not_streamable = "would have to carry the D frames of its delay line from one push to the next, and that is not built"
+    shard_order = 1  # its frames depend on every frame before them: a rank cannot start in the middle, and handing the state on is not built
+    demand = _need_x
 
     def __init__(self, x, delay, b0, bD, a):
         self.signal = x
@@ -552,44 +619,55 @@ class CombSignal(AbstractSignal):
         self.b0 = float(b0)
         self.bD = float(bD)
         self.a = float(a)
-        self.fs = x.fs
-        self.nch = x.nch
-        self.dtype = F64
+        self._like(x, x.nch, F64)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):
+        # the delay is a number of frames (a time was converted with the rate x had): a missing rate goes to x
+        return CombSignal(f(self.signal), self.delay, self.b0, self.bD, self.a)
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):
+        return dict(l0=self.delay, d0=self.b0, d1=self.bD, d2=self.a)
 
 
-class CumsumSignal(AbstractSignal):
+class CumsumSignal(StageSignal):
     """`Cumsum(x)`: the running sum of `x` per channel, summed over one fixed tree (no reference counterpart;
     include/sigops.h SO_NODE_CUMSUM, DESIGN.md "Cumsum").  It has the length, frame rate and channels of `x` and is
     Float64."""
 
-    evaltrait = "computed"
+    family = "Cumsum / Integrate"
+    node = "CUMSUM"
+    not_streamable = ("would have to carry its running sum (and its place in the summation tree) from one push to the next, "
+                      "and that is not built")
+    shard_order = 1  # (as Comb)
+    demand = _need_x
 
     def __init__(self, x):
         self.signal = x
         self.children = (x,)
-        self.fs = x.fs
-        self.nch = x.nch
-        self.dtype = F64
+        self._like(x, x.nch, F64)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):  # the sum runs over frames, whatever rate they have
+        return CumsumSignal(f(self.signal))
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):
+        return {}
 
 
-class MovingSignal(AbstractSignal):
+_HALO = ": a rank would need `back` frames of the rank before it and `ahead` of the one after (a halo exchange)"
+
+
+class MovingSignal(StageSignal):
     """`MovingMax(x, w)` / `MovingMin(x, w)`: per channel the greatest (least) sample of `x` over the frames
     `[n - back, n + ahead]`, clipped to the signal (no reference counterpart; include/sigops.h SO_NODE_MOVING, DESIGN.md
     "Moving extrema").  It has the length, frame rate, channels and sample type of `x`."""
 
-    evaltrait = "computed"
+    family = "MovingMax / MovingMin"
+    node = "MOVING"
+    not_streamable = ("would have to keep the `back` input frames of its window from one push to the next and hold `ahead` "
+                      "output frames back, and that is not built")
+    shard_order = 2  # a rank's window reaches into its neighbours' frames
+    shard_tail = _HALO
+    demand = _need_x_ahead
 
     def __init__(self, x, back, ahead, is_min):
         self.signal = x
@@ -597,24 +675,28 @@ class MovingSignal(AbstractSignal):
         self.back = int(back)
         self.ahead = int(ahead)
         self.is_min = bool(is_min)
-        self.fs = x.fs
-        self.nch = x.nch
-        self.dtype = x.dtype
+        self._like(x, x.nch, x.dtype)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):  # the window is counted in frames, whatever rate they have
+        return MovingSignal(f(self.signal), self.back, self.ahead, self.is_min)
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):
+        return dict(l0=self.back, l1=self.ahead, i0=1 if self.is_min else 0)
 
 
-class MovingSumSignal(AbstractSignal):
+class MovingSumSignal(StageSignal):
     """`MovingSum(x, w)` / `MovingMean(x, w)` / `MovingRMS(x, w)`: per channel the sum (the mean, the root of the mean square)
     of `x` over the frames `[n - back, n + ahead]`, clipped to the signal, over one fixed summation tree (no reference
     counterpart; include/sigops.h SO_NODE_MOVSUM, DESIGN.md "Moving sums").  It has the length, frame rate and channels of
     `x` and is Float64.  `op`: 0 sum, 1 mean, 2 rms."""
 
-    evaltrait = "computed"
+    family = "MovingSum / MovingMean / MovingRMS"
+    node = "MOVSUM"
+    not_streamable = ("would have to keep the `back` input frames of its window from one push to the next, hold `ahead` output "
+                      "frames back and keep its place in the summation tree, and that is not built")
+    shard_order = 3  # (as Moving)
+    shard_tail = _HALO + ", summed over the whole signal's tree"
+    demand = _need_x_ahead
 
     def __init__(self, x, back, ahead, op):
         self.signal = x
@@ -622,23 +704,26 @@ class MovingSumSignal(AbstractSignal):
         self.back = int(back)
         self.ahead = int(ahead)
         self.op = int(op)
-        self.fs = x.fs
-        self.nch = x.nch
-        self.dtype = F64
+        self._like(x, x.nch, F64)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):
+        return MovingSumSignal(f(self.signal), self.back, self.ahead, self.op)
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):
+        return dict(l0=self.back, l1=self.ahead, i0=self.op)
 
 
-class MovingRankSignal(AbstractSignal):
+class MovingRankSignal(StageSignal):
     """`MovingMedian(x, w)` / `MovingQuantile(x, w, q)`: per channel the sample of rank `floor(q (m - 1))` among the `m` samples
     of `x` over the frames `[n - back, n + ahead]`, clipped to the signal (no reference counterpart; include/sigops.h
     SO_NODE_MOVRANK, DESIGN.md "Moving ranks").  It has the length, frame rate, channels and sample type of `x`."""
 
-    evaltrait = "computed"
+    family = "MovingMedian / MovingQuantile"
+    node = "MOVRANK"
+    not_streamable = MovingSignal.not_streamable
+    shard_order = 4  # (as Moving)
+    shard_tail = _HALO
+    demand = _need_x_ahead
 
     def __init__(self, x, back, ahead, q):
         self.signal = x
@@ -646,24 +731,27 @@ class MovingRankSignal(AbstractSignal):
         self.back = int(back)
         self.ahead = int(ahead)
         self.q = float(q)
-        self.fs = x.fs
-        self.nch = x.nch
-        self.dtype = x.dtype
+        self._like(x, x.nch, x.dtype)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):
+        return MovingRankSignal(f(self.signal), self.back, self.ahead, self.q)
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):
+        return dict(l0=self.back, l1=self.ahead, d0=self.q)
 
 
-class RecurSignal(AbstractSignal):
+class RecurSignal(StageSignal):
     """`Recur(a, b)` / `OnePole` / `Smooth` / `PeakDecay`: per channel the first-order scan `y[n] = J(a[n], y[n-1], b[n])`,
     `y[0] = b[0]`, over one fixed tree (no reference counterpart; include/sigops.h SO_NODE_RECUR, DESIGN.md "Recur").
     `op` 0: `J = a y + b`; `op` 1: `J = max(a y, b)`.  The coefficient is the number `a` (then `coef` is None) or the signal
     `coef` of one channel or of `b`'s.  It has the length, frame rate and channels of `b` and is Float64."""
 
-    evaltrait = "computed"
+    family = "Recur / OnePole / Smooth / PeakDecay"
+    node = "RECUR"
+    not_streamable = ("would have to carry its last value (and its place in the tree of the scan) from one push to the next, "
+                      "and that is not built")
+    shard_order = 1  # (as Comb)
+    demand = _need_every_child
 
     def __init__(self, a, b, op):
         self.signal = b
@@ -674,25 +762,28 @@ class RecurSignal(AbstractSignal):
             self.coef, self.a = None, float(a)
             self.children = (b,)
         self.op = int(op)
-        self.fs = b.fs
-        self.nch = b.nch
-        self.dtype = F64
+        self._like(b, b.nch, F64)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):  # the recurrence runs over frames, whatever rate they have
+        return RecurSignal(self.a if self.coef is None else f(self.coef), f(self.signal), self.op)
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):  # one child: b, the constant a in d0; two children: (a, b)
+        return dict(i0=self.op, d0=0.0 if self.a is None else self.a)
 
 
-class Recur2Signal(AbstractSignal):
+class Recur2Signal(StageSignal):
     """`Recur2(a1, a2, b)` / `Resonator` / `Sweep`: per channel the second-order scan
     `y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n]`, `y[0] = b[0]`, over one fixed tree (no reference counterpart;
     include/sigops.h SO_NODE_RECUR2, DESIGN.md "Recur2").  The coefficients are the numbers `a1`, `a2` (then `coefs` is None)
     or the two signals `coefs`, each of one channel or of `b`'s.  It has the length, frame rate and channels of `b` and is
     Float64."""
 
-    evaltrait = "computed"
+    family = "Recur2 / Resonator / Sweep"
+    node = "RECUR2"
+    not_streamable = ("would have to carry its last two values (and its place in the tree of the scan) from one push to the "
+                      "next, and that is not built")
+    shard_order = 1  # (as Comb)
+    demand = _need_every_child
 
     def __init__(self, a1, a2, b):
         self.signal = b
@@ -702,15 +793,15 @@ class Recur2Signal(AbstractSignal):
         else:
             self.coefs, self.a1, self.a2 = None, float(a1), float(a2)
             self.children = (b,)
-        self.fs = b.fs
-        self.nch = b.nch
-        self.dtype = F64
+        self._like(b, b.nch, F64)
 
-    def nframes_helper(self):
-        return self.signal.nframes_helper()
+    def rebuild(self, f):
+        if self.coefs is None:
+            return Recur2Signal(self.a1, self.a2, f(self.signal))
+        return Recur2Signal(f(self.coefs[0]), f(self.coefs[1]), f(self.signal))
 
-    def duration(self):
-        return self.signal.duration()
+    def fields(self):  # one child: b, the constants a1 in d0 and a2 in d1; three children: (a1, a2, b)
+        return dict(d0=self.a1 if self.coefs is None else 0.0, d1=self.a2 if self.coefs is None else 0.0)
 
 
 # map functions (src/mapsignal.jl:308,333,360,389; src/reformatting.jl:148-184)
@@ -1070,44 +1161,11 @@ def ToFramerate(x, fs=None, blocksize=default_blocksize):
         if known and x.fs != x.signal.fs:
             return _resample(x.signal, fs, bs)
         return FilteredSignal(ToFramerate(x.signal, fs, bs), x.fn, x.blocksize, fs)
-    if isinstance(x, SampleAtSignal):
-        # a rate the positions do not have yet is theirs to take (never the table's: it is a table of frames, its own
-        # rate is not consulted); a result that has a rate is resampled like any computed signal
+    if isinstance(x, StageSignal):
+        # a result that has a rate is resampled like any computed signal; a missing rate goes to the children that take one
         if known:
             return _resample(x, fs, bs)
-        return SampleAtSignal(x.signal, ToFramerate(x.pos, fs, bs), x.left, x.right, x.relative, x.wrap, x.interp, x.taps, x.cutoff)
-    if isinstance(x, CombSignal):
-        # the delay is a number of frames (a time was converted with the rate x had): a missing rate goes to x, a
-        # result that has a rate is resampled like any computed signal
-        if known:
-            return _resample(x, fs, bs)
-        return CombSignal(ToFramerate(x.signal, fs, bs), x.delay, x.b0, x.bD, x.a)
-    if isinstance(x, CumsumSignal):  # Comb's two rules: the sum runs over frames, whatever rate they have
-        if known:
-            return _resample(x, fs, bs)
-        return CumsumSignal(ToFramerate(x.signal, fs, bs))
-    if isinstance(x, MovingSignal):  # Comb's two rules: the window is counted in frames, whatever rate they have
-        if known:
-            return _resample(x, fs, bs)
-        return MovingSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.is_min)
-    if isinstance(x, MovingSumSignal):  # the same two rules
-        if known:
-            return _resample(x, fs, bs)
-        return MovingSumSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.op)
-    if isinstance(x, MovingRankSignal):  # the same two rules
-        if known:
-            return _resample(x, fs, bs)
-        return MovingRankSignal(ToFramerate(x.signal, fs, bs), x.back, x.ahead, x.q)
-    if isinstance(x, RecurSignal):  # Comb's two rules: the recurrence runs over frames, whatever rate they have
-        if known:
-            return _resample(x, fs, bs)
-        return RecurSignal(x.a if x.coef is None else ToFramerate(x.coef, fs, bs), ToFramerate(x.signal, fs, bs), x.op)
-    if isinstance(x, Recur2Signal):  # Recur's two rules
-        if known:
-            return _resample(x, fs, bs)
-        if x.coefs is None:
-            return Recur2Signal(x.a1, x.a2, ToFramerate(x.signal, fs, bs))
-        return Recur2Signal(ToFramerate(x.coefs[0], fs, bs), ToFramerate(x.coefs[1], fs, bs), ToFramerate(x.signal, fs, bs))
+        return x.rebuild(lambda c: ToFramerate(c, fs, bs))
     computed = x.evaltrait == "computed"
     if known and not computed:  # generic DataSignal method :88-90
         return _resample(x, fs, bs)
