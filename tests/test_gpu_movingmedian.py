@@ -238,6 +238,9 @@ def test_windows_and_streams_equal_the_whole_sink(W, ahead, q):
 
 # ---- 6. composites ----------------------------------------------------------------------------------------------------------
 def test_under_append_pad_and_mix():
+    """two channels and an even first length: the second window of `Append of two` is 16-byte aligned.  Windows at odd frames
+    and at every 4-byte phase of a Float32 result, 1 and 3 channels, several readers, windows, blocks and random trees are in
+    tests/test_gpu_node_trees.py, against tests/tree_ref.py `evaluate`, which has the node"""
     N = T + 50
     x, y = halves(N, 2, seed=6), halves(700, 2, seed=7)
     xs, ys = so.Signal(x, FS), so.Signal(y, FS)

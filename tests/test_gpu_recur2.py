@@ -273,8 +273,10 @@ def test_consumers_behind_the_node():
 
 
 def test_the_node_under_and_over_append_pad_and_mix():
-    """tests/tree_ref.py `evaluate` knows the structural nodes and not this one: under them the node is replaced by an array
-    of its definition's values, over them the child is evaluated and handed to the definition"""
+    """written when tests/tree_ref.py `evaluate` knew the structural nodes and not this one, and kept as it was: under them
+    the node is replaced by an array of its definition's values, over them the child is evaluated and handed to the
+    definition.  `evaluate` has the node now, and tests/test_gpu_node_trees.py holds it to the whole composite matrix: windows
+    at odd frames of every result form, 1 and 3 channels, several readers, windows, blocks and random trees"""
     n = CH + T + 9
     x, z = signal(n, 2), signal(700, 2, seed=3)
     a1, a2 = coef("reson", n + 700, 1)

@@ -1,10 +1,11 @@
-"""A NumPy evaluator for composite trees of the device-only nodes (`SampleAt`, `Comb` / `Allpass`, `Cumsum`, `MovingMax` /
-`MovingMin`, `MovingSum` / `MovingMean` / `MovingRMS`, `Recur` / `PeakDecay`) under the structural operators, and the
-generator of random trees of that grammar.  `evaluate(tree)` walks the Python signal objects and never calls the engine:
-the structural operators are slices and concatenations, `Mix` and `Amplify` are single IEEE additions and multiplications,
-and every device-only node is evaluated by its own definition (tests/*_ref.py), so every tree of the grammar has ONE
-expected value, bit for bit.  tests/test_tree_ref_host.py holds the structural part to the CPU oracle bit for bit;
-tests/test_gpu_node_trees.py holds the device to `evaluate`.
+"""A NumPy evaluator for composite trees of the device-only nodes (`SampleAt` with linear, cubic and windowed-sinc
+interpolation, `Comb` / `Allpass`, `Cumsum`, `MovingMax` / `MovingMin`, `MovingSum` / `MovingMean` / `MovingRMS`, `Recur` /
+`PeakDecay`, `Recur2`, `MovingMedian` / `MovingQuantile`) under the structural operators, and the generator of random trees
+of that grammar.  `evaluate(tree)` walks the Python signal objects and never calls the engine: the structural operators are
+slices and concatenations, `Mix` and `Amplify` are single IEEE additions and multiplications, and every device-only node
+is evaluated by its own definition (tests/*_ref.py), so every tree of the grammar has ONE expected value, bit for bit.
+tests/test_tree_ref_host.py holds the structural part to the CPU oracle bit for bit and every node's branch to a direct
+call of its definition; tests/test_gpu_node_trees.py holds the device to `evaluate`.
 
 The grammar (every signal at one frame rate, FS = 10 kHz):
 
@@ -14,14 +15,27 @@ The grammar (every signal at one frame rate, FS = 10 kHz):
                 `ToChannels` (mono -> n), `Mix(x, y)`, `Mix(x, number)`, `Amplify(x, y)`, `Amplify(x, number)`: unequal
                 lengths (the shorter operand is extended with 0.0 under `Mix` and 1.0 under `Amplify`, and the operation
                 is carried out there too: -0.0 + 0.0 is +0.0) and mono against n channels
-    nodes       the six families above, their parameters as their own test files map them
+    nodes       nine families (`FAMILIES`), their parameters as their own test files map them: the six of `SIX`, and
+                "Recur2" (constants or two coefficient rows: three inputs), "MovingRank" (it keeps the sample type, as the
+                extrema do: a Float32 one stands where a Float32 extremum may) and "SampleAtFir", a `SampleAt` whose
+                `interp` is "cubic" or "sinc" ("SampleAt" is the linear one)
+
+The random trees come in two sets.  `SEEDS` draw from `SIX`, the families the generator began with, and their trees are
+pinned by digest (tests/golden/tree_seeds.json): a change to the generator must not move them.  `SEEDS_ALL` draw from all
+nine.
 
 Outside the grammar, deliberately: generators (`sin` on the device is not NumPy's `sin` bit for bit), `Ramp`, `FadeTo`,
-`Filt`, `ToFramerate`, `Normpower`, Float32 arithmetic, `OnePole` / `Smooth` / `Integrate` (a scaling map over the node).
+`Filt`, `ToFramerate`, `Normpower`, Float32 arithmetic, `OnePole` / `Smooth` / `Integrate` (a scaling map over the node) and
+`Resonator` / `Sweep` (their coefficient maps use the device's `cos` and `exp`, which are not NumPy's bit for bit: with
+constants they are `Recur2` over a scaled input, and tests/test_gpu_recur2.py holds them).
 
 Refused by design, and therefore not generated: `Pad(x, cycle)` and `Pad(x, mirror)` over anything but an array leaf
 (the engine and the oracle raise the reference's "indexing pad function" error: the pad indexes its child, and only an
-array can be indexed); signals of no frames (`After` never takes a whole signal, `Until` at least one frame)."""
+array can be indexed); signals of no frames (`After` never takes a whole signal, `Until` at least one frame); a moving
+rank whose window is longer than the 1025 frames that are built."""
+import hashlib
+import math
+
 import numpy as np
 
 import sigops_amd as so
@@ -30,13 +44,18 @@ from sigops_amd import signals as S
 from comb_ref import DELAYS, comb_ref
 from cumsum_ref import CH, L, T, cumsum_ref
 from moving_ref import moving_ref
+from movingmedian_ref import movrank_ref
 from movingsum_ref import B, TILE, movingsum_ref
+from recur2_ref import recur2_ref
 from recur_ref import recur_ref
+from sampleat_interp_ref import sampleat_interp
 from sampleat_ref import sampleat_np
 
 FS = 10 * so.kHz
-NODE_TYPES = (S.SampleAtSignal, S.CombSignal, S.CumsumSignal, S.MovingSignal, S.MovingSumSignal, S.RecurSignal)
-FAMILIES = ("SampleAt", "Comb", "Cumsum", "Moving", "MovingSum", "Recur")
+NODE_TYPES = (S.SampleAtSignal, S.CombSignal, S.CumsumSignal, S.MovingSignal, S.MovingSumSignal, S.RecurSignal, S.Recur2Signal,
+              S.MovingRankSignal)
+SIX = ("SampleAt", "Comb", "Cumsum", "Moving", "MovingSum", "Recur")  # what the generator began with: the trees of `SEEDS`
+FAMILIES = SIX + ("Recur2", "MovingRank", "SampleAtFir")
 
 
 # ---- the evaluator -----------------------------------------------------------------------------------------------------
@@ -73,6 +92,9 @@ def _extend(base, n, pad, child):
 
 def _ev(x, n, memo):
     """the first n frames of x (all of a finite x for n None), frames x channels in x's sample type"""
+    if n is not None and isinstance(x, NODE_TYPES) and _finite_len(x) is not None:
+        assert n <= _finite_len(x)
+        return _ev(x, None, memo)[:n]  # (a node's first n frames are the first n of all of them: one call of its definition)
     key = (id(x), n)
     if key not in memo:
         memo[key] = _ev1(x, n, memo)
@@ -120,21 +142,31 @@ def _ev1(x, n, memo):
         assert acc.dtype == x.dtype
         return acc
     if isinstance(x, S.SampleAtSignal):
-        return sampleat_np(_ev(x.signal, None, memo), _ev(x.pos, n, memo), x.left, x.right, x.relative, x.wrap)
+        table, pos = _ev(x.signal, None, memo), _ev(x.pos, n, memo)
+        if x.interp == "linear":
+            return sampleat_np(table, pos, x.left, x.right, x.relative, x.wrap)
+        return sampleat_interp(table, pos, x.interp, x.left, x.right, x.relative, x.wrap, taps=x.taps, cutoff=x.cutoff)
     if isinstance(x, S.CombSignal):
         return comb_ref(_ev(x.signal, None, memo), x.delay, x.b0, x.bD, x.a)[:n]
     if isinstance(x, S.CumsumSignal):
         return cumsum_ref(_ev(x.signal, None, memo))[:n]
-    if isinstance(x, (S.MovingSignal, S.MovingSumSignal)):
+    if isinstance(x, (S.MovingSignal, S.MovingSumSignal, S.MovingRankSignal)):
         # (an infinite child: the window is clipped at the front only, and `ahead` more frames are all frame n - 1 reaches)
         child = _ev(x.signal, None if _finite_len(x.signal) is not None else n + x.ahead, memo)
         if isinstance(x, S.MovingSignal):
             return moving_ref(child, x.back, x.ahead, x.is_min)[:n]
+        if isinstance(x, S.MovingRankSignal):
+            return movrank_ref(child, x.back, x.ahead, x.q)[:n]
         return movingsum_ref(child, x.back, x.ahead, x.op)[:n]
     if isinstance(x, S.RecurSignal):
         b = _ev(x.signal, None, memo)
         a = x.a if x.coef is None else _ev(x.coef, b.shape[0], memo)
         return recur_ref(a, b, x.op)[:n]
+    if isinstance(x, S.Recur2Signal):
+        b = _ev(x.signal, None, memo)
+        # (a coefficient row may have one channel against b's, and more frames than b: the first of them are read)
+        a1, a2 = (x.a1, x.a2) if x.coefs is None else (_ev(c, b.shape[0], memo) for c in x.coefs)
+        return recur2_ref(a1, a2, b)[:n]
     raise AssertionError(f"outside the grammar: {type(x).__name__}")
 
 
@@ -148,7 +180,20 @@ def evaluate(tree):
 
 # ---- what a tree holds -------------------------------------------------------------------------------------------------
 def family(x):
-    return FAMILIES[NODE_TYPES.index(type(x))] if isinstance(x, NODE_TYPES) else None
+    if not isinstance(x, NODE_TYPES):
+        return None
+    if isinstance(x, S.SampleAtSignal) and x.interp != "linear":
+        return "SampleAtFir"
+    return (SIX + ("Recur2", "MovingRank"))[NODE_TYPES.index(type(x))]
+
+
+def digest(a):
+    """sha256 over the sample type, the shape and the bytes (planar) of an array"""
+    a = np.asfortranarray(a)
+    h = hashlib.sha256()
+    h.update(f"{a.dtype.str} {a.shape}".encode())
+    h.update(a.tobytes(order="F"))
+    return h.hexdigest()
 
 
 def _through_cuts(x):
@@ -192,14 +237,39 @@ def census(tree):
     return fams, places
 
 
+def placed(tree):
+    """-> the set of (family, placement) of the tree's nodes, the placements as `census` has them, each told of the node
+    itself: the child of the root `Append`, the node over an `Append` or a `Pad`, the node behind the `Pad`, the node read twice"""
+    tree = S._assignal(tree)
+    out = set()
+    if isinstance(tree, S.AppendSignals):
+        out.update((family(c), "under_root_append") for c in tree.signals if isinstance(c, NODE_TYPES))
+    for x, readers in walk(tree):
+        if isinstance(x, NODE_TYPES):
+            if readers >= 2:
+                out.add((family(x), "two_readers"))
+            if any(isinstance(_through_cuts(c), (S.AppendSignals, S.PaddedSignal)) for c in x.children):
+                out.add((family(x), "over_append_or_pad"))
+        if isinstance(x, S.PaddedSignal) and isinstance(_through_cuts(x.signal), NODE_TYPES):
+            out.add((family(_through_cuts(x.signal)), "pad_behind_node"))
+    return out
+
+
 # ---- the generator -----------------------------------------------------------------------------------------------------
-SEEDS = (11, 12, 13, 14, 15)       # the seeds of test_random_node_trees
+SEEDS = (11, 12, 13, 14, 15)       # the seeds of test_random_node_trees: trees of `SIX`
+SEEDS_ALL = (21, 22, 23, 24, 25)   # and these: trees of all of `FAMILIES`
 TREES_PER_SEED = 20
 SHORT = [1, 2, L - 1, L, L + 1, 255, T - 1, T, T + 1, TILE - 1, TILE, TILE + 1, 2 * TILE + 77]
 LONG = [CH - 1, CH, CH + 1, CH + T + 77]
 MARKS = [1, L - 1, L, L + 1, T - 1, T, T + 1, TILE - 1, TILE, TILE + 1, CH - 1, CH, CH + 1]
 WINDOWS = [1, 2, 3, 16, 17, 33, 480, B, B + 1, B + 2, TILE + 1, TILE + 2, 2 * TILE + 1]
 NUMBERS = [0.5, -1.25, 2.5, 1.0, 0.0, -0.0]
+RANK_WINDOWS = [1, 2, 3, 5, 16, 17, 33, 65, 257, 1024, 1025]  # 1025: the longest window that is built
+RANK_Q = [0.0, 0.1, 0.5, 0.9, 1.0]
+RANK_LONG = 4 * T   # over more frames than this, a window above 257 is kept one time in six (the definition sorts every window)
+STABLE_PAIRS = [(1.8, -0.9), (1.2, -0.5), (0.0, 0.25), (-0.5, 0.0), (0.0, 0.0)]  # `Recur2`'s constants: poles inside the circle
+FIR_KINDS = [dict(interp="cubic"), dict(interp="sinc"), dict(interp="sinc", taps=4), dict(interp="sinc", taps=64),
+             dict(interp="sinc", taps=10, cutoff=0.5)]
 
 
 def _length(rng):
@@ -245,14 +315,17 @@ def _pad(rng, x, indexing=False):
 
 
 class _Gen:
-    def __init__(self, rng, nodes=True):
+    def __init__(self, rng, nodes=True, families=SIX):
+        """with the default families every draw is what it was when there were six: the trees of `SEEDS` stay"""
         self.rng = rng
         self.nodes = nodes
+        self.families = tuple(families)
 
-    # -- Float32: nothing but structure and the extrema, which keep the type
+    # -- Float32: nothing but structure, the extrema and the moving ranks, which keep the type
     def f32(self, nch, depth):
         rng = self.rng
-        how = rng.integers(0, 5 if self.nodes else 4) if depth > 0 else 0
+        kinds = 4 + (1 + ("MovingRank" in self.families) if self.nodes else 0)
+        how = rng.integers(0, kinds) if depth > 0 else 0
         if how == 0:
             return _leaf(rng, nch, np.float32)
         if how == 1:
@@ -262,13 +335,46 @@ class _Gen:
             return _pad(rng, x, isinstance(x, S.ArraySig))
         if how == 3:
             return so.Append(*[self.f32(nch, depth - 1) for _ in range(rng.integers(2, 4))])
-        return self.moving(self.f32(nch, depth - 1))
+        return (self.moving if how == 4 else self.rank)(self.f32(nch, depth - 1))
 
     # -- the nodes
     def moving(self, x):
         rng = self.rng
         w = int(rng.choice(WINDOWS))
         return (so.MovingMax, so.MovingMin)[rng.integers(0, 2)](x, w, ahead=int(rng.choice([0, (w - 1) // 2, w - 1])))
+
+    def rank(self, x):
+        rng = self.rng
+        w = int(rng.choice(RANK_WINDOWS))
+        if w > 257 and S.nframes(x) > RANK_LONG and rng.random() >= 1 / 6:
+            w = int(rng.choice([v for v in RANK_WINDOWS if v <= 257]))
+        q, ahead = float(rng.choice(RANK_Q)), int(rng.choice([0, (w - 1) // 2, w - 1]))
+        return so.MovingMedian(x, w, ahead=ahead) if q == 0.5 and rng.random() < 0.5 else so.MovingQuantile(x, w, q, ahead=ahead)
+
+    def coefficients2(self, n, nch):
+        """`Recur2`'s a1 and a2 for a b of n frames: two numbers, or two rows (resonator pairs, or U[-1, 1] and U[-0.5, 0.5],
+        as tests/recur2_ref.py `coef`) of one channel or nch each, at times an `Append` of two rows or longer than b"""
+        rng = self.rng
+        if rng.random() < 0.3:
+            return STABLE_PAIRS[rng.integers(0, len(STABLE_PAIRS))]
+        m = n + 7
+        shape = (m, 1 if rng.random() < 0.5 else nch)
+        if rng.random() < 0.5:
+            r, th = rng.uniform(0.5, 0.9995, shape), rng.uniform(0.0, math.pi, shape)
+            a1, a2 = 2.0 * r * np.cos(th), -(r * r)
+        else:
+            a1, a2 = rng.uniform(-1.0, 1.0, shape), rng.uniform(-0.5, 0.5, shape)
+        if shape[1] > 1 and rng.random() < 0.4:  # (one of the two mono, the other of nch channels)
+            a2 = a2[:, :1]
+        row = lambda a, lo, hi: so.Signal(np.asfortranarray(a[lo:hi]), FS)  # noqa: E731
+        out = []
+        for a in (a1, a2):
+            if n > 2 and rng.random() < 0.4:
+                k = _beside(rng, n, 1)
+                out.append(so.Append(row(a, 0, k), row(a, k, n + int(rng.choice([0, 5])))))
+            else:
+                out.append(row(a, 0, n + int(rng.choice([0, 0, 7]))))
+        return tuple(out)
 
     def operand(self, nch, depth):
         """a node's input: Float64, or (one time in five) a Float32 structure"""
@@ -301,13 +407,18 @@ class _Gen:
 
     def node(self, nch, depth):
         rng = self.rng
-        fam = FAMILIES[rng.integers(0, len(FAMILIES))]
-        # (an extremum keeps Float32, and arithmetic may follow this node: a Float32 extremum comes from `f32` alone)
-        x = self.f64(nch, depth - 1) if fam == "Moving" else self.operand(nch, depth - 1)
+        fam = self.families[rng.integers(0, len(self.families))]
+        # (an extremum or a rank keeps Float32, and arithmetic may follow this node: a Float32 one comes from `f32` alone)
+        x = self.f64(nch, depth - 1) if fam in ("Moving", "MovingRank") else self.operand(nch, depth - 1)
         n = S.nframes(x)
-        if fam == "SampleAt":
+        if fam in ("SampleAt", "SampleAtFir"):
+            kind = FIR_KINDS[rng.integers(0, len(FIR_KINDS))] if fam == "SampleAtFir" else {}
             return so.SampleAt(x, self.positions(n, nch), left=float(rng.choice([0.0, -1.5])), right=float(rng.choice([0.0, 2.0])),
-                               wrap=bool(rng.random() < 0.25))
+                               wrap=bool(rng.random() < 0.25), **kind)
+        if fam == "Recur2":
+            return so.Recur2(*self.coefficients2(n, nch), x)
+        if fam == "MovingRank":
+            return self.rank(x)
         if fam == "Comb":
             D, g = int(rng.choice(DELAYS)), float(rng.choice([0.7, -0.8, 0.5, 0.6]))
             return so.Allpass(x, D, g) if rng.random() < 0.4 else so.Comb(x, D, g, feedforward=float(rng.choice([0.0, -0.35])))
@@ -373,21 +484,24 @@ class _Gen:
         return self.f32(nch, depth) if self.rng.random() < 0.1 else self.f64(nch, depth)
 
 
-def random_tree(rng, nch, depth, nodes=True):
+def random_tree(rng, nch, depth, nodes=True, families=SIX):
     """a finite tree of the grammar with nch channels, at most `depth` operators deep (depth <= 4), with at least one
-    device-only node -- or, with `nodes=False`, of the structural operators alone, which the oracle can evaluate"""
+    device-only node of `families` -- or, with `nodes=False`, of the structural operators alone, which the oracle can evaluate"""
     assert 1 <= depth <= 4
     while True:
-        t = _Gen(rng, nodes).tree(nch, depth)
+        t = _Gen(rng, nodes, families).tree(nch, depth)
         if not nodes or census(t)[0]:
             return t
 
 
-def random_trees(seed, count=TREES_PER_SEED, nodes=True):
-    """the trees of one seed: [(nch, tree)], channel counts 1, 2 and 3 and depths 2 to 4 in turn"""
+def random_trees(seed, count=TREES_PER_SEED, nodes=True, families=None):
+    """the trees of one seed: [(nch, tree)], channel counts 1, 2 and 3 and depths 2 to 4 in turn; of all of `FAMILIES` for a
+    seed of `SEEDS_ALL` and of `SIX` for any other, where `families` does not say"""
+    if families is None:
+        families = FAMILIES if seed in SEEDS_ALL else SIX
     rng = np.random.default_rng(seed)
     out = []
     for i in range(count):
         nch = (1, 2, 3)[i % 3]
-        out.append((nch, random_tree(rng, nch, 2 + (i % 3), nodes)))
+        out.append((nch, random_tree(rng, nch, 2 + (i % 3), nodes, families)))
     return out
