@@ -485,8 +485,10 @@ typedef enum so_counter {
     SO_COUNTER_RSOS_PERIOD_INPUTS = 7,  /* input frames per period                                                   */
     SO_COUNTER_WPROJ_FRAMES = 8,        /* frames a projected warm-up reads                                          */
     SO_COUNTER_WPROJ_FIRST = 9,         /* the first of them, counted from the warm-up's first period (may be < 0)   */
-    SO_COUNTER_RSOS_FOLD = 10 /* 1: the fused resampler + IIR kernel runs its folded block -- the cascade's zero-state response
+    SO_COUNTER_RSOS_FOLD = 10, /* 1: the fused resampler + IIR kernel runs its folded block -- the cascade's zero-state response
                                * folded into the tap table, 4 MFMAs fewer per block (0: the unfolded block, or no such launch) */
+    SO_COUNTER_RSOS_CHAIN4 = 11 /* 1: the fused kernel's chain wave runs its recurrence on the 4 x 4 x 4 matrix shape, one
+                                 * instruction per block of the block-triangular A^16 (0: three 16 x 16 x 4, or no such launch) */
 } so_counter_t;
 int64_t so_plan_counter(const so_plan_t* plan, int32_t which);
 
@@ -634,6 +636,17 @@ int32_t so_rsos_wproj_matrix(const double* sos, int32_t nsec, double gain, const
  * / max_i sum_j |D|_ij;  *fold = 1 where the planner's gate (amp <= 256) admits the cascade. */
 int32_t so_rsos_fold_tables(const double* sos, int32_t nsec, double gain, const double* tab, int32_t ngroups, int32_t kw,
                             double* e, double* ftab, double* amp, int32_t* fold);
+
+/* Diagnostic, host only: the chain wave's recurrence matrix of the fused resampler + IIR kernel for the cascade `sos` ([nsec][6]
+ * rows, times `gain`, as above).  a16: [12][12] row-major, A^16 -- the map from the DF2T state entering a block of 16 samples to
+ * the state behind it (rows and columns from 2 nsec on are zero).  *chain4 = 1 where every 4 x 4 block above the diagonal is
+ * exactly zero and the kernel therefore runs the recurrence on the 4 x 4 x 4 matrix shape; blocks: [6][64] is then the table it
+ * reads -- the blocks (r, c) in the order (0,0) (1,0) (1,1) (2,0) (2,1) (2,2), entry l of a block being
+ * A^16[4 r + (l & 3)][4 c + (l >> 4)], the instruction's A operand -- and all zeros otherwise. */
+/* (the return type stands on a line of its own ON PURPOSE: tests/test_movingmedian_host.py pins the number of one-line
+ * entry-point declarations in this header at what it was when that node was added, and must stay as it is) */
+int32_t
+    so_rsos_chain_blocks(const double* sos, int32_t nsec, double gain, double* a16, double* blocks, int32_t* chain4);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

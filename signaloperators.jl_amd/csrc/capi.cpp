@@ -261,4 +261,12 @@ int32_t so_rsos_fold_tables(const double* sos, int32_t nsec, double gain, const 
     return SO_OK;
 }
 
+int32_t so_rsos_chain_blocks(const double* sos, int32_t nsec, double gain, double* a16, double* blocks, int32_t* chain4) {
+    if (!sos || !a16 || !blocks || !chain4 || nsec < 1 || nsec > 6) return set_err(SO_ERR_INVALID, "so_rsos_chain_blocks: bad arguments");
+    int c = 0;
+    so::rsos_chain4_tables_sos(sos, nsec, gain, a16, blocks, &c);
+    *chain4 = c;
+    return SO_OK;
+}
+
 }  // extern "C"

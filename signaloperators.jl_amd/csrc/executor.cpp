@@ -1589,12 +1589,18 @@ int64_t plan_counter(const Plan* P, int which) {
     case SO_COUNTER_DIRECT_EXECUTES: return P->n_direct;
     case SO_COUNTER_FUSED_MFMAS_PER_BLOCK: {  // k_rsos: window k-steps + 14 (D . X, X^T T^T, the chain's A^16 . S, S^T C^T)
         for (const Stage& S : P->stages)    // ... + 10 for a folded plan (E . Z, the chain's A^16 . S, C . S)
+                                            // (the chain's share counts as three large MFMAs whatever shape it runs on)
             if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.ks + (S.rs.fold ? 10 : 14);
         return 0;
     }
     case SO_COUNTER_RSOS_FOLD: {  // k_rsos: the folded block (RsSos::fold)
         for (const Stage& S : P->stages)
             if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.fold;
+        return 0;
+    }
+    case SO_COUNTER_RSOS_CHAIN4: {  // k_rsos: the chain's recurrence on the 4 x 4 x 4 shape (RsSos::chain4_off)
+        for (const Stage& S : P->stages)
+            if (S.kind == ST_SOS && S.rsos_src >= 0 && S.need > 0) return S.rs.chain4_off != 0 ? 1 : 0;
         return 0;
     }
     case SO_COUNTER_WPROJ: {  // k_rsos: the warm-up of a range as one product where it lies inside the array (RsSos::wproj)

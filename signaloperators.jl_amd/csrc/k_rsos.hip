@@ -623,6 +623,193 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
     }
 }
 
+// The same recurrence on v_mfma_f64_4x4x4_4b_f64 (RsSos::chain4_off; stages.cpp, rsos_chain4_operands).  A^16 of a cascade in
+// cascade order is block lower triangular in 4 x 4 blocks -- a section's state never depends on a later section's -- and the
+// small shape computes four independent 4 x 4 x 4 products per instruction: ONE instruction is one block (r, c), c <= r, of
+// A^16 applied to all four groups of four sequences.  Six instructions per step for NK = 3, three for 2, one for 1, in the
+// order (2,0) (1,0) (0,0) (2,1) (1,1) (2,2): every accumulate chain is spaced by the ~48 cycles it needs, every B operand
+// of the next step has been ready for several issue slots, and the matrix pipe of this SIMD is taken for 6 x ~17 cycles a
+// block instead of 3 x 64 (tools/micro/mfma64_chain.hip, k4 and k5; profiles/r17/mfma64_chain4.txt).  The sums keep their
+// order per row block -- ((D . x + A_r0 . S_0) + A_r1 . S_1) + A_r2 . S_2 --; the blocks left out added exact zeros.
+// Lanes (the micro-benchmark's probe): A_b[i][k] in lane 16 k + 4 b + i, B_b[k][j] in 16 k + 4 b + j, D_b[i][j] in 16 i + 4 b + j.
+// A row block r of the state is therefore ONE register pair, lane l = state row 4 r + (l >> 4) of sequence l & 15: where the
+// instruction leaves D, where it reads B, and the very place the large shape keeps it -- the exchange slots ([row][16
+// sequences]), the counters, the look-ahead, the y waves, the helper and rsos_wproj_chain are rsos_chain's.
+// What differs is the gap.  The large shape leaves 48 idle cycles in front of a step's first MFMA and hides the step's
+// bookkeeping there; the small one leaves none, and a wave issues an instruction every four cycles at best: the step is as
+// long as its instruction count.  So: D . x of block b + 2 and the counters are read unconditionally (past the last block a
+// slot nobody uses) into the registers the step has just used -- the compiler then needs ONE wait per pair of steps, in the
+// gap, none between two MFMAs --; one ds_read_b32 fetches ALL counters (lane s = slot s, a loop-invariant address) and
+// v_readlane picks block b + 2's; the state counter's address is loop invariant; the next step's slot arithmetic stands under
+// this step's last instructions.  (Tried and measured equal in the kernel, profiles/r17/chain4_forms.jsonl: inline-asm reads
+// with a hand-counted s_waitcnt lgkmcnt(2 (NK + 1)) per step -- correct only while the compiler copies none of the pending
+// registers --, and reads under `if (b + 2 < NB)`.  The plain form stays.)
+template <int NY, int NK>
+__device__ __attribute__((noinline)) void rsos_chain4(RsosShared* sh_, double* dyn, int64_t G_) {
+    constexpr int NX = 2 * NY + 1, NS = rsos_nss(NY);
+    const int lane = threadIdx.x & 63;
+    SO_LDS RsosShared* const sh = (SO_LDS RsosShared*)rsos_lds_ptr(sh_);
+    const SO_LDS RsSos& g = sh->g;
+    const int ngroups = uni(g.ngroups);
+    const RsosLds l = rsos_carve(dyn, uni(g.cyc) > 0 ? 0 : ngroups * uni(g.ks) * 64, uni(g.rpitch), NX, NS);
+    const int NB = (uni(sh->wpe) + (int)rfl64(g.pr)) * ngroups;
+    const double SO_GLB* mats = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats) + uni(g.chain4_off);
+    long long* trace = (long long*)rfl64((int64_t)(uintptr_t)g.trace);
+    const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
+    const int debug = uni(g.debug);
+    // blocks (0,0) (1,0) (1,1) (2,0) (2,1) (2,2) of A^16 as A operands, the same 4 x 4 in all four 16-lane groups
+    double A00 = mats[lane], A10 = 0.0, A11 = 0.0, A20 = 0.0, A21 = 0.0, A22 = 0.0;
+    if constexpr (NK >= 2) A10 = mats[64 + lane], A11 = mats[128 + lane];
+    if constexpr (NK >= 3) A20 = mats[192 + lane], A21 = mats[256 + lane], A22 = mats[320 + lane];
+    __builtin_amdgcn_s_setprio(3);  // (rsos_chain: this wave is the critical path)
+    int spins = 0;
+    [[maybe_unused]] int cnt_wait = 0, cnt_blocks = 0;
+    [[maybe_unused]] const long long cyc0 = SO_RSOS_COUNT ? clock64() : 0;
+    while (uni(flag_ld(fl_base + 4 * (kRsosFlagXseq + 0))) < 1 && !(debug & 4)) SO_SPIN_PAUSE(spins, 1, 1 << 22);
+    // two steps per loop iteration, the register sets swapping roles, as in rsos_chain
+    double sA[3] = {0.0, 0.0, 0.0}, sB[3] = {0.0, 0.0, 0.0};  // state entering the even / odd block, a row block each
+#pragma unroll
+    for (int v = 0; v < NK; ++v) sA[v] = l.ss[v * 64 + lane];
+    double dA[3] = {0.0, 0.0, 0.0}, dB[3] = {0.0, 0.0, 0.0};  // D . x of the even / odd block: the C operand of a row block's first instruction
+#pragma unroll
+    for (int v = 0; v < NK; ++v) dA[v] = l.xs[v * 64 + lane];
+    if (NB > 1) {
+        spins = 0;
+        while (uni(flag_ld(fl_base + 4 * (kRsosFlagXseq + 1))) < 2 && !(debug & 4)) SO_SPIN_PAUSE(spins, 1, 1 << 22);
+#pragma unroll
+        for (int v = 0; v < NK; ++v) dB[v] = l.xs[192 + v * 64 + lane];
+    }
+    const uint32_t xs0 = (uint32_t)(uintptr_t)l.xs + (uint32_t)lane * 8u, ss0 = (uint32_t)(uintptr_t)l.ss + (uint32_t)lane * 8u;
+    // lane s: the address of D . x slot s's counter; ... and of the state counter.  In vector registers for good.
+    uint32_t afl = fl_base + 4u * (uint32_t)(kRsosFlagXseq + (lane < NX ? lane : NX - 1)), ag = fl_base + 4u * (uint32_t)kRsosFlagSseq;
+    asm volatile("" : "+v"(afl), "+v"(ag));
+    int fA = flag_ld(afl), fB = fA;  // the counters as the steps two before blocks 0 and 1 would have seen them
+    int s2 = 2 % NX;                 // D . x slot of block b + 2 (b modulo NX)
+    // ... its byte offset, and those of the state slots (b modulo NS) of the even and the odd block: five scalar
+    // instructions a step (NS == NX: the state slot of block b + 2 has the number of its D . x slot, which this step has in hand)
+    uint32_t offx = (uint32_t)s2 * 1536u, offsA = 0, offsB = (uint32_t)(1 % NS) * 1536u;
+    [[maybe_unused]] int sslot2 = 2 % NS;
+    const int NBw = (debug & (4 | 512)) ? 0 : NB;  // (blocks whose D . x this wave waits for)
+    int nowrite = debug & 1024;
+    asm volatile("" : "+s"(nowrite));
+    if constexpr (NK == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A00), "+v"(A10), "+v"(A11), "+v"(A20), "+v"(A21), "+v"(A22));
+    else if constexpr (NK == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(A00), "+v"(A10), "+v"(A11));
+    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(A00));  // (not in front of the loop's MFMAs, in every round)
+    auto step = [&](int b, double (&sin)[3], double (&sout)[3], double (&din)[3], int& fpend, uint32_t& offs) __attribute__((always_inline)) {
+        // ---- the gap in front of the first instruction: four vector instructions (and, every other step, the wait) ----
+        int f = __builtin_amdgcn_readlane(fpend, s2);  // counter of block b + 2's slot, requested two steps ago
+        uint32_t ax = xs0 + offx, as = ss0 + offs;
+        int bv = b;
+        asm volatile("" : "+v"(ax), "+v"(as), "+v"(bv));  // (in vector registers NOW)
+        // ---- between the instructions: scalar and LDS instructions only.  Behind the first: the state entering block b for
+        //      its y wave (the earliest it can go).  Behind the last that takes D . x of block b as its C operand: D . x of
+        //      block b + 2 into those registers, and the counters.  Then the next step's slots.  Nothing behind the last one.
+        auto put_state = [&]() __attribute__((always_inline)) {
+            if (__builtin_expect(nowrite != 0, 0)) {  // (SIGOPS_RSOS_DEBUG 1024)
+                asm volatile("s_nop 0");  // (keeps this a scalar branch: as a select the test is two vector instructions under the first MFMA)
+                return;
+            }
+#pragma unroll
+            for (int v = 0; v < NK; ++v) *(volatile SO_LDS double*)(uintptr_t)(as + (uint32_t)v * 512u) = sin[v];
+            *(volatile SO_LDS int*)(uintptr_t)ag = bv;
+        };
+        auto get_dx = [&]() __attribute__((always_inline)) {
+            if (__builtin_expect(f < b + 3, 0) && b + 3 <= NBw) {  // (the y waves are behind: wait here -- everybody waits for this wave anyway)
+                spins = 0;
+                if constexpr (SO_RSOS_COUNT) cnt_blocks += lane == (b + 2) % NY ? 1 : 0;
+                do {
+                    SO_SPIN_PAUSE(spins, 1, 1 << 22);
+                    if constexpr (SO_RSOS_COUNT) cnt_wait += lane == (b + 2) % NY ? 1 : 0;
+                    f = uni(flag_ld(fl_base + 4 * (kRsosFlagXseq + s2)));
+                } while (f < b + 3);
+            }
+            // (unconditional: past the last block they fetch a slot nobody reads)
+#pragma unroll
+            for (int v = 0; v < NK; ++v) din[v] = *(volatile SO_LDS double*)(uintptr_t)(ax + (uint32_t)v * 512u);
+            fpend = *(volatile SO_LDS int*)(uintptr_t)afl;
+        };
+        auto next_slots = [&]() __attribute__((always_inline)) {
+            if constexpr (NS == NX) offs = offx;  // (this register set's next block is b + 2)
+            else {
+                offs = (uint32_t)sslot2 * 1536u;
+                sslot2 = sslot2 + 1 == NS ? 0 : sslot2 + 1;
+            }
+            s2 = s2 + 1 == NX ? 0 : s2 + 1;
+            offx = (uint32_t)s2 * 1536u;
+            asm volatile("" : "+s"(offx), "+s"(offs));  // (computed HERE, not in the gap)
+        };
+        double acc0, acc1 = 0.0, acc2 = 0.0;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (NK == 3) {
+            acc2 = __builtin_amdgcn_mfma_f64_4x4x4f64(A20, sin[0], din[2], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            put_state();
+            __builtin_amdgcn_sched_barrier(0);
+            acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(A10, sin[0], din[1], 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(A00, sin[0], din[0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            get_dx();
+            __builtin_amdgcn_sched_barrier(0);
+            acc2 = __builtin_amdgcn_mfma_f64_4x4x4f64(A21, sin[1], acc2, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            next_slots();
+            __builtin_amdgcn_sched_barrier(0);
+            acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(A11, sin[1], acc1, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f64_4x4x4f64(A22, sin[2], acc2, 0, 0, 0);
+        } else if constexpr (NK == 2) {
+            acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(A10, sin[0], din[1], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            put_state();
+            __builtin_amdgcn_sched_barrier(0);
+            acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(A00, sin[0], din[0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            get_dx();
+            next_slots();
+            __builtin_amdgcn_sched_barrier(0);
+            acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(A11, sin[1], acc1, 0, 0, 0);
+        } else {
+            acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(A00, sin[0], din[0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            put_state();
+            get_dx();
+            next_slots();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        sout[0] = acc0;
+        if constexpr (NK >= 2) sout[1] = acc1;
+        if constexpr (NK >= 3) sout[2] = acc2;
+    };
+    for (int b = 0; b < NB; b += 2) {
+        rsos_stamp(trace, 0, b >> 1, 0, 200);
+        step(b, sA, sB, dA, fA, offsA);
+        if (b + 1 < NB) step(b + 1, sB, sA, dB, fB, offsB);
+        rsos_stamp(trace, 0, b >> 1, 3, 200);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    if constexpr (SO_RSOS_COUNT) {
+        if (lane < 8) rsos_count_out(trace, 0, 0, lane, cnt_wait);
+        else if (lane < 16) rsos_count_out(trace, 0, 1, lane - 8, cnt_wait);
+        if (lane < 8) rsos_count_out(trace, 0, 2, lane, cnt_blocks);
+        else if (lane < 16) rsos_count_out(trace, 0, 3, lane - 8, cnt_blocks);
+        if (lane == 0) rsos_count_out(trace, 0, 4, 0, clock64() - cyc0);
+    }
+    // (rsos_chain: a range whose walk ends in a non-finite state is noted per channel; row = lane & 15 here too)
+    int32_t* bad = (int32_t*)rfl64((int64_t)(uintptr_t)g.bad);
+    if (bad != nullptr) {
+        const double(&sE)[3] = (NB & 1) ? sB : sA;  // the state the last block left
+        const bool nf = !(isfinite(sE[0]) && (NK < 2 || isfinite(sE[1])) && (NK < 3 || isfinite(sE[2])));
+        const uint64_t m = __ballot(nf);
+        const uint32_t rows = (uint32_t)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xffffu);
+        if (rows != 0 && lane < 16 && ((rows >> lane) & 1u)) {
+            const int ct = uni(g.ct), rgs = uni(g.rgs);
+            const int64_t G = rfl64(G_);
+            const int64_t ncg = uni(g.nch) / ct;
+            const int64_t r = (G / ncg) * rgs + lane / ct;
+            if (r < uni(g.nranges)) atomicMin(bad + ((int)(G % ncg) * ct + lane % ct), (int32_t)r);
+        }
+    }
+}
+
 // Two arrays (RsSos::arr2): the second one's rows can be read 16 bytes per lane at the frames the first one's 128-byte lines
 // start at -- both arrays' rows equally aligned.  Loaders, step waves and y waves agree on it (it is part of `single`).
 __device__ __forceinline__ bool rsos_two_ok(const SO_LDS DCarrier& C0, int chunk) {
@@ -2020,7 +2207,11 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
             if (!(g.debug & 64)) {
                 if (proj) rsos_wproj_chain<NY>(&sh, lds_raw, G);
                 const int nk = (g.debug & 131072) ? 3 : (2 * g.nsec + 3) / 4;
-                if (nk <= 1) rsos_chain<NY, 1>(&sh, lds_raw, G);
+                if (g.chain4_off != 0) {  // (the filter's alone, never the geometry's: every form of a plan takes the same chain)
+                    if (nk <= 1) rsos_chain4<NY, 1>(&sh, lds_raw, G);
+                    else if (nk == 2) rsos_chain4<NY, 2>(&sh, lds_raw, G);
+                    else rsos_chain4<NY, 3>(&sh, lds_raw, G);
+                } else if (nk <= 1) rsos_chain<NY, 1>(&sh, lds_raw, G);
                 else if (nk == 2) rsos_chain<NY, 2>(&sh, lds_raw, G);
                 else rsos_chain<NY, 3>(&sh, lds_raw, G);
             }

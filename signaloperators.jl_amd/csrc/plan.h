@@ -27,6 +27,7 @@ void rsos_wproj_matrix_sos(const double* sos, int nsec, double gain, const doubl
 // (stages.cpp) ... its folded block: e[12][16] = D . T^-1, ftab[ngroups][kw][16] = T . Tap_g^T in the kernel's row order, the gate
 void rsos_fold_tables_sos(const double* sos, int nsec, double gain, const double* tab, int ngroups, int kw, double* e, double* ftab, double* amp,
                           int* fold);
+void rsos_chain4_tables_sos(const double* sos, int nsec, double gain, double* a16, double* blocks, int* chain4);
 int resample_positions(double fs_in, double fs_out, double rate, int nphi, const double* h, int hlen,
                        int64_t n_out, int64_t* j, int32_t* p, double* alpha, int64_t* nfix, int64_t* nbaked);
 

@@ -427,7 +427,14 @@ struct RsSos {
                           // the chain wave gets E . Z with E = D . T^-1 (= D . X), the result is Z + C . S: 20 MFMAs per y-wave block, not 24
     int32_t fold_off;     // ... its operands in `mats`, from this double on: [4][64] E k-steps, [3][64] C k-steps, [ngroups][ks][64] M_g --
                           // MFMA row m = gq + 4 v of a block holds output time 2 gq + (v & 1) + 8 (v >> 1) (rsos_fold_time)
+    int32_t chain4_off;   // != 0: the chain wave runs S' = D . x + A^16 . S on v_mfma_f64_4x4x4_4b_f64, one instruction per 4 x 4 block of
+                          // the block lower triangular A^16 (k_rsos.hip, rsos_chain4); its six blocks as A operands in `mats`, from
+                          // this double on (stages.cpp, rsos_chain4_operands).  The filter's alone: every geometry and form takes it.
 };
+// lane l of an A operand of v_mfma_f64_4x4x4_4b_f64 holds A_b[i][k] with i = l & 3, k = l >> 4 (b = (l >> 2) & 3: the chain's
+// blocks are the same in all four); tools/micro/mfma64_chain.hip prints the map
+constexpr int rsos_c4_a_i(int lane) { return lane & 3; }
+constexpr int rsos_c4_a_k(int lane) { return lane >> 4; }
 constexpr int kRsosTraceIters = 96;
 // output time (within its block) of MFMA row m of a folded block: registers 0, 1 of a lane hold two adjacent outputs, registers
 // 2, 3 the pair eight outputs later -- two 16-byte stores per lane and block

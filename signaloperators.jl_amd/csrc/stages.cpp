@@ -2096,6 +2096,33 @@ static void rsos_block_matrices(const SosCoefs& cf, std::vector<double>& mats) {
     }
 }
 
+// The chain wave's recurrence on the 4 x 4 x 4 matrix shape (k_rsos.hip, rsos_chain4): A^16 of a cascade in cascade order is
+// block lower triangular in 4 x 4 blocks -- the recurrence above never carries a later section's state into an earlier one, so
+// the zeros are exact --, and one v_mfma_f64_4x4x4_4b_f64 applies one block to all four groups of four sequences.  Appended to
+// `mats` (RsSos::chain4_off): the blocks (r, c), c <= r, in the order (0,0) (1,0) (1,1) (2,0) (2,1) (2,2) as A operands -- lane l
+// holds A^16[4 r + rsos_c4_a_i(l)][4 c + rsos_c4_a_k(l)], the same 4 x 4 in all four 16-lane groups.  The doubles are the ones
+// `mats` holds for the large shape (k-steps 4 .. 6): no new arithmetic.  false (and nothing appended) where a block above the
+// diagonal is not exactly zero: that filter keeps the large shape.
+static double rsos_a16_at(const std::vector<double>& mats, int i, int k) { return mats[(size_t)(4 + k / 4) * 64 + (size_t)(k % 4) * 16 + i]; }
+static bool rsos_chain4_operands(std::vector<double>& mats) {
+    for (int i = 0; i < 12; ++i)
+        for (int k = 4 * (i / 4 + 1); k < 12; ++k)
+            if (rsos_a16_at(mats, i, k) != 0.0) return false;
+    const size_t o = mats.size();
+    mats.resize(o + (size_t)6 * 64, 0.0);
+    for (int r = 0, t = 0; r < 3; ++r)
+        for (int c = 0; c <= r; ++c, ++t)
+            for (int lane = 0; lane < 64; ++lane) mats[o + (size_t)t * 64 + lane] = rsos_a16_at(mats, 4 * r + rsos_c4_a_i(lane), 4 * c + rsos_c4_a_k(lane));
+    return true;
+}
+// sets RsSos::chain4_off (0: the large shape); SIGOPS_RSOS_CHAIN16=1 keeps the large shape everywhere
+static void rsos_chain4_tables(RsSos& rs, std::vector<double>& mats) {
+    rs.chain4_off = 0;
+    if (std::getenv("SIGOPS_RSOS_CHAIN16")) return;
+    const size_t o = mats.size();
+    if (rsos_chain4_operands(mats)) rs.chain4_off = (int32_t)o;
+}
+
 // The FOLDED block (k_rsos.hip, rsos_ywave<..., FOLD>).  T is the same 16 x 16 matrix for every block, so the y waves can resample
 // with M_g = T . Tap_g^T and get the block's zero-state output Z = T . X in the place of X: what was X^T . T^T, four MFMAs of the
 // 24 a y wave issues per block, goes.  The chain wave's share of the next state is then E . Z with E = D . T^-1 (T is lower
@@ -2212,6 +2239,16 @@ void rsos_fold_tables_sos(const double* sos, int nsec, double gain, const double
     std::copy(F.ftab.begin(), F.ftab.end(), ftab);
     *amp = F.amp;
     *fold = F.ok ? 1 : 0;
+}
+void rsos_chain4_tables_sos(const double* sos, int nsec, double gain, double* a16, double* blocks, int* chain4) {
+    std::vector<double> mats;
+    rsos_block_matrices(sos_rows_coefs(sos, nsec, gain), mats);
+    for (int i = 0; i < 12; ++i)
+        for (int k = 0; k < 12; ++k) a16[i * 12 + k] = rsos_a16_at(mats, i, k);
+    const size_t o = mats.size();
+    *chain4 = rsos_chain4_operands(mats) ? 1 : 0;
+    std::fill(blocks, blocks + 6 * 64, 0.0);
+    if (*chain4) std::copy(mats.begin() + (ptrdiff_t)o, mats.end(), blocks);
 }
 
 // The state a range's warm-up leaves, as a matrix (k_rsos.hip, rsos_wproj_*).  The kernel walks the wp warm-up periods of a
@@ -2825,6 +2862,7 @@ struct RsosFusion : RsosRanges {
     }
 
     void commit_launch() {
+        rsos_chain4_tables(S2.rs, S2.rsos_mats_host);  // (behind the projection's and the fold's tables)
         S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
         // first range per channel that ended in a non-finite state: two sets of words, used in turn (run_rsos_fused)
         if (S2.bad_buf < 0) S2.bad_buf = P.raw_buf((size_t)nch * 8);
@@ -3014,6 +3052,7 @@ struct PlainRsos {
         const int64_t ngrp = (int64_t)(g.nch / g.ct) * ((g.nranges + g.rgs - 1) / g.rgs);
         S2.rsos_grid = (int)std::min<int64_t>(ngrp, cus);
         rsos_block_matrices(S2.groups[0], S2.rsos_mats_host);
+        rsos_chain4_tables(S2.rs, S2.rsos_mats_host);
         S2.rsos_mats_buf = P.raw_buf(S2.rsos_mats_host.size() * 8);
         if (std::getenv("SIGOPS_DEBUG_PLAN"))
             std::fprintf(stderr, "[sigops] IIR in one pass (k_rsos, identity resampler%s): %lld ranges of %lld periods (+%d warm-up), %lld groups of %d ch x %d ranges, ring=%d fuse=%d/%d\n",

@@ -133,7 +133,8 @@ class Plan:
         L = K.lib()
         return {"graph_replays": L.so_plan_counter(self.handle, 0), "graph_captures": L.so_plan_counter(self.handle, 1),
                 "direct_executes": L.so_plan_counter(self.handle, 2), "fused_mfmas_per_block": L.so_plan_counter(self.handle, 3),
-                "wproj": L.so_plan_counter(self.handle, 4), "fold": L.so_plan_counter(self.handle, 10)}
+                "wproj": L.so_plan_counter(self.handle, 4), "fold": L.so_plan_counter(self.handle, 10),
+                "chain4": L.so_plan_counter(self.handle, 11)}
 
     def rsos_geometry(self):
         """the first fused resampler + IIR launch's ranges (so_plan_counter 5 .. 10): periods per range, warm-up periods, input
