@@ -294,14 +294,8 @@ __device__ __forceinline__ void rsos_widen(uint32_t slot, uint32_t row_bytes, in
     }
 }
 
-constexpr int kRsosFlagLdp = 0, kRsosFlagYrd = 4, kRsosFlagXseq = 16, kRsosFlagSseq = 48, kRsosFlagXh = 49, kRsosFlagLnd = 52, kRsosFlags = 56;
+constexpr int kRsosFlagLdp = 0, kRsosFlagYrd = 4, kRsosFlagXseq = 16, kRsosFlagSseq = 48, kRsosFlagLnd = 52, kRsosFlags = 56;  // (49 .. 51 unused: sizeof(RsosShared) stays a multiple of 16, and the dynamic LDS behind it aligned)
 constexpr int kRsosFlagWp = 37;  // (37 .. 46: a y wave's share of a projected warm-up is in its slot -- rsos_wproj_y)
-// Helper geometry (RsSos::help; 12 waves, taps in registers): the y waves of residues kRsosHres[0..2] -- one on each of SIMDs 1 .. 3 --
-// hand the y wave that shares the chain's SIMD (residue kRsosHelper) their X block instead of computing D . X themselves:
-// 68 / 68 / 68 / 66 MFMAs per round of ten blocks on the four SIMDs instead of 72 / 72 / 72 / 54.  (Not the chain wave: its
-// steps are the kernel's serial dependency.  Not the back parts -- state-dependent, needed at once: round 5 moved those and
-// made that wave the pace of everybody --: D . X of a block is needed ~8 blocks after its X exists.)
-constexpr int kRsosHres0 = 1, kRsosHres1 = 5, kRsosHres2 = 7, kRsosHelper = 6, kRsosHslots = 3;  // (SIMDs 2, 3, 1)
 constexpr int kRsosMaxGroups = 256;
 
 // What the three roles share besides the dynamic LDS (taps, ring, exchange slots): a copy of the kernel's arguments
@@ -377,7 +371,6 @@ __device__ __forceinline__ void rsos_count_out(long long* trace, int wave, int r
 struct RsosLds {
     SO_LDS double *taps, *ring, *gtab;
     volatile SO_LDS double *xs, *ss;  // what the waves hand each other
-    volatile SO_LDS double* xh;       // helper geometry: the fourth register of an X block ([3 waves][kRsosHslots][64]; 0..2 go to its xs slot)
 };
 // The roles are called with generic pointers (in vector registers, as the calling convention has it): made wave-uniform
 // 32-bit LDS pointers again here, so that every access below is a ds_ instruction with a scalar base.
@@ -392,10 +385,7 @@ __device__ __forceinline__ SO_LDS double* rsos_lds_ptr(const void* p) {
 // wins (NY + 4 slots, tried for a larger input ring: one bad block in a million, the re-read of a low-priority wave whose
 // vector instructions wait behind its neighbours' MFMAs while the chain runs six steps; waiting for the state BEFORE the
 // hand-over instead makes the y waves and the chain wait for each other: 0.955 -> 1.007 ms).
-#ifndef SO_NSS_EXTRA
-#define SO_NSS_EXTRA (ny + 1)  // (-DSO_NSS_EXTRA=4: the racy NY + 4 of the measurement above)
-#endif
-__host__ __device__ constexpr int rsos_nss(int ny) { return ny + SO_NSS_EXTRA; }
+__host__ __device__ constexpr int rsos_nss(int ny) { return 2 * ny + 1; }
 __device__ __forceinline__ RsosLds rsos_carve(double* dyn_, int tapd, int rpitch, int nx, int ns) {  // tapd: doubles of the tap table in LDS
     RsosLds l;
     SO_LDS double* dyn = rsos_lds_ptr(dyn_);
@@ -404,7 +394,6 @@ __device__ __forceinline__ RsosLds rsos_carve(double* dyn_, int tapd, int rpitch
     l.xs = l.ring + (size_t)16 * rpitch;
     l.ss = l.xs + (size_t)nx * 192;
     l.gtab = (SO_LDS double*)l.ss + (size_t)ns * 192;
-    l.xh = l.gtab + 16 * 16 * 2;
     return l;
 }
 
@@ -520,9 +509,6 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
         //      Under the first: the state entering block b (the registers the MFMAs are reading) for its y wave -- the
         //      earliest it can go.  Under the second: D . x of block b + 2 into the registers the FIRST MFMA took its C
         //      operand from (issued 64 cycles behind it: that read is over).  ... and the counter of block b + 4.  Nothing under the third: the next step's first wait would count its requests.
-#ifndef SO_CHAIN_ORDER
-#define SO_CHAIN_ORDER 1
-#endif
         auto put_state = [&]() __attribute__((always_inline)) {
             if (!(debug & 1024)) {
 #pragma unroll
@@ -565,15 +551,8 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
             get_flag();
             __builtin_amdgcn_sched_barrier(0);
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ak[1], sin[1], acc, 0, 0, 0);
-        } else if constexpr (SO_CHAIN_ORDER == 0) {
-            wait_dx();
-            get_dx();
-            get_flag();
-            put_state();
-            __builtin_amdgcn_sched_barrier(0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ak[1], sin[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ak[2], sin[2], acc, 0, 0, 0);
         } else {
+            // (three: as the comment above has it; all the LDS traffic under the first one, the state last, was the slower order)
             put_state();
             __builtin_amdgcn_sched_barrier(0);
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ak[1], sin[1], acc, 0, 0, 0);
@@ -634,7 +613,7 @@ __device__ __attribute__((noinline)) void rsos_chain(RsosShared* sh_, double* dy
 // Lanes (the micro-benchmark's probe): A_b[i][k] in lane 16 k + 4 b + i, B_b[k][j] in 16 k + 4 b + j, D_b[i][j] in 16 i + 4 b + j.
 // A row block r of the state is therefore ONE register pair, lane l = state row 4 r + (l >> 4) of sequence l & 15: where the
 // instruction leaves D, where it reads B, and the very place the large shape keeps it -- the exchange slots ([row][16
-// sequences]), the counters, the look-ahead, the y waves, the helper and rsos_wproj_chain are rsos_chain's.
+// sequences]), the counters, the look-ahead, the y waves and rsos_wproj_chain are rsos_chain's.
 // What differs is the gap.  The large shape leaves 48 idle cycles in front of a step's first MFMA and hides the step's
 // bookkeeping there; the small one leaves none, and a wave issues an instruction every four cycles at best: the step is as
 // long as its instruction count.  So: D . x of block b + 2 and the counters are read unconditionally (past the last block a
@@ -1535,55 +1514,6 @@ __device__ __attribute__((noinline)) void rsos_wproj_chain(RsosShared* sh_, doub
     rsos_stamp_pro(trace, 2);
 }
 
-// =========================== helper wave ===========================
-// (16-wave geometry with RsSos::help: wave 12, the fourth wave of the chain's SIMD.)  D . X of the blocks whose y waves
-// hand over X itself -- residues kRsosHres0/1/2 of every round of NY blocks, in block order: four MFMAs that depend on
-// nothing but X, on the SIMD whose matrix pipe the chain's dependent steps leave idle two thirds of the time.  The result
-// replaces X in the block's exchange slot and the slot's counter tells the chain: what the y wave would have done itself.
-template <int NY>
-__device__ __attribute__((noinline)) void rsos_helper(RsosShared* sh_, double* dyn) {
-    constexpr int NX = 2 * NY + 1;
-    const int lane = threadIdx.x & 63;
-    SO_LDS RsosShared* const sh = (SO_LDS RsosShared*)rsos_lds_ptr(sh_);
-    const SO_LDS RsSos& g = sh->g;
-    const RsosLds l = rsos_carve(dyn, 0, uni(g.rpitch), NX, rsos_nss(NY));
-    const int NB = (uni(sh->wpe) + (int)rfl64(g.pr)) * uni(g.ngroups);
-    const double SO_GLB* mats = (const double SO_GLB*)rfl64((int64_t)(uintptr_t)g.mats);
-    const uint32_t fl_base = (uint32_t)(uintptr_t)sh->flags;
-    const int debug = uni(g.debug);
-    const bool f32m = uni(g.f32m) != 0 && uni(g.out_f32) != 0;
-    double Dk[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) Dk[v] = f32m ? mats[(lane >> 4) * 64 + v * 16 + (lane & 15)] : mats[v * 64 + lane];
-    __builtin_amdgcn_s_setprio(1);
-    constexpr int res[3] = {kRsosHres0, kRsosHres1, kRsosHres2};
-    int hslot[3] = {kRsosHres0 % NX, kRsosHres1 % NX, kRsosHres2 % NX}, hring = 0;
-    for (int b0 = 0; b0 < NB; b0 += NY) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int bh = b0 + res[j];
-            if (bh < NB) {
-                int spins = 0;
-                while (uni(flag_ld(fl_base + 4 * (kRsosFlagXh + j))) < bh + 1 && !(debug & 16)) SO_SPIN_PAUSE(spins, 2, 1 << 22);
-                double xr[4];
-#pragma unroll
-                for (int v = 0; v < 3; ++v) xr[v] = l.xs[hslot[j] * 192 + v * 64 + lane];
-                xr[3] = l.xh[(j * kRsosHslots + hring) * 64 + lane];
-                v4d dh = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int v = 0; v < 4; ++v) dh = __builtin_amdgcn_mfma_f64_16x16x4f64(Dk[v], xr[v], dh, 0, 0, 0);
-#pragma unroll
-                for (int v = 0; v < 3; ++v) l.xs[hslot[j] * 192 + v * 64 + lane] = dh[v];
-                flag_st(fl_base + 4 * (kRsosFlagXseq + hslot[j]), bh + 1);
-            }
-            hslot[j] += NY;
-            if (hslot[j] >= NX) hslot[j] -= NX;
-        }
-        hring = hring + 1 == kRsosHslots ? 0 : hring + 1;
-    }
-    __builtin_amdgcn_s_setprio(0);
-}
-
 // =========================== y waves ===========================
 // CYC > 0: the wave's blocks cycle through CYC phase groups of the period (yi, yi + NY, ... modulo ngroups) and their
 // taps stay in registers for the whole kernel; CYC == 0: taps of any phase from the LDS table.
@@ -1600,10 +1530,10 @@ __device__ __attribute__((noinline)) void rsos_helper(RsosShared* sh_, double* d
 // gq + 4 v holds output time 2 gq + (v & 1) + 8 (v >> 1) (rsos_fold_time -- the planner permuted the rows of M_g and C and the
 // columns of E accordingly), i.e. registers 0, 1 and 2, 3 of a lane are two pairs of adjacent outputs of ITS sequence, 64 bytes
 // apart: two 16-byte stores per lane and block, each writing 64 contiguous bytes in each of the 16 rows.
-template <int KS, int NY, int NL, typename TO, int CYC, bool F32M = false, bool HW = false, bool FOLD = false>
+template <int KS, int NY, int NL, typename TO, int CYC, bool F32M = false, bool FOLD = false>
 __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dyn, int64_t G_, int yi_) {
     static_assert(!F32M || (sizeof(TO) == 4 && CYC > 0), "the Float32 MFMA form: Float32 results, taps in registers");
-    static_assert(!FOLD || (sizeof(TO) == 8 && !F32M && !HW), "the folded block: Float64 results, no helper wave");
+    static_assert(!FOLD || (sizeof(TO) == 8 && !F32M), "the folded block: Float64 results");
     constexpr int NX = 2 * NY + 1;
     const int lane = threadIdx.x & 63;
     const int wave = uni(threadIdx.x >> 6);
@@ -1676,19 +1606,13 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
     uint32_t yo0;
     int64_t ystep[4];
     const int64_t ybase_e = (int64_t)(grp.cg * ct) * out_pitch + grp.ob0;
-#ifndef SO_Y_EARLY
-#define SO_Y_EARLY 0  // (see block(): the pending block's state-dependent MFMAs in front of D . X -- measured, slower)
-#endif
-#ifndef SO_Y_SADDR
-#define SO_Y_SADDR 1
-#endif
 #ifndef SO_ST_NT
 // cache-policy bits of the Float64 result stores.  Together with the same hint on the staging loads (kstage.h SO_LD_NT) it lost on
 // 12.5 M x 8; on the stores ALONE it gains on every shape measured (profiles/r09/store_policy.txt: headline 0.959 -> 0.951 ms,
 // 12.5 M x 8 0.496 -> 0.493): a result is written once and read by nobody in the launch, the loads keep their lines.
 #define SO_ST_NT " nt"
 #endif
-    const bool yfits = SO_Y_SADDR && uni((int)((((int64_t)(ct - 1) * out_pitch + (int64_t)(16 / ct) * grp.prL + 16) * (int64_t)sizeof(TO)) < ((int64_t)1 << 32)));
+    const bool yfits = uni((int)((((int64_t)(ct - 1) * out_pitch + (int64_t)(16 / ct) * grp.prL + 16) * (int64_t)sizeof(TO)) < ((int64_t)1 << 32)));
     int nbs_all;     // block b is stored by every lane of the wave while b < nbs_all (no predicates then)
     [[maybe_unused]] bool st16 = false;  // FOLD: every lane's stores of a block fall on 16-byte boundaries (wave-uniform)
     if constexpr (FOLD) {
@@ -1749,11 +1673,6 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
         nb0_any = uni(m);
     }
-    // helper geometry: this wave hands its X blocks over (hj: which of the three), or is the one that takes them
-    constexpr bool HELPABLE = HW && NY == 10 && CYC == 1;  // (its own instantiation: the 12-wave kernel's block is what it was)
-    const bool help_on = HELPABLE && uni(g.help) != 0;
-    const int hj = !help_on ? -1 : yi == kRsosHres0 ? 0 : yi == kRsosHres1 ? 1 : yi == kRsosHres2 ? 2 : -1;
-    int hr = 0;  // (owner: this block's slot of the fourth-register ring; helper: per owner, below)
     int pi = 0, gi = yi;
     while (gi >= ngroups) {
         gi -= ngroups;
@@ -1817,16 +1736,16 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         if (nkc > 2) ay = __builtin_amdgcn_mfma_f64_16x16x4f64(sv[2], Ck[2], ay, 0, 0, 0);
         return ay;
     };
-    // (fresh: the MFMAs that wrote ay are the last instructions in front of this -- the 18 wait states a Float64 store needs
-    //  behind them are inserted here, tied to the accumulators; not fresh: at least eight MFMAs lie in between)
-    auto back_store = [&](v4d ay, bool fresh) __attribute__((always_inline)) {
+    // (the MFMAs that wrote ay are the last instructions in front of this: the 18 wait states a Float64 store needs behind
+    //  them are inserted here, tied to the accumulators)
+    auto back_store = [&](v4d ay) __attribute__((always_inline)) {
         if (debug & 1) return;
         const int64_t t0 = (int64_t)16 * pb_;
         // (a scalar register pair + the lanes' 32-bit offsets: the store's own address form -- written out, the compiler
         //  widens the offsets once and adds 64-bit lane pointers per store again.  It does not see the MFMA result a
-        //  Float64 store reads behind the asm either: hence `fresh`)
+        //  Float64 store reads behind the asm either: hence the s_nop)
         const uint64_t yb = (uint64_t)rfl64((int64_t)ypend);
-        if (fresh && yfits && sizeof(TO) == 8) asm volatile("s_nop 15\n\ts_nop 1" : "+v"(ay[0]), "+v"(ay[1]), "+v"(ay[2]), "+v"(ay[3])::"memory");
+        if (yfits && sizeof(TO) == 8) asm volatile("s_nop 15\n\ts_nop 1" : "+v"(ay[0]), "+v"(ay[1]), "+v"(ay[2]), "+v"(ay[3])::"memory");
         if constexpr (FOLD) {
             // register v of lane (gq, n16): output t0 + rsos_fold_time(gq + 4 v) of sequence n16, at byte 8 (v & 1) + 64 (v >> 1)
             // from the lane's offset
@@ -1889,7 +1808,7 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         back_wait(sq, sv);
         if (ppi_ < wp) return;  // (a warm-up block: nothing to store)
         rsos_stamp(trace, wave, pb_ / NY, 4, 40);
-        back_store(back_mfma(sv, pay_), true);
+        back_store(back_mfma(sv, pay_));
         rsos_stamp(trace, wave, pb_ / NY, 5, 40);
     };
     // (je / jn: the window ends of this block's phase group and of the wave's next block's -- loop constants of a wave whose
@@ -2014,16 +1933,8 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
                 for (int v = 0; v < 4; ++v) ax[v] = (double)(float)ax[v];
             }
         }
-        // ---- (-DSO_Y_EARLY=1) the pending block's state-dependent product HERE where its state has arrived: D . X and
-        //      X^T T^T below read the resampler's accumulators as A / B operands and cannot issue until the last of its MFMAs
-        //      has left the pipe; these three depend on nothing in flight, and the stores then need no wait states.  Measured:
-        //      the y waves alone 0.899 -> 0.896 ms, the whole kernel 0.964 -> 0.978 -- D . x reaches the chain three MFMAs later.
-        bool early = false;
-        v4d ay_early = pin;
-        if (SO_Y_EARLY && pb_ >= 0 && ppi_ >= wp && (uni(sq) >= pb_ || (debug & 8))) {
-            ay_early = back_mfma(sv, pin);
-            early = true;
-        }
+        // (Tried HERE: the pending block's state-dependent product where its state has arrived, in front of D . X -- the y waves
+        //  alone 0.899 -> 0.896 ms, the whole kernel 0.964 -> 0.978: D . x reaches the chain three MFMAs later.  Not kept.)
         // next block of this wave: its window start is what this wave still needs of the ring
         int pi2 = pi, gi2 = gi + NY;
         while (gi2 >= ngroups) {
@@ -2044,12 +1955,9 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
         }
         rsos_stamp(trace, wave, b / NY, 2, 40);
         // ---- D . X for the chain wave (its share of the recurrence that does not depend on the state) ----
-        // (helper geometry, a wave of the three: X itself goes to the exchange slot below, the helper wave forms D . X)
         v4d dx = v4d{0.0, 0.0, 0.0, 0.0};
-        if (!HELPABLE || hj < 0) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) dx = __builtin_amdgcn_mfma_f64_16x16x4f64(Dk[v], ax[v], dx, 0, 0, 0);
-        }
+        for (int v = 0; v < 4; ++v) dx = __builtin_amdgcn_mfma_f64_16x16x4f64(Dk[v], ax[v], dx, 0, 0, 0);
         // ---- X^T T^T of this block (kept for the next round) ----
         // (also for a warm-up block, whose result is not stored: 7 % of the blocks; skipping the four products there makes
         //  the set a conditional value, and the register allocator pays for that with four copies behind an MFMA-result
@@ -2059,20 +1967,11 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
 #pragma unroll
             for (int v = 1; v < 4; ++v) pout = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[v], Tk[v], pout, 0, 0, 0);
         }
-        if (!HELPABLE || hj < 0) {
 #pragma unroll
-            for (int v = 0; v < 3; ++v) l.xs[slot * 192 + v * 64 + lane] = dx[v];
-            flag_st(fl_base + 4 * (kRsosFlagXseq + slot), b + 1);
-        } else {
-#pragma unroll
-            for (int v = 0; v < 3; ++v) l.xs[slot * 192 + v * 64 + lane] = ax[v];
-            l.xh[(hj * kRsosHslots + hr) * 64 + lane] = ax[3];
-            flag_st(fl_base + 4 * (kRsosFlagXh + hj), b + 1);
-            hr = hr + 1 == kRsosHslots ? 0 : hr + 1;
-        }
+        for (int v = 0; v < 3; ++v) l.xs[slot * 192 + v * 64 + lane] = dx[v];
+        flag_st(fl_base + 4 * (kRsosFlagXseq + slot), b + 1);
         // ---- the previous block's result ----
-        if (early) back_store(ay_early, false);
-        else if (pb_ >= 0) back(sq, sv, pin);
+        if (pb_ >= 0) back(sq, sv, pin);
         rsos_stamp(trace, wave, b / NY, 3, 40);
         pb_ = b;
         ppi_ = pi;
@@ -2146,19 +2045,16 @@ __device__ __attribute__((noinline)) void rsos_ywave(RsosShared* sh_, double* dy
 }
 
 
-// NW: 8 / 12 / 16 waves, or 17 = the HELPER geometry: 16 waves of 128 registers with ONE loader (wave 4), ten y waves (1 - 3,
-// 5 - 7, 8 - 11: wave 8 shares the chain's SIMD) and wave 12 -- the chain's SIMD again -- forming D . X for three of them
-// (rsos_helper): what VERDICT round 5 asked for, a second wave on SIMD 0 that uses the matrix cycles the chain leaves.
-constexpr int rsos_nthreads(int nw) { return (nw == 17 ? 16 : nw) * 64; }
+// NW: 8 / 12 / 16 waves
+constexpr int rsos_nthreads(int nw) { return nw * 64; }
 // (the kernel's body: sequence groups G0, G0 + Gstep, ... of ONE filter -- the whole grid's for k_rsos, a share of it for a member
 //  of k_rsos_batch)
 // FOLDABLE: the body of k_rsos where the folded block exists (Float64 results, 12 and 8 waves; RsSos::fold selects it per launch)
 template <int KS, int NW, typename TO, int CYC, bool FOLDABLE = false>
 __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const int* __restrict__ jend_g, const RsSos& g, TO* __restrict__ y,
                                           const RsGlobalTables& gsrc, int64_t G0, int64_t Gstep) {
-    constexpr bool HW = NW == 17;
     constexpr int NT = rsos_nthreads(NW);
-    constexpr int NY = NW >= 16 ? 10 : NW - 2, NL = NW == 16 ? 2 : 1, NX = 2 * NY + 1;
+    constexpr int NY = NW == 16 ? 10 : NW - 2, NL = NW == 16 ? 2 : 1, NX = 2 * NY + 1;
     // wave 0: chain; wave 4 (and 8 at 16 waves): loaders; the others: y waves (at 16 waves: ten of them -- one more on the
     // chain's SIMD, three on each of the others --, waves 13..15 have nothing to do)
     extern __shared__ double lds_raw[];
@@ -2195,7 +2091,7 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
         if (threadIdx.x == 0) {
             // (a group that projects its warm-ups walks none: the state entering block 0 is not there until the chain wave has
             //  made it -- the state counter says "before block 0" and the y wave of block 0 waits like any other)
-            const bool pj = NW != 16 && NW != 17 && rsos_wproj_group(sh, G);  // (the twelve- and eight-wave geometries)
+            const bool pj = NW != 16 && rsos_wproj_group(sh, G);  // (the twelve- and eight-wave geometries)
             sh.proj = pj ? 1 : 0;
             sh.wpe = pj ? 0 : g.wp;
             if (pj) sh.flags[kRsosFlagSseq] = -1;
@@ -2279,29 +2175,27 @@ __device__ __forceinline__ void rsos_body(const double* __restrict__ tab, const 
                 else rsos_loader<NY, NL, 1, false>(&sh, lds_raw, G, q);
                 break;
             }
-        } else if (HW && wave == 12) {
-            if (g.help && !(g.debug & 128)) rsos_helper<NY>(&sh, lds_raw);
         } else if (!(g.debug & 128))
             {
-            if (NW >= 16 && wave > 12) continue;
-            // (12 waves, and the helper geometry's sixteen: wave w sits on SIMD w % 4 and consecutive blocks go to consecutive
-            //  SIMDs -- residues 0 3 7 | 1 4 8 | 2 5 9 on SIMDs 1 | 2 | 3, 6 next to the chain.  Three consecutive residues on one
-            //  SIMD, tried for the helper geometry, cost the plain 12-wave form 4 %: the chain takes the blocks in order.)
+            if (NW == 16 && wave > 12) continue;
+            // (12 waves: wave w sits on SIMD w % 4 and consecutive blocks go to consecutive SIMDs -- residues 0 3 7 | 1 4 8 | 2 5 9
+            //  on SIMDs 1 | 2 | 3, 6 next to the chain.  Three consecutive residues on one SIMD cost this form 4 %: the chain
+            //  takes the blocks in order.)
             const int yi = NW == 16 ? (wave < 4 ? wave - 1 : wave < 8 ? wave - 2 : wave < 12 ? wave - 3 : 9) : wave - (wave > 4 ? 2 : 1);
             if (proj) rsos_wproj_y<NY>(&sh, lds_raw, G, yi);
             if constexpr (sizeof(TO) == 4 && CYC > 0) {
                 if (g.f32m) {
-                    rsos_ywave<KS, NY, NL, TO, CYC, true, HW>(&sh, lds_raw, G, yi);
+                    rsos_ywave<KS, NY, NL, TO, CYC, true>(&sh, lds_raw, G, yi);
                     continue;
                 }
             }
             if constexpr (FOLDABLE && sizeof(TO) == 8 && (NW == 12 || NW == 8)) {
                 if (g.fold) {
-                    rsos_ywave<KS, NY, NL, TO, CYC, false, false, true>(&sh, lds_raw, G, yi);
+                    rsos_ywave<KS, NY, NL, TO, CYC, false, true>(&sh, lds_raw, G, yi);
                     continue;
                 }
             }
-            rsos_ywave<KS, NY, NL, TO, CYC, false, HW>(&sh, lds_raw, G, yi);
+            rsos_ywave<KS, NY, NL, TO, CYC>(&sh, lds_raw, G, yi);
         }
     }
 }
@@ -2322,8 +2216,6 @@ __global__ __launch_bounds__(rsos_nthreads(NW)) void k_rsos_batch(const RsosItem
     rsos_body<KS, NW, TO, CYC>(I.tab, I.jend, I.g, (TO*)I.y, I.gsrc, (int64_t)(blockIdx.x % (unsigned)gpm), (int64_t)gpm);
 }
 
-constexpr size_t kRsosStaticLds = sizeof(RsosShared) + 64;
-
 #if SO_RSOS_ONLY_KS != 0
 template <int KS, int NW, typename TO, int CYC>
 static void launch_rsos_k(const double* tab, const int* jend, const RsSos& g, void* y, const RsGlobalTables& gsrc, int grid, hipStream_t st) {
@@ -2343,55 +2235,32 @@ static void launch_rsos_batch_k(const RsosItem* items, int nitems, int gpm, cons
     hipLaunchKernelGGL((k_rsos_batch<KS, NW, TO, 1>), dim3((unsigned)(nitems * gpm)), dim3(rsos_nthreads(NW)), lds, st, items, gpm);
 }
 
+// one (waves, cyc) of this window length: instantiated and launched where rsos_instantiated (sigops_internal.h) has it -- the
+// planner asks the same question
+template <int KS, int NW, typename TO, int CYC>
+static bool launch_rsos_c(const double* tab, const int* jend, const RsSos& g, void* y, const RsGlobalTables& gsrc, int grid, hipStream_t st) {
+    if constexpr ((SO_RSOS_ONLY_NW == 0 || SO_RSOS_ONLY_NW == NW) && rsos_instantiated(NW, CYC, KS)) {
+        if (g.nwaves == NW && g.cyc == CYC) {
+            launch_rsos_k<KS, NW, TO, CYC>(tab, jend, g, y, gsrc, grid, st);
+            return true;
+        }
+    }
+    return false;
+}
+// (the CYC listed here must cover every value rsos_instantiated accepts: 0, 1, 2, 3, 5)
+template <int KS, int NW, typename TO>
+static bool launch_rsos_w(const double* tab, const int* jend, const RsSos& g, void* y, const RsGlobalTables& gsrc, int grid, hipStream_t st) {
+    return launch_rsos_c<KS, NW, TO, 0>(tab, jend, g, y, gsrc, grid, st) || launch_rsos_c<KS, NW, TO, 1>(tab, jend, g, y, gsrc, grid, st) ||
+           launch_rsos_c<KS, NW, TO, 2>(tab, jend, g, y, gsrc, grid, st) || launch_rsos_c<KS, NW, TO, 3>(tab, jend, g, y, gsrc, grid, st) ||
+           launch_rsos_c<KS, NW, TO, 5>(tab, jend, g, y, gsrc, grid, st);
+}
 // returns 0 when launched, -1 if no instantiation fits
 template <int KS, typename TO>
 static int launch_rsos_t(const double* tab, const int* jend, const RsSos& g, void* y, const RsGlobalTables& gsrc, int grid, hipStream_t st) {
-    // (register taps: cyc * KS doubles per y wave -- up to 32 of them at 12 waves per workgroup (168 registers each), up
-    //  to 80 at 8 waves (256 registers))
-    if constexpr (SO_RSOS_ONLY_NW == 0 || SO_RSOS_ONLY_NW == 12) if (g.nwaves == 12) {
-        switch (g.cyc) {
-        case 0: launch_rsos_k<KS, 12, TO, 0>(tab, jend, g, y, gsrc, grid, st); return 0;
-        case 1: launch_rsos_k<KS, 12, TO, 1>(tab, jend, g, y, gsrc, grid, st); return 0;
-        case 2:
-            if constexpr (KS <= 16) {
-                launch_rsos_k<KS, 12, TO, 2>(tab, jend, g, y, gsrc, grid, st);
-                return 0;
-            }
-            return -1;
-        default: return -1;
-        }
-    }
-    if constexpr (SO_RSOS_ONLY_NW == 0 || SO_RSOS_ONLY_NW == 16) if (g.nwaves == 16) {
-        if (g.cyc != 1) return -1;
-        launch_rsos_k<KS, 16, TO, 1>(tab, jend, g, y, gsrc, grid, st);
-        return 0;
-    }
-    if constexpr (SO_RSOS_ONLY_NW == 0 || SO_RSOS_ONLY_NW == 17) if (g.nwaves == 17) {
-        if (g.cyc != 1) return -1;
-        launch_rsos_k<KS, 17, TO, 1>(tab, jend, g, y, gsrc, grid, st);
-        return 0;
-    }
-    if constexpr (SO_RSOS_ONLY_NW == 0 || SO_RSOS_ONLY_NW == 8) if (g.nwaves == 8) {
-        switch (g.cyc) {
-        case 0: launch_rsos_k<KS, 8, TO, 0>(tab, jend, g, y, gsrc, grid, st); return 0;
-        case 1: launch_rsos_k<KS, 8, TO, 1>(tab, jend, g, y, gsrc, grid, st); return 0;
-        case 2: launch_rsos_k<KS, 8, TO, 2>(tab, jend, g, y, gsrc, grid, st); return 0;
-        case 3:
-            if constexpr (KS <= 20) {
-                launch_rsos_k<KS, 8, TO, 3>(tab, jend, g, y, gsrc, grid, st);
-                return 0;
-            }
-            return -1;
-        case 5:
-            if constexpr (KS <= 16) {
-                launch_rsos_k<KS, 8, TO, 5>(tab, jend, g, y, gsrc, grid, st);
-                return 0;
-            }
-            return -1;
-        default: return -1;
-        }
-    }
-    return -1;
+    return launch_rsos_w<KS, 12, TO>(tab, jend, g, y, gsrc, grid, st) || launch_rsos_w<KS, 16, TO>(tab, jend, g, y, gsrc, grid, st) ||
+                   launch_rsos_w<KS, 8, TO>(tab, jend, g, y, gsrc, grid, st)
+               ? 0
+               : -1;
 }
 #endif  // SO_RSOS_ONLY_KS != 0
 
@@ -2422,17 +2291,16 @@ int SO_RSOS_CAT(SO_RSOS_CAT(launch_rsos_batch4, SO_RSOS_TAG), SO_RSOS_ONLY_NW)(c
 #else
 // LDS the kernel needs besides its static block (the planner sizes the ring with this); cyc > 0: no tap table
 size_t rsos_lds_bytes(int ngroups, int ks, int rpitch, int nwaves, int cyc) {
-    const int ny = nwaves >= 16 ? 10 : nwaves - 2, nx = 2 * ny + 1;
-    return ((cyc > 0 ? 0 : (size_t)ngroups * ks * 64) + (size_t)16 * rpitch + (size_t)nx * 192 + (size_t)rsos_nss(ny) * 192 + 16 * 16 * 2 +
-            (nwaves == 17 ? 3 * kRsosHslots * 64 : 0)) * 8;
+    const int ny = nwaves == 16 ? 10 : nwaves - 2, nx = 2 * ny + 1;
+    return ((cyc > 0 ? 0 : (size_t)ngroups * ks * 64) + (size_t)16 * rpitch + (size_t)nx * 192 + (size_t)rsos_nss(ny) * 192 + 16 * 16 * 2) * 8;
 }
+constexpr size_t kRsosStaticLds = sizeof(RsosShared) + 64;
 size_t rsos_lds_budget() { return 160 * 1024 - kRsosStaticLds; }
 
 #if SO_RSOS_ONLY_KS == 0
 #define SO_RS(KS_) \
     int launch_rsos_ks##KS_##d12(SO_RSOS_ARGS); int launch_rsos_ks##KS_##d16(SO_RSOS_ARGS); int launch_rsos_ks##KS_##d8(SO_RSOS_ARGS); \
-    int launch_rsos_ks##KS_##f12(SO_RSOS_ARGS); int launch_rsos_ks##KS_##f16(SO_RSOS_ARGS); int launch_rsos_ks##KS_##f8(SO_RSOS_ARGS); \
-    int launch_rsos_ks##KS_##d17(SO_RSOS_ARGS); int launch_rsos_ks##KS_##f17(SO_RSOS_ARGS);
+    int launch_rsos_ks##KS_##f12(SO_RSOS_ARGS); int launch_rsos_ks##KS_##f16(SO_RSOS_ARGS); int launch_rsos_ks##KS_##f8(SO_RSOS_ARGS);
 SO_RS(4) SO_RS(12) SO_RS(13) SO_RS(14) SO_RS(16) SO_RS(20)
 #undef SO_RS
 #endif
@@ -2470,7 +2338,6 @@ int launch_rsos(SO_RSOS_ARGS) {
         if (g.nwaves == 12) return g.out_f32 ? launch_rsos_ks##KS_##f12(tab, jend, g, y, gsrc, grid, st) : launch_rsos_ks##KS_##d12(tab, jend, g, y, gsrc, grid, st); \
         if (g.nwaves == 16) return g.out_f32 ? launch_rsos_ks##KS_##f16(tab, jend, g, y, gsrc, grid, st) : launch_rsos_ks##KS_##d16(tab, jend, g, y, gsrc, grid, st); \
         if (g.nwaves == 8) return g.out_f32 ? launch_rsos_ks##KS_##f8(tab, jend, g, y, gsrc, grid, st) : launch_rsos_ks##KS_##d8(tab, jend, g, y, gsrc, grid, st);    \
-        if (g.nwaves == 17) return g.out_f32 ? launch_rsos_ks##KS_##f17(tab, jend, g, y, gsrc, grid, st) : launch_rsos_ks##KS_##d17(tab, jend, g, y, gsrc, grid, st); \
         return -1;                                                                                                                 \
     }
 #else

@@ -384,7 +384,7 @@ struct RsSos {
     int32_t ulo;          // input frame (relative to a period's first input) of ring position 0, before the row's alignment shift
     int32_t ct, rgs;      // channels x ranges per sequence group, ct * rgs == 16
     int32_t nch;
-    int32_t nwaves;       // 8, 12 or 16: wave 0 chain, waves 4, 8, 12 loaders, the others y waves
+    int32_t nwaves;       // 8, 12 or 16: wave 0 chain, wave 4 (and 8 at 16 waves) loaders, the others y waves
     int32_t ring;         // input ring per row in LDS, frames (power of two, multiple of chunk)
     int32_t rpitch;       // doubles between ring rows (ring + 2: rows on different banks)
     int32_t chunk;        // frames per row and LDS-DMA instruction: 128 or 64
@@ -404,8 +404,6 @@ struct RsSos {
     int32_t sring;        // f32m with the fast path's step v + m / v - m: the loader writes m (Float32, once per unit and chunk) into the
                           // free half of the unit's first ring row and the y waves add it to their window operands
     int32_t gsplit;       // 16 waves, groups of 2 / 4 channels with a fused step: the step is applied by waves 13 / 14 (k_rsos.hip, MODE)
-    int32_t help;         // 12 waves, taps in registers: three y waves hand their X blocks to the y wave on the chain's SIMD, which
-                          // forms D . X for them (k_rsos.hip, kRsosHres*: the SIMDs' MFMA counts evened out)
     int32_t debug;        // ablation bits (SIGOPS_RSOS_DEBUG): 1 no stores, 2 no gain, 4 chain does not wait for x, 8 y waves not for states, 16 nor for input, 32 loader not for ring space
     int32_t cyc;          // > 0: a y wave's blocks cycle through cyc phase groups whose taps it keeps in registers; 0: tap table in LDS
     int32_t arr2;         // the fast path's step takes a SECOND array as its operand (DCarrier::base2): the loader's A2 instantiation
@@ -431,6 +429,15 @@ struct RsSos {
                           // the block lower triangular A^16 (k_rsos.hip, rsos_chain4); its six blocks as A operands in `mats`, from
                           // this double on (stages.cpp, rsos_chain4_operands).  The filter's alone: every geometry and form takes it.
 };
+// The (waves, phase groups per y wave, window k-steps) k_rsos has a kernel for -- what launch_rsos_t instantiates and what the
+// planner may choose (register taps: cyc * ks doubles per y wave -- up to 32 of them at 12 waves per workgroup, 168 registers
+// each; up to 80 at 8 waves, 256 registers; 16 waves keep one group's)
+constexpr bool rsos_instantiated(int nw, int cyc, int ks) {
+    return nw == 12 ? (cyc == 0 || cyc == 1 || (cyc == 2 && ks <= 16))
+         : nw == 16 ? cyc == 1
+         : nw == 8  ? (cyc == 0 || cyc == 1 || cyc == 2 || (cyc == 3 && ks <= 20) || (cyc == 5 && ks <= 16))
+                    : false;
+}
 // lane l of an A operand of v_mfma_f64_4x4x4_4b_f64 holds A_b[i][k] with i = l & 3, k = l >> 4 (b = (l >> 2) & 3: the chain's
 // blocks are the same in all four); tools/micro/mfma64_chain.hip prints the map
 constexpr int rsos_c4_a_i(int lane) { return lane & 3; }
