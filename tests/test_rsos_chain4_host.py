@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import rsos_matrix
 import sigops_amd as so
 from sigops_amd import FilterFn, _capi
 
@@ -25,6 +26,12 @@ DESIGNS = [HEADLINE] + [("bandstop", ("butterworth", n), (500.0, 2000.0)) for n 
     + [("lowpass", ("butterworth", n), (3000.0,)) for n in (1, 2, 3, 5, 7, 8, 9, 11, 12)] \
     + [("highpass", ("butterworth", n), (200.0,)) for n in (2, 4, 6, 7, 10, 12)] \
     + [("lowpass", ("chebyshev1", 9, 1.0), (5000.0,))]
+# the Chebyshev and the slow high-pass designs of the fused kernel's matrix (tests/rsos_matrix.py), at 44.1 -> 48 kHz: cutoffs in Hz
+# at 48 kHz.  (Appended: the designs above keep their test ids.)
+MATRIX_DESIGNS = [(d.kind, d.method, d.hz((44.1, 48.0))) for d in rsos_matrix.DESIGNS
+                  if d.method[0] == "chebyshev1" or (d.kind == "highpass" and not d.absolute and d.bounds[0] <= 0.005)]
+assert len(MATRIX_DESIGNS) == 4 + 6
+DESIGNS = DESIGNS + MATRIX_DESIGNS
 
 
 def chain_blocks(sos, gain):
@@ -58,7 +65,7 @@ def a16_reference(sos):
 
 
 def ids(d):
-    return f"{d[0]}-{d[1][0]}{d[1][1]}"
+    return f"{d[0]}-{d[1][0]}{d[1][1]}" + (f"@{d[2][0]:g}Hz" if d in MATRIX_DESIGNS else "")
 
 
 @pytest.mark.parametrize("design", DESIGNS, ids=ids)
