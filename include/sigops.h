@@ -357,6 +357,26 @@ typedef enum so_rskind {
  *            l0 < 0, l1 < 0 or a d0 that is NaN or outside [0, 1] is SO_ERR_INVALID; an integer child, or a window of
  *            min(l0, frames read) + min(l1, frames read) > 1024 frames beside frame n (one form is built: the tile and its
  *            halo in LDS), SO_ERR_UNSUPPORTED.
+ *
+ * Carried state (COMB, CUMSUM, RECUR, RECUR2; a stream that keeps only a tail of its input, DESIGN.md "Streaming the
+ * device-only nodes").  Their otherwise unused fields let a plan start such a node in the middle of its signal:
+ *            s0 = r, the resume frame: the stage computes the frames [r, frames read) from the children's frames from r on and
+ *            touches nothing before r.  0 = from rest.  A multiple of 16384 (the chunk) for CUMSUM / RECUR / RECUR2, any
+ *            frame for COMB.
+ *            p0 = the carry-in record, Float64 in DEVICE memory: the state that enters frame r.  Read only where r > 0.
+ *            p1 = the carry-out record, of the same layout, in device memory, not p0: once an execute has run it holds the
+ *            state that enters the frame SO_COUNTER_CARRY_FRAME_FIRST + k reports.  0 = none wanted.  p0 is never
+ *            written, so executing a plan twice gives the same bytes in the result and in p1.
+ *            Records: CUMSUM [nch], the running total; RECUR [nch], the carry C; RECUR2 [nch][2], the state (s0, s1) as the
+ *            carry over the chunks leaves it (composites applied in double-doubles -- NOT the last two outputs, whose bits
+ *            differ); COMB [nch][D][2], (x, y) of the last frame of every residue class n mod D before r, +0.0 where a
+ *            class has none.  For the three scans p1 is written only where the frames read reach into a later chunk than
+ *            r's (the reported frame says so).
+ *            A node with s0 = 0, p0 = p1 = NULL is the node as described above.  s0 < 0, an s0 that is not a multiple of the
+ *            chunk (the scans), s0 > 0 without p0, p1 == p0, or an s0 beyond the frames read is SO_ERR_INVALID; a reader of
+ *            the node's frames before s0 is SO_ERR_LENGTH (they are not computed again), and the message of that refusal --
+ *            of no other -- ends in "[resume node N]", N the node's index in the table: a stream that keeps an older
+ *            carry-in record reads N there and plans again with that node resumed from it.
  */
 typedef struct so_node {
     int32_t kind;            /* so_kind_t                                              */
@@ -487,8 +507,17 @@ typedef enum so_counter {
     SO_COUNTER_WPROJ_FIRST = 9,         /* the first of them, counted from the warm-up's first period (may be < 0)   */
     SO_COUNTER_RSOS_FOLD = 10, /* 1: the fused resampler + IIR kernel runs its folded block -- the cascade's zero-state response
                                * folded into the tap table, 4 MFMAs fewer per block (0: the unfolded block, or no such launch) */
-    SO_COUNTER_RSOS_CHAIN4 = 11 /* 1: the fused kernel's chain wave runs its recurrence on the 4 x 4 x 4 matrix shape, one
-                                 * instruction per block of the block-triangular A^16 (0: three 16 x 16 x 4, or no such launch) */
+    SO_COUNTER_RSOS_CHAIN4 = 11, /* 1: the fused kernel's chain wave runs its recurrence on the 4 x 4 x 4 matrix shape, one
+                                  * instruction per block of the block-triangular A^16 (0: three 16 x 16 x 4, or no such launch) */
+    /* the nodes that carry a stream's state ("Carried state" above: s0 > 0 or p1 set), numbered k = 0 .. in node-table order: */
+    SO_COUNTER_CARRY_NODES = 12,           /* how many there are                                                      */
+    SO_COUNTER_CARRY_NODE_FIRST = 1000,    /* + k: the index of the k-th in the node table                            */
+    SO_COUNTER_CARRY_FRAME_FIRST = 2000000, /* + k: the frame whose entering state the k-th node's carry-out record (p1)
+                                            * holds once an execute has run: the first frame of the last chunk read for
+                                            * CUMSUM / RECUR / RECUR2, the number of frames read for COMB; s0 where nothing
+                                            * advanced, no record was asked for or nobody reads the node */
+    SO_COUNTER_CARRY_NEED_FIRST = 4000000  /* + k: the frames [0, need) of the k-th node that the plan reads (0: nobody reads it);
+                                            * the rule above is need for COMB, max(s0, (need - 1) / 16384 * 16384) for the scans */
 } so_counter_t;
 int64_t so_plan_counter(const so_plan_t* plan, int32_t which);
 

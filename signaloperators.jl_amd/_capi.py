@@ -32,6 +32,8 @@ PAD = {"value": 0, "vector": 1, "zero": 2, "one": 3, "lastframe": 4, "cycle": 5,
 RS_RATIONAL, RS_ARBITRARY, RS_FIR = 0, 1, 2
 FILT = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}
 METHOD = {"butterworth": 0, "chebyshev1": 1}
+# so_counter_t: the nodes that carry a stream's state (include/sigops.h, "Carried state")
+COUNTER_CARRY_NODES, COUNTER_CARRY_NODE_FIRST, COUNTER_CARRY_FRAME_FIRST, COUNTER_CARRY_NEED_FIRST = 12, 1000, 2000000, 4000000
 
 
 class so_node_t(C.Structure):

@@ -129,9 +129,9 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
         return (S.need - S.base) * ((int64_t)P->nodes[N.kids[1]].nch * 8 + (int64_t)N.nch * (taps * kid_esz(0) + 8));
     }
     case ST_COMB:  // per sample: one read where x lies, one Float64 written
-        return S.need * (int64_t)N.nch * (kid_esz(0) + 8);
+        return (S.need - S.base) * (int64_t)N.nch * (kid_esz(0) + 8);
     case ST_CUMSUM:  // per sample: two reads where x lies (the totals' pass and the scan's), one Float64 written
-        return S.need * (int64_t)N.nch * (2 * kid_esz(0) + 8);
+        return (S.need - S.base) * (int64_t)N.nch * (2 * kid_esz(0) + 8);
     case ST_MOVING:  // the frames read where x lies (the long form's second and third reads and the tile halos left out), one sample of x's type written
         return (S.in_frames + (S.need - S.base)) * (int64_t)N.nch * esz;
     case ST_MOVRANK:  // the frames read where x lies (the tile halos left out), one sample of x's type written
@@ -141,13 +141,13 @@ static int64_t stage_step_bytes(const Plan* P, int sid) {
     case ST_RECUR: {  // per sample: b read twice where it lies (the totals' pass and the scan's), a row of a twice as Float64, one Float64 written
         const bool row = N.kids.size() == 2;
         const int64_t a_rows = !row ? 0 : S.side[0].pitch == 0 ? 1 : N.nch;
-        return S.need * ((int64_t)N.nch * (2 * kid_esz(row ? 1 : 0) + 8) + a_rows * 16);
+        return (S.need - S.base) * ((int64_t)N.nch * (2 * kid_esz(row ? 1 : 0) + 8) + a_rows * 16);
     }
     case ST_RECUR2: {  // per sample: b read twice where it lies, each row of a1 and of a2 twice as Float64, one Float64 written
         const bool row = N.kids.size() == 3;
         int64_t a_rows = 0;
         for (int w = 0; row && w < 2; ++w) a_rows += S.side[w].pitch == 0 ? 1 : N.nch;
-        return S.need * ((int64_t)N.nch * (2 * kid_esz(row ? 2 : 0) + 8) + a_rows * 16);
+        return (S.need - S.base) * ((int64_t)N.nch * (2 * kid_esz(row ? 2 : 0) + 8) + a_rows * 16);
     }
     default: return (S.need - S.base) * N.nch * esz;
     }
@@ -829,7 +829,10 @@ static int run_comb(Plan* P, const Step& s, void* outp, hipStream_t st) {
     a.x_f32 = xdt == SO_F32;
     a.y = (double*)out.d;
     a.ycs = out.pitch;
-    a.n = S.need;
+    a.n = S.need - S.base;  // (a carried state: the rows start at the resume frame, Plan::process_from_frame_0)
+    a.r = S.base;
+    a.cin = (const double*)N.nd.p0;
+    a.cout = (double*)const_cast<void*>(N.nd.p1);
     a.D = N.nd.l0;
     a.b0 = N.nd.d0;
     a.bD = N.nd.d1;
@@ -854,9 +857,12 @@ static int run_cumsum(Plan* P, const Step& s, void* outp, hipStream_t st) {
     a.x_f32 = xdt == SO_F32;
     a.y = (double*)out.d;
     a.ycs = out.pitch;
-    a.n = S.need;
+    a.n = S.need - S.base;  // (a carried state: the rows start at the resume frame, Plan::process_from_frame_0)
+    a.k0 = S.base / kCumsumChunk;
+    a.cin = (const double*)N.nd.p0;
+    a.cout = (double*)const_cast<void*>(N.nd.p1);
     a.nch = N.nch;
-    a.tot_pitch = cumsum_totals(S.need);
+    a.tot_pitch = cumsum_totals(a.n);
     a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
     const int nl = launch_cumsum(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
@@ -887,10 +893,13 @@ static int run_recur(Plan* P, const Step& s, void* outp, hipStream_t st) {
     }
     a.y = (double*)out.d;
     a.ycs = out.pitch;
-    a.n = S.need;
+    a.n = S.need - S.base;  // (a carried state: the rows start at the resume frame, Plan::process_from_frame_0)
+    a.k0 = S.base / kCumsumChunk;
+    a.cin = (const double*)N.nd.p0;
+    a.cout = (double*)const_cast<void*>(N.nd.p1);
     a.nch = N.nch;
     a.op = N.nd.i0;
-    a.tot_pitch = cumsum_totals(S.need);
+    a.tot_pitch = cumsum_totals(a.n);
     a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
     const int nl = launch_recur(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
@@ -923,9 +932,12 @@ static int run_recur2(Plan* P, const Step& s, void* outp, hipStream_t st) {
     }
     a.y = (double*)out.d;
     a.ycs = out.pitch;
-    a.n = S.need;
+    a.n = S.need - S.base;  // (a carried state: the rows start at the resume frame, Plan::process_from_frame_0)
+    a.k0 = S.base / kCumsumChunk;
+    a.cin = (const double*)N.nd.p0;
+    a.cout = (double*)const_cast<void*>(N.nd.p1);
     a.nch = N.nch;
-    a.tot_pitch = cumsum_totals(S.need);
+    a.tot_pitch = cumsum_totals(a.n);
     a.tot = S.aux_buf >= 0 ? (double*)P->bufs[S.aux_buf].d : nullptr;
     const int nl = launch_recur2(a, st);
     // (one workgroup per chunk of kCumsumChunk frames in grid.x, the channels in grid.y)
@@ -1618,8 +1630,20 @@ int64_t plan_counter(const Plan* P, int which) {
                 return which == SO_COUNTER_RSOS_RANGE_PERIODS ? S.rs.pr : which == SO_COUNTER_RSOS_WARMUP_PERIODS ? S.rs.wp
                      : which == SO_COUNTER_RSOS_PERIOD_INPUTS ? S.rs.M : which == SO_COUNTER_WPROJ_FRAMES ? S.rs.wk : S.rs.wj0;
         return 0;
-    default: return -1;
+    default: break;
     }
+    // the nodes that carry a stream's state, in node-table order: how many, which, and where their carry-out records stand
+    const int64_t nc = (int64_t)P->carry_nodes.size();
+    if (which == SO_COUNTER_CARRY_NODES) return nc;
+    for (const int64_t first : {(int64_t)SO_COUNTER_CARRY_NODE_FIRST, (int64_t)SO_COUNTER_CARRY_FRAME_FIRST, (int64_t)SO_COUNTER_CARRY_NEED_FIRST}) {
+        if (which < first || which >= first + nc) continue;
+        const int ni = P->carry_nodes[(size_t)(which - first)];
+        if (first == SO_COUNTER_CARRY_NODE_FIRST) return ni;
+        for (const Stage& S : P->stages)
+            if (S.node == ni && S.processed) return first == SO_COUNTER_CARRY_NEED_FIRST ? S.need : S.carried;
+        return first == SO_COUNTER_CARRY_NEED_FIRST ? 0 : P->nodes[ni].nd.s0;  // (nobody reads the node: nothing ran)
+    }
+    return -1;
 }
 int plan_step_info(const Plan* P, int index, so_step_info_t* info) {
     if (info && index >= 0 && index < (int)P->steps.size()) {

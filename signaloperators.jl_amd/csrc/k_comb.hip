@@ -14,6 +14,13 @@
 // address is formed (k_sample_at.hip clamps its table index the same way) and stores under a guard: no lane forms an
 // address outside its row for any D, a.n or r.  Frame arithmetic is 64-bit throughout; launch_comb passes D <= a.n (a
 // longer delay leaves every class with one frame, as D = a.n does), so n + kCombUnroll * D cannot overflow.
+//
+// The resumed form (k_comb_resume; CombArgs::r, cin, cout; a stream's push): the rows start at frame r of the signal and
+// lane j walks the class of frame r + j, residue (r + j) mod D, from the (xd, yd) its entry of the record cin holds --
+// the x and the y of the class's last frame before r, +0.0 where it has none -- and leaves the pair it ends with in cout.
+// The grid runs over all D classes, not min(D, n): a class without a frame in [r, r + n) -- a delay longer than what a push
+// adds -- copies its entry from cin to cout.  cin and cout are different records and every entry of cout is written by
+// exactly one lane with plain stores, so the same launch twice gives the same bytes.  launch_comb takes D < 2^40 there.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -30,16 +37,13 @@ __device__ __forceinline__ double comb_step(double x0, double& xd, double& yd, d
     return t;
 }
 
+// the frames r, r + D, r + 2D, ... <= a.n - 1 of channel c, from (xd, yd), which leave as the class's last x and y
 template <typename TX, bool FF, bool FB>
-__global__ __launch_bounds__(kBlock) void k_comb(CombArgs a) {
-    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (r >= a.D || r >= a.n) return;
-    const int c = blockIdx.y;
+__device__ __forceinline__ void comb_walk(const CombArgs& a, int c, int64_t r, double& xd, double& yd) {
     const TX* __restrict__ xc = (const TX*)a.x + (int64_t)c * a.xcs;
     double* __restrict__ yr = a.y + (int64_t)c * a.ycs;
     const int64_t D = a.D, xfs = a.xfs, last = a.n - 1;
     const double b0 = a.b0, bD = a.bD, g = a.a;
-    double xd = 0.0, yd = 0.0;
     int64_t n = r;
     TX v[kCombUnroll];
     while (n + (kCombUnroll - 1) * D <= last) {  // kCombUnroll whole steps
@@ -62,9 +66,36 @@ __global__ __launch_bounds__(kBlock) void k_comb(CombArgs a) {
     }
 }
 
+template <typename TX, bool FF, bool FB>
+__global__ __launch_bounds__(kBlock) void k_comb(CombArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= a.D || r >= a.n) return;
+    double xd = 0.0, yd = 0.0;
+    comb_walk<TX, FF, FB>(a, blockIdx.y, r, xd, yd);
+}
+
+template <typename TX, bool FF, bool FB>
+__global__ __launch_bounds__(kBlock) void k_comb_resume(CombArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= a.D) return;
+    const int c = blockIdx.y;
+    const int64_t e = 2 * ((int64_t)c * a.D + (a.r + j) % a.D);  // the entry of the class of frame r + j
+    double xd = 0.0, yd = 0.0;
+    if (a.cin != nullptr) xd = a.cin[e], yd = a.cin[e + 1];
+    if (j < a.n) comb_walk<TX, FF, FB>(a, c, j, xd, yd);
+    if (a.cout != nullptr) a.cout[e] = xd, a.cout[e + 1] = yd;
+}
+
 template <typename TX>
 static void launch_comb_t(const CombArgs& a, dim3 grid, hipStream_t st) {
     const bool ff = a.bD != 0.0, fb = a.a != 0.0;
+    if (a.r > 0 || a.cout != nullptr) {
+        if (ff && fb) hipLaunchKernelGGL((k_comb_resume<TX, true, true>), grid, dim3(kBlock), 0, st, a);
+        else if (ff) hipLaunchKernelGGL((k_comb_resume<TX, true, false>), grid, dim3(kBlock), 0, st, a);
+        else if (fb) hipLaunchKernelGGL((k_comb_resume<TX, false, true>), grid, dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((k_comb_resume<TX, false, false>), grid, dim3(kBlock), 0, st, a);
+        return;
+    }
     if (ff && fb) hipLaunchKernelGGL((k_comb<TX, true, true>), grid, dim3(kBlock), 0, st, a);
     else if (ff) hipLaunchKernelGGL((k_comb<TX, true, false>), grid, dim3(kBlock), 0, st, a);
     else if (fb) hipLaunchKernelGGL((k_comb<TX, false, true>), grid, dim3(kBlock), 0, st, a);
@@ -74,8 +105,12 @@ static void launch_comb_t(const CombArgs& a, dim3 grid, hipStream_t st) {
 int launch_comb(const CombArgs& a0, hipStream_t st) {
     if (a0.n <= 0 || a0.nch <= 0) return 0;
     if (a0.D < 1 || a0.nch > 65535) return -1;
+    if (a0.r < 0 || (a0.r > 0 && a0.cin == nullptr)) return -1;
     CombArgs a = a0;
-    a.D = a.D < a.n ? a.D : a.n;  // (a delay of a.n frames or more: every class is its first frame)
+    if (a.r == 0) a.cin = nullptr;  // (from rest: no record is read)
+    const bool resumed = a.r > 0 || a.cout != nullptr;
+    if (resumed && a.D >= ((int64_t)1 << 40)) return -1;  // (the records have 2 D doubles a channel; n + kCombUnroll * D stays in range)
+    if (!resumed) a.D = a.D < a.n ? a.D : a.n;  // (a delay of a.n frames or more: every class is its first frame)
     const int64_t nblocks = (a.D + kBlock - 1) / kBlock;
     if (nblocks >= ((int64_t)1 << 31)) return -1;
     const dim3 grid((unsigned)nblocks, (unsigned)a.nch);

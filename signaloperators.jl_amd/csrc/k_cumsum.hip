@@ -15,6 +15,12 @@
 //   k_cumsum_scan    one workgroup per (chunk, channel): the chunk-local scan again, + tot[chunk - 1], stored
 // A signal of one chunk is the third launch alone.
 //
+// The resumed form (CumsumArgs::k0 > 0, a stream's push): the rows start at chunk k0 of the signal, so blockIdx.x is the
+// chunk number relative to k0 and so is the index into tot; the carry starts from cin, the total that enters chunk k0,
+// instead of from the first total, and the scan of the first chunk adds cin.  "The signal's chunk 0", which adds no carry,
+// is keyed on the absolute chunk: relative chunk 0 without a cin.  The carry leaves the total that enters the last chunk
+// in cout (one plain store a channel), never in cin: the same launch twice gives the same bytes.
+//
 // A workgroup is kCumsumWaves waves; a wave takes kCumsumTiles / kCumsumWaves consecutive tiles, one after the other, a
 // lane one run of each and keeps its 16 values in registers until the tile carries are known (one barrier).  A lane's run
 // is 128 contiguous bytes, so x is not loaded in run order: a full tile of a unit-stride, 16-byte aligned row is loaded 16
@@ -84,10 +90,11 @@ __global__ __launch_bounds__(64 * kCumsumWaves) void k_cumsum_totals(CumsumArgs 
 
 // The carries: tot[k] <- tot[0] + ... + tot[k], summed in that order, per channel (blockIdx.x), in place.  The totals go
 // through LDS kBlock at a time; lane 0 reads 16 of them, adds, writes 16.
-__global__ __launch_bounds__(kBlock) void k_cumsum_carry(double* tot, int64_t pitch, int64_t count) {
+__global__ __launch_bounds__(kBlock) void k_cumsum_carry(double* tot, int64_t pitch, int64_t count, const double* cin, double* cout) {
     __shared__ double in[kBlock], out[kBlock];
     double* row = tot + (int64_t)blockIdx.x * pitch;
-    double s = 0.0;  // (lane 0's; replaced, not added to, by the first total)
+    const bool resumed = cin != nullptr;
+    double s = resumed ? cin[blockIdx.x] : 0.0;  // (lane 0's; from rest: replaced, not added to, by the first total)
     for (int64_t k0 = 0; k0 < count; k0 += kBlock) {
         const int64_t k = k0 + threadIdx.x;
         if (k < count) in[threadIdx.x] = row[k];
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_cumsum_carry(double* tot, int64_t pi
                 for (int j = 0; j < 16; ++j) w[j] = in[j0 + j];
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    s = (k0 == 0 && j0 == 0 && j == 0) ? w[0] : s + w[j];
+                    s = (!resumed && k0 == 0 && j0 == 0 && j == 0) ? w[0] : s + w[j];
                     out[j0 + j] = s;
                 }
             }
@@ -108,6 +115,9 @@ __global__ __launch_bounds__(kBlock) void k_cumsum_carry(double* tot, int64_t pi
         __syncthreads();
         if (k < count) row[k] = out[threadIdx.x];
     }
+    // the total that enters chunk `count`, the last one: the last entry written (lane 0's s has run on over the rest of its
+    // group of 16, which nobody reads); lane 0 wrote `out` itself and count >= 1
+    if (threadIdx.x == 0 && cout != nullptr) cout[blockIdx.x] = out[(count - 1) % kBlock];
 }
 
 // Pass 2: chunk blockIdx.x of channel blockIdx.y, stored.
@@ -136,8 +146,8 @@ __global__ __launch_bounds__(64 * kCumsumWaves) void k_cumsum_scan(CumsumArgs a)
     // the carry into the wave's first tile: the last value of the tile before it, summed tile after tile
     double cy = 0.0;
     for (int k = 0; k < wave * kCumsumPerWave; ++k) cy = k == 0 ? total[0] : cy + total[k];
-    const bool chunks_before = chunk > 0;
-    const double C = chunks_before ? a.tot[(int64_t)c * a.tot_pitch + chunk - 1] : 0.0;
+    const bool chunks_before = chunk > 0 || a.cin != nullptr;  // (the absolute chunk: launch_cumsum passes cin where k0 > 0 only)
+    const double C = chunk > 0 ? a.tot[(int64_t)c * a.tot_pitch + chunk - 1] : a.cin != nullptr ? a.cin[c] : 0.0;
 #pragma unroll
     for (int i = 0; i < kCumsumPerWave; ++i) {
         const int64_t f0 = f00 + (int64_t)i * kCumsumTile;
@@ -168,7 +178,7 @@ static void launch_cumsum_t(const CumsumArgs& a, int64_t nchunks, hipStream_t st
         const dim3 grid((unsigned)(nchunks - 1), (unsigned)a.nch);
         if (vl) hipLaunchKernelGGL((k_cumsum_totals<TX, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_cumsum_totals<TX, false>), grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_cumsum_carry, dim3((unsigned)a.nch), dim3(kBlock), 0, st, a.tot, a.tot_pitch, nchunks - 1);
+        hipLaunchKernelGGL(k_cumsum_carry, dim3((unsigned)a.nch), dim3(kBlock), 0, st, a.tot, a.tot_pitch, nchunks - 1, a.cin, a.cout);
     }
     const dim3 grid((unsigned)nchunks, (unsigned)a.nch);
     if (vl && vs) hipLaunchKernelGGL((k_cumsum_scan<TX, true, true>), grid, block, 0, st, a);
@@ -177,8 +187,11 @@ static void launch_cumsum_t(const CumsumArgs& a, int64_t nchunks, hipStream_t st
     else hipLaunchKernelGGL((k_cumsum_scan<TX, false, false>), grid, block, 0, st, a);
 }
 
-int launch_cumsum(const CumsumArgs& a, hipStream_t st) {
-    if (a.n <= 0 || a.nch <= 0) return 0;
+int launch_cumsum(const CumsumArgs& a0, hipStream_t st) {
+    if (a0.n <= 0 || a0.nch <= 0) return 0;
+    if (a0.k0 < 0 || (a0.k0 > 0 && a0.cin == nullptr)) return -1;
+    CumsumArgs a = a0;
+    if (a.k0 == 0) a.cin = nullptr;  // (from rest: no record is read)
     const int64_t nchunks = (a.n + kCumsumChunk - 1) / kCumsumChunk;
     if (a.nch > 65535 || nchunks >= ((int64_t)1 << 31)) return -1;
     if (nchunks > 1 && (a.tot == nullptr || a.tot_pitch < nchunks - 1)) return -1;

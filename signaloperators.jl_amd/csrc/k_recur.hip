@@ -17,6 +17,10 @@
 //   k_recur_scan    one workgroup per (chunk, channel): the chunk-local scan again, C applied, stored
 // A signal of one chunk is the third launch alone.
 //
+// The resumed form (RecurArgs::k0 > 0, a stream's push) is k_cumsum.hip's: the rows start at chunk k0, blockIdx.x and the
+// index into tot are relative to it, the carry starts from cin, the C that enters chunk k0, and leaves the C that enters
+// the last chunk in cout; "chunk 0 of the signal" (y[0] = b[0], no C applied) is relative chunk 0 without a cin.
+//
 // A lane holds the 16 p and the 16 r of its run: 64 VGPRs a tile, so the four tiles a wave that k_cumsum keeps in
 // registers do not fit.  A workgroup is sixteen waves instead, a wave ONE tile of the chunk: both inputs are read once a
 // pass, nothing is reloaded, and one barrier separates the tile scans from the carries.  A wave's LDS image (kscan.h)
@@ -112,10 +116,11 @@ __global__ __launch_bounds__(64 * kRecurWaves) void k_recur_totals(RecurArgs g) 
 // chunk k + 1 starts from: C[0] = u[last] of chunk 0, C[k] = J(Q[last], C[k - 1], u[last]).  The pairs go through LDS
 // kBlock at a time; lane 0 walks them.
 template <int OP>
-__global__ __launch_bounds__(kBlock) void k_recur_carry(double* tot, int64_t pitch, int64_t count) {
+__global__ __launch_bounds__(kBlock) void k_recur_carry(double* tot, int64_t pitch, int64_t count, const double* cin, double* cout) {
     __shared__ double q[kBlock], u[kBlock];
     double* row = tot + 2 * (int64_t)blockIdx.x * pitch;
-    double C = 0.0;  // (lane 0's; replaced, not joined, by the first chunk's)
+    const bool resumed = cin != nullptr;
+    double C = resumed ? cin[blockIdx.x] : 0.0;  // (lane 0's; from rest: replaced, not joined, by the first chunk's)
     for (int64_t k0 = 0; k0 < count; k0 += kBlock) {
         const int64_t k = k0 + threadIdx.x;
         if (k < count) q[threadIdx.x] = row[2 * k], u[threadIdx.x] = row[2 * k + 1];
@@ -123,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void k_recur_carry(double* tot, int64_t pit
         if (threadIdx.x == 0) {
             const int m = (int)(count - k0 < kBlock ? count - k0 : kBlock);  // (the entries past m are not read back)
             for (int j = 0; j < m; ++j) {
-                C = (k0 == 0 && j == 0) ? u[0] : rc_join<OP>(q[j], C, u[j]);
+                C = (!resumed && k0 == 0 && j == 0) ? u[0] : rc_join<OP>(q[j], C, u[j]);
                 u[j] = C;
             }
         }
@@ -131,6 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_recur_carry(double* tot, int64_t pit
         if (k < count) row[2 * k + 1] = u[threadIdx.x];
         __syncthreads();
     }
+    if (threadIdx.x == 0 && cout != nullptr) cout[blockIdx.x] = C;  // the C that enters chunk `count`, the last one
 }
 
 // Pass 2: chunk blockIdx.x of channel blockIdx.y, stored.
@@ -154,7 +160,7 @@ __global__ __launch_bounds__(64 * kRecurWaves) void k_recur_scan(RecurArgs g) {
     }
     __syncthreads();
     if (!exists) return;
-    const bool chunks_before = chunk > 0;
+    const bool chunks_before = chunk > 0 || g.cin != nullptr;  // (the absolute chunk: launch_recur passes cin where k0 > 0 only)
     if (wave > 0) {
         double P, cy;
         rc_carry<OP>(tq, tt, wave, P, cy);
@@ -165,7 +171,7 @@ __global__ __launch_bounds__(64 * kRecurWaves) void k_recur_scan(RecurArgs g) {
         }
     }
     if (chunks_before) {
-        const double C = g.tot[2 * ((int64_t)c * g.tot_pitch + chunk - 1) + 1];
+        const double C = chunk > 0 ? g.tot[2 * ((int64_t)c * g.tot_pitch + chunk - 1) + 1] : g.cin[c];
 #pragma unroll
         for (int m = 0; m < kCumsumRun; ++m) r[m] = rc_join<OP>(p[m], C, r[m]);
     }
@@ -186,7 +192,7 @@ static void launch_recur_t(const RecurArgs& g, int64_t nchunks, hipStream_t st) 
         const dim3 grid((unsigned)(nchunks - 1), (unsigned)g.nch);
         if (vl) hipLaunchKernelGGL((k_recur_totals<OP, TB, AROW, true>), grid, block, 0, st, g);
         else hipLaunchKernelGGL((k_recur_totals<OP, TB, AROW, false>), grid, block, 0, st, g);
-        hipLaunchKernelGGL((k_recur_carry<OP>), dim3((unsigned)g.nch), dim3(kBlock), 0, st, g.tot, g.tot_pitch, nchunks - 1);
+        hipLaunchKernelGGL((k_recur_carry<OP>), dim3((unsigned)g.nch), dim3(kBlock), 0, st, g.tot, g.tot_pitch, nchunks - 1, g.cin, g.cout);
     }
     const dim3 grid((unsigned)nchunks, (unsigned)g.nch);
     if (vl && vs) hipLaunchKernelGGL((k_recur_scan<OP, TB, AROW, true, true>), grid, block, 0, st, g);
@@ -206,8 +212,11 @@ static void launch_recur_op(const RecurArgs& g, int64_t nchunks, hipStream_t st)
     }
 }
 
-int launch_recur(const RecurArgs& g, hipStream_t st) {
-    if (g.n <= 0 || g.nch <= 0) return 0;
+int launch_recur(const RecurArgs& g0, hipStream_t st) {
+    if (g0.n <= 0 || g0.nch <= 0) return 0;
+    if (g0.k0 < 0 || (g0.k0 > 0 && g0.cin == nullptr)) return -1;
+    RecurArgs g = g0;
+    if (g.k0 == 0) g.cin = nullptr;  // (from rest: no record is read)
     const int64_t nchunks = (g.n + kCumsumChunk - 1) / kCumsumChunk;
     if (g.nch > 65535 || nchunks >= ((int64_t)1 << 31) || (g.op != 0 && g.op != 1)) return -1;
     if (nchunks > 1 && (g.tot == nullptr || g.tot_pitch < nchunks - 1)) return -1;

@@ -23,6 +23,12 @@
 //   k_recur2_scan    one workgroup per (chunk, channel): the tile scans again, the entering states, the outputs, stored
 // A signal of one chunk is the third launch alone.
 //
+// The resumed form (Recur2Args::k0 > 0, a stream's push) is k_cumsum.hip's: the rows start at chunk k0, blockIdx.x and the
+// index into tot are relative to it, the carry starts from cin, the state (s0, s1) that enters chunk k0, and leaves the
+// state that enters the last chunk in cout.  That state is the carry's own -- composites applied in double-doubles -- and
+// not the last two outputs, which walk the loop.  "No state yet" (`have`, run 0 of the signal) is relative chunk 0 without
+// a cin.
+//
 // Registers: a lane's run of a1, a2 and b is 48 doubles and its composite six more, which k_recur.hip's geometry --
 // sixteen waves a workgroup, a wave ONE tile, 128 VGPRs a wave -- does not hold.  So b stays in the wave's LDS image
 // (kscan.h): the lane reads its run there, 16 bytes a read, in the composite's walk and again in the outputs' walk, and
@@ -219,10 +225,11 @@ __global__ __launch_bounds__(64 * kRecur2Waves) void k_recur2_totals(Recur2Args 
 // The carries: entry k of a channel (blockIdx.x) holds G[15] of chunk k; its (v0, v1) become the state S that chunk k + 1
 // starts from: S[0] = the v of chunk 0 as it is, S[k] = G[15] of chunk k applied to S[k - 1].  The elements go through
 // LDS kBlock at a time; lane 0 walks them.
-__global__ __launch_bounds__(kBlock) void k_recur2_carry(double* tot, int64_t pitch, int64_t count) {
+__global__ __launch_bounds__(kBlock) void k_recur2_carry(double* tot, int64_t pitch, int64_t count, const double* cin, double* cout) {
     __shared__ double el[kR2Words * kBlock];
     double* row = tot + kR2Words * (int64_t)blockIdx.x * pitch;
-    double s0 = 0.0, s1 = 0.0;  // (lane 0's; replaced, not joined, by the first chunk's)
+    const bool resumed = cin != nullptr;
+    double s0 = resumed ? cin[2 * blockIdx.x] : 0.0, s1 = resumed ? cin[2 * blockIdx.x + 1] : 0.0;  // (lane 0's; from rest: replaced, not joined, by the first chunk's)
     for (int64_t k0 = 0; k0 < count; k0 += kBlock) {
         const int64_t k = k0 + threadIdx.x;
         if (k < count) {
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void k_recur2_carry(double* tot, int64_t pi
         if (threadIdx.x == 0) {
             const int m = (int)(count - k0 < kBlock ? count - k0 : kBlock);  // (the entries past m are not read back)
             for (int j = 0; j < m; ++j) {
-                r2_enter(r2_get(el + kR2Words * j), !(k0 == 0 && j == 0), s0, s1);
+                r2_enter(r2_get(el + kR2Words * j), resumed || !(k0 == 0 && j == 0), s0, s1);
                 el[kR2Words * j + 4] = s0, el[kR2Words * j + 5] = s1;
             }
         }
@@ -241,6 +248,7 @@ __global__ __launch_bounds__(kBlock) void k_recur2_carry(double* tot, int64_t pi
         if (k < count) row[kR2Words * k + 4] = el[kR2Words * threadIdx.x + 4], row[kR2Words * k + 5] = el[kR2Words * threadIdx.x + 5];
         __syncthreads();
     }
+    if (threadIdx.x == 0 && cout != nullptr) cout[2 * blockIdx.x] = s0, cout[2 * blockIdx.x + 1] = s1;  // the state that enters chunk `count`, the last one
 }
 
 // Pass 2: chunk blockIdx.x of channel blockIdx.y, stored.
@@ -267,11 +275,13 @@ __global__ __launch_bounds__(64 * kRecur2Waves) void k_recur2_scan(Recur2Args g)
     __syncthreads();
     if (!exists) return;
     // the state that enters the tile, then the one that enters the lane's run
-    bool have = chunk > 0;
+    bool have = chunk > 0 || g.cin != nullptr;  // (the absolute chunk: launch_recur2 passes cin where k0 > 0 only)
     double s0 = 0.0, s1 = 0.0;
-    if (have) {
+    if (chunk > 0) {
         const double* S = g.tot + kR2Words * ((int64_t)c * g.tot_pitch + chunk - 1);
         s0 = S[4], s1 = S[5];
+    } else if (have) {
+        s0 = g.cin[2 * c], s1 = g.cin[2 * c + 1];
     }
     for (int k = 0; k < wave; ++k) {  // tile after tile: the total of tile k applied to the state that entered it
         r2_enter(r2_get(tk + kR2Words * k), have, s0, s1);
@@ -325,7 +335,7 @@ static void launch_recur2_t(const Recur2Args& g, int64_t nchunks, hipStream_t st
         const dim3 grid((unsigned)(nchunks - 1), (unsigned)g.nch);
         if (vl) hipLaunchKernelGGL((k_recur2_totals<TB, AROW, true>), grid, block, 0, st, g);
         else hipLaunchKernelGGL((k_recur2_totals<TB, AROW, false>), grid, block, 0, st, g);
-        hipLaunchKernelGGL(k_recur2_carry, dim3((unsigned)g.nch), dim3(kBlock), 0, st, g.tot, g.tot_pitch, nchunks - 1);
+        hipLaunchKernelGGL(k_recur2_carry, dim3((unsigned)g.nch), dim3(kBlock), 0, st, g.tot, g.tot_pitch, nchunks - 1, g.cin, g.cout);
     }
     const dim3 grid((unsigned)nchunks, (unsigned)g.nch);
     if (vl && vs) hipLaunchKernelGGL((k_recur2_scan<TB, AROW, true, true>), grid, block, 0, st, g);
@@ -334,8 +344,11 @@ static void launch_recur2_t(const Recur2Args& g, int64_t nchunks, hipStream_t st
     else hipLaunchKernelGGL((k_recur2_scan<TB, AROW, false, false>), grid, block, 0, st, g);
 }
 
-int launch_recur2(const Recur2Args& g, hipStream_t st) {
-    if (g.n <= 0 || g.nch <= 0) return 0;
+int launch_recur2(const Recur2Args& g0, hipStream_t st) {
+    if (g0.n <= 0 || g0.nch <= 0) return 0;
+    if (g0.k0 < 0 || (g0.k0 > 0 && g0.cin == nullptr)) return -1;
+    Recur2Args g = g0;
+    if (g.k0 == 0) g.cin = nullptr;  // (from rest: no record is read)
     const int64_t nchunks = (g.n + kCumsumChunk - 1) / kCumsumChunk;
     if (g.nch > 65535 || nchunks >= ((int64_t)1 << 31)) return -1;
     if ((g.a[0] == nullptr) != (g.a[1] == nullptr)) return -1;  // (both rows, or both constants)

@@ -129,6 +129,13 @@ struct CombArgs {
     int64_t n, D;
     double b0, bD, a;
     int32_t nch, x_f32;
+    // The resumed form (a stream's push, DESIGN.md "Streaming the device-only nodes"): frame 0 of x and y is frame r of the
+    // signal, and the lane of residue class (r + j) mod D takes its (xd, yd) from the record instead of +0.0 and leaves the
+    // pair it ends with in the other record.  A record is [nch][D][2] Float64; a class without a frame in [r, r + n) copies
+    // its entry.  cin is read only where r > 0; cout may be null.  All three zero: the kernel of a whole signal, as ever.
+    int64_t r;
+    const double* cin;
+    double* cout;
 };
 int launch_comb(const CombArgs& a, hipStream_t st);
 // Cumsum (k_cumsum.hip, -ffp-contract=off): per channel y[n] = x[0] + ... + x[n] in Float64 over ONE summation tree that
@@ -150,6 +157,12 @@ struct CumsumArgs {
     int64_t tot_pitch;
     int64_t n;
     int32_t nch, x_f32;
+    // The resumed form (a stream's push): frame 0 of x and y is frame k0 * kCumsumChunk of the signal, cin[c] the running
+    // total that enters that chunk (read only where k0 > 0).  cout[c], where it is not null and n covers more than one
+    // chunk, receives the total that enters the LAST chunk of [0, n): what a later launch resumes from.
+    int64_t k0;
+    const double* cin;
+    double* cout;
 };
 // the chunk totals a channel of n frames needs: one for every chunk that has a chunk behind it
 constexpr int64_t cumsum_totals(int64_t n) { return n <= kCumsumChunk ? 0 : (n - 1) / kCumsumChunk; }
@@ -175,6 +188,10 @@ struct RecurArgs {
     int64_t tot_pitch;
     int64_t n;
     int32_t nch, b_f32, op;
+    // the resumed form, as CumsumArgs': the state is the carry C, one Float64 a channel
+    int64_t k0;
+    const double* cin;
+    double* cout;
 };
 int launch_recur(const RecurArgs& a, hipStream_t st);
 // Recur2 / Resonator / Sweep (k_recur2.hip, -ffp-contract=off): per channel the second-order scan
@@ -202,6 +219,11 @@ struct Recur2Args {
     int64_t tot_pitch;
     int64_t n;
     int32_t nch, b_f32;
+    // the resumed form, as CumsumArgs': the state is (s0, s1) as k_recur2_carry leaves it -- the chunk's composite applied in
+    // double-double arithmetic, NOT the last two outputs, whose bits differ -- two Float64 a channel
+    int64_t k0;
+    const double* cin;
+    double* cout;
 };
 int launch_recur2(const Recur2Args& a, hipStream_t st);
 // MovingMax / MovingMin (k_moving.hip): output j in [0, n_out) of a channel is the greatest (least) of the input frames

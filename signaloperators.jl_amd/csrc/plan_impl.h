@@ -145,12 +145,13 @@ struct Stage {
     int64_t lo = (int64_t)1 << 62;  // first frame anybody reads
     int64_t base = 0;  // first frame the stage computes (warm start, see rs_warm_start / sos_warm_start in stages.cpp): its buffer holds [base, need)
     int64_t in_base = 0;  // first frame of the child the stage consumes
+    int64_t carried = 0;  // Comb, Cumsum, Recur, Recur2 with a carry-out record (node p1): the frame whose entering state the record holds after an execute (process_from_frame_0)
     bool processed = false;
     bool norm_alias = false;  // Normpower whose `vals` is its child stage's output buffer (no copy)
     bool norm_direct = false; // Normpower of a plain array leaf: the rms is taken over the array where it lies, readers divide its loads
     bool under_norm = false;  // a Normpower consumes this stage (directly or through further stages)
     int64_t norm_df = 0;      // ... the largest frame offset it is read at on such a path (0: every Normpower's region starts at this stage's first frame)
-    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys; Movsum's block totals and dyadic nodes, [nch * movsum_scratch(..)] Float64; Recur's chunk totals, [nch][cumsum_totals(need)][2] Float64; Recur2's, [nch][cumsum_totals(need)][12] Float64
+    int out_buf = -1, in_buf = -1, aux_buf = -1;  // aux_buf: Cumsum's chunk totals, [nch][cumsum_totals(need - base)] Float64; Moving's block maxima and table, [nch * moving_scratch(..)] keys; Movsum's block totals and dyadic nodes, [nch * movsum_scratch(..)] Float64; Recur's chunk totals, [nch][cumsum_totals(need - base)][2] Float64; Recur2's, [nch][cumsum_totals(need - base)][12] Float64
     int64_t win_off = -1;  // >= 0: the stage writes the RESULT's frames [win_off, win_off + need) itself (window aliasing)
     // input source (after processing): either a materialised buffer or a direct view
     const void* in_ptr = nullptr;  // direct device pointer (nullptr -> in_buf)
@@ -382,6 +383,7 @@ struct Plan {
     int64_t array_epoch = 0, graph_epoch = -1, last_epoch = -1;
     bool graph_failed = false;
     bool graph_plan = false;  // this execute may be captured or replayed (plan_execute): its launches take fixed arguments
+    std::vector<int> carry_nodes;  // the nodes that carry a stream's state (s0 > 0 or p1), in node-table order (build_nodes)
     int64_t n_replays = 0, n_captures = 0, n_direct = 0;  // so_plan_counter
     so_stats_t stats{};
     int64_t algo_bytes = 0;

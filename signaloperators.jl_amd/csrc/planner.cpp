@@ -135,6 +135,15 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             shaped(b, b, SO_F64);
             if (rows && !N.short_skip) N.short_skip = b.short_skip;
         };
+        // the carried state of a stream (include/sigops.h, "Carried state"): s0 = the frame the stage resumes at, p0 = the
+        // record it starts from, p1 = the record it leaves; `step`: the frames s0 is a multiple of
+        auto carried = [&](int64_t step) {
+            if (nd.s0 < 0) fail(SO_ERR_INVALID, where + "resumes at frame " + std::to_string(nd.s0) + ": a frame of the signal expected");
+            if (nd.s0 % step) fail(SO_ERR_INVALID, where + "resumes at frame " + std::to_string(nd.s0) + ", which is not a multiple of its chunk of " + std::to_string(step) + " frames");
+            if (nd.s0 > 0 && !nd.p0) fail(SO_ERR_INVALID, where + "resumes at frame " + std::to_string(nd.s0) + " without a carry-in record (p0)");
+            if (nd.p0 && nd.p0 == nd.p1) fail(SO_ERR_INVALID, where + "takes a carry-out record (p1) that is not its carry-in record (p0)");
+            if (nd.s0 > 0 || nd.p1) carry_nodes.push_back(i);
+        };
         switch (nd.kind) {
         case SO_NODE_ARRAY:
             if (nd.dtype != SO_F32 && nd.dtype != SO_F64)
@@ -324,6 +333,7 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             finite(x, "signal x");
             floats(x, "signal x");
             shaped(x, x, SO_F64);
+            carried(1);
             break;
         }
         case SO_NODE_CUMSUM: {  // the running sum over one fixed summation tree (no reference counterpart; DESIGN.md "Cumsum")
@@ -332,6 +342,7 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             finite(x, "signal x");
             floats(x, "signal x");
             shaped(x, x, SO_F64);
+            carried(kCumsumChunk);
             break;
         }
         case SO_NODE_MOVING: {  // sliding-window extrema over [n - l0, n + l1] (no reference counterpart; DESIGN.md "Moving extrema")
@@ -366,11 +377,13 @@ void Plan::build_nodes(const so_node_t* in, int n) {
             if (nd.i0 != 0 && nd.i0 != 1) fail(SO_ERR_INVALID, where + "is affine (0) or max-decay (1), not " + std::to_string(nd.i0));
             takes(1, 2, "one child, the signal b (the constant a in d0), or two, a and b");
             scan(std::isfinite(nd.d0), "a finite constant a");
+            carried(kCumsumChunk);
             break;
         }
         case SO_NODE_RECUR2: {  // the second-order scan y[n] = (a1[n] y[n-1] + a2[n] y[n-2]) + b[n] over one fixed tree (no reference counterpart; DESIGN.md "Recur2")
             takes(1, 3, "one child, the signal b (the constants a1 in d0 and a2 in d1), or three, a1, a2 and b");
             scan(std::isfinite(nd.d0) && std::isfinite(nd.d1), "finite constants a1 and a2");
+            carried(kCumsumChunk);
             break;
         }
         default: fail(SO_ERR_INVALID, "unknown node kind " + std::to_string(nd.kind));
@@ -1629,6 +1642,7 @@ Plan* plan_create(const so_node_t* nodes, int32_t n_nodes, int32_t root, const s
                     if (P->stages[i].out_buf == e.leaf.buf && P->stages[i].kind != ST_NORM &&
                         P->stages[i].need == out->nframes + e.leaf.df &&
                         // (a window of the stage: the three-pass IIR can leave out the frames before it)
+                        e.leaf.df >= P->stages[i].base &&
                         (e.leaf.df == 0 || (P->stages[i].kind == ST_SOS && P->stages[i].groups.size() == 1 &&
                                             !P->stages[i].onepass && out->frame_stride == 1 &&
                                             e.leaf.df >= P->stages[i].base && !std::getenv("SIGOPS_NO_WINDOW_ALIAS"))) &&

@@ -597,35 +597,50 @@ void Plan::second_input(int sid, int kid, int64_t base, int64_t frames, int whic
 // Recur2's composite (M, v) of the chunk, six double-doubles, whose v the carry kernel turns into the state that enters the
 // next chunk.  Every entry read is written by the same execute (k_cumsum.hip, k_recur.hip, k_recur2.hip), so nothing clears
 // them.
+// A node that carries a stream's state (s0 = r > 0, p0, p1; include/sigops.h "Carried state") starts at frame r instead: the
+// stage computes [r, need) from the children's [r, need) -- base, in_base and the buffer's frame0 are r, nothing before r is
+// lowered, so a leaf whose head has left memory is not touched -- and owns totals for the chunks from r on.  Whoever reads
+// the stage before r is refused: those frames are not computed.  Stage::carried is the frame whose entering state the
+// carry-out record holds once the plan has run: the last chunk's first frame for the scans, need for Comb; r where
+// nothing advanced or no record is wanted.
 void Plan::process_from_frame_0(int sid) {
     const int ni = stages[sid].node, kind = stages[sid].kind;
     const int rows = (int)nodes[ni].kids.size() - 1;
     const int xk = nodes[ni].kids[rows];
     const int nch = nodes[ni].nch;
-    const int64_t need = stages[sid].need;
+    const int64_t need = stages[sid].need, r = nodes[ni].nd.s0;
     stages[sid].processed = true;
+    stages[sid].carried = r;
     if (need <= 0) return;
-    stages[sid].base = stages[sid].in_base = 0;
-    bufs[stages[sid].out_buf].frame0 = 0;
-    stage_input(sid, lower(xk, Rect{0, need, 0, nch}, Map{1, 0, 1, 0}), need, nch, nodes[xk].dtype);
-    for (int w = 0; w < rows; ++w) second_input(sid, nodes[ni].kids[w], 0, need, w);
+    if (r > 0) {
+        const std::string who = "node " + std::to_string(ni) + ": " + stage_node_kind(nodes[ni].nd.kind)->name + " ";
+        if (r > need) fail(SO_ERR_INVALID, who + "resumes at frame " + std::to_string(r) + ", beyond the " + std::to_string(need) + " frames that are read");
+        if (stages[sid].lo < r)
+            // (the token at the end is part of the C-ABI, include/sigops.h "Carried state": a stream reads the node from it)
+            fail(SO_ERR_LENGTH, who + "is read from frame " + std::to_string(stages[sid].lo) + " on, before its resume frame " + std::to_string(r) + ": the frames before it are not computed again [resume node " + std::to_string(ni) + "]");
+    }
+    stages[sid].base = stages[sid].in_base = r;
+    bufs[stages[sid].out_buf].frame0 = r;
+    if (nodes[ni].nd.p1) stages[sid].carried = kind == ST_COMB ? need : std::max(r, (need - 1) / kCumsumChunk * kCumsumChunk);
+    stage_input(sid, lower(xk, Rect{0, need - r, 0, nch}, Map{1, r, 1, 0}), need - r, nch, nodes[xk].dtype);
+    for (int w = 0; w < rows; ++w) second_input(sid, nodes[ni].kids[w], r, need - r, w);
     const size_t entry = kind == ST_CUMSUM ? 8 : kind == ST_RECUR ? 16 : kind == ST_RECUR2 ? 96 : 0;
-    if (entry && cumsum_totals(need) > 0) {
-        const int b = raw_buf((size_t)cumsum_totals(need) * (size_t)nch * entry);
+    if (entry && cumsum_totals(need - r) > 0) {
+        const int b = raw_buf((size_t)cumsum_totals(need - r) * (size_t)nch * entry);
         stages[sid].aux_buf = b;
     }
     if (std::getenv("SIGOPS_DEBUG_PLAN")) {
         const Stage& S = stages[sid];
         const so_node_t& nd = nodes[ni].nd;
         const int order = kind == ST_RECUR ? 1 : kind == ST_RECUR2 ? 2 : 0;
-        std::string what = kind == ST_COMB ? "D=" + std::to_string(nd.l0) : "chunk totals a channel " + std::to_string(cumsum_totals(need));
+        std::string what = kind == ST_COMB ? "D=" + std::to_string(nd.l0) : "chunk totals a channel " + std::to_string(cumsum_totals(need - r));
         if (kind == ST_RECUR) what = std::string(nd.i0 ? "max-decay, " : "affine, ") + what;
         std::string inputs = std::string(order ? "b " : "x ") + how_read(S);
         for (int w = 0; w < order; ++w)
             inputs += std::string(order == 1 ? ", a " : w ? ", a2 " : ", a1 ") +
                       (!rows ? "the constant " + std::to_string(w ? nd.d1 : nd.d0)
                              : std::string(S.side[w].array_node >= 0 ? "a Float64 array read in place" : "materialised by a pointwise step") + (S.side[w].pitch == 0 ? ", one row for every channel" : ""));
-        std::fprintf(stderr, "[sigops] %s stage %d: %s, frames [0,%lld) x %d channels, %s\n", stage_node_kind(nd.kind)->name, sid, what.c_str(), (long long)need, nch, inputs.c_str());
+        std::fprintf(stderr, "[sigops] %s stage %d: %s, frames [%lld,%lld) x %d channels, %s\n", stage_node_kind(nd.kind)->name, sid, what.c_str(), (long long)r, (long long)need, nch, inputs.c_str());
     }
 }
 

@@ -4,6 +4,7 @@ reference src/sink.jl:28-168 for type resolution, length checks and ToChannels;
 the block loop (src/sink.jl:225-260) is replaced by so_plan_create/so_plan_execute.
 """
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -85,7 +86,11 @@ class Plan:
         st = L.so_plan_create(self.lowered.nodes, self.lowered.n, self.lowered.root,
                               C.byref(self.desc), device, C.byref(self.handle))
         if st != 0:
-            raise S.ErrorException(K.last_error())
+            err = S.ErrorException(K.last_error())
+            # (a reader before a carrying node's resume frame ends in the ABI's "[resume node N]": which node, for _refused)
+            m = re.search(r"\[resume node (\d+)\]$", str(err))
+            err.lowered, err.resume_node = self.lowered, int(m.group(1)) if m else -1
+            raise err
 
     def execute(self, out_ptr, stream=None):
         st = K.lib().so_plan_execute(self.handle, C.c_void_p(out_ptr), C.c_void_p(stream or 0))
@@ -135,6 +140,17 @@ class Plan:
                 "direct_executes": L.so_plan_counter(self.handle, 2), "fused_mfmas_per_block": L.so_plan_counter(self.handle, 3),
                 "wproj": L.so_plan_counter(self.handle, 4), "fold": L.so_plan_counter(self.handle, 10),
                 "chain4": L.so_plan_counter(self.handle, 11)}
+
+    def carried(self):
+        """the nodes that carry a stream's state (include/sigops.h "Carried state"), in node-table order: `(signal, frame,
+        need)`, the frame whose entering state the node's carry-out record holds once the plan has run and the frames
+        `[0, need)` of the node that the plan reads"""
+        L = K.lib()
+        by_index = dict(self.lowered.carry_nodes)
+        return [(by_index[L.so_plan_counter(self.handle, K.COUNTER_CARRY_NODE_FIRST + k)],
+                 L.so_plan_counter(self.handle, K.COUNTER_CARRY_FRAME_FIRST + k),
+                 L.so_plan_counter(self.handle, K.COUNTER_CARRY_NEED_FIRST + k))
+                for k in range(L.so_plan_counter(self.handle, K.COUNTER_CARRY_NODES))]
 
     def rsos_geometry(self):
         """the first fused resampler + IIR launch's ranges (so_plan_counter 5 .. 10): periods per range, warm-up periods, input
@@ -189,8 +205,9 @@ def _result_fields(result):
         result.ctypes.data
 
 
-def sink_into(result, x, *, device=0, rng=None, stream=None):
-    """sink!(result,x): write size(result,1) frames of x (reference src/sink.jl:154-168)"""
+def sink_into(result, x, *, device=0, rng=None, stream=None, report=None):
+    """sink!(result,x): write size(result,1) frames of x (reference src/sink.jl:154-168).  `report(plan)` is called once the
+    result is complete, before the plan is closed (a `BlockStream` reads where its carried states stand)."""
     x = S._assignal(x)
     shape, dt, strides, is_dev, ptr = _result_fields(result)
     n = S.nframes(x)
@@ -202,6 +219,8 @@ def sink_into(result, x, *, device=0, rng=None, stream=None):
         plan.execute(ptr, stream)
         if is_dev:
             plan.check(stream)  # (a complete result or an exception, as the reference's sink!)
+        if report is not None:
+            report(plan)
     finally:
         plan.close()
     return result
@@ -307,7 +326,20 @@ class BlockStream:
     resampler, `Filt` one to one).  Concatenated, the outputs are the sink of the pipeline over the
     whole input.  Not streamable, and refused with an error at the first push (`_streamable`): `Normpower`,
     ramps at the end of the signal (`RampOff`, `Ramp`, `FadeTo`), pads that index the end of the input --
-    anything whose early outputs depend on the input's total length."""
+    anything whose early outputs depend on the input's total length -- and `SampleAt` / `Delay`, whose table may be
+    read at any position.
+
+    The device-only nodes stream bit for bit (DESIGN.md "Streaming the device-only nodes").  The moving windows
+    (`MovingMax`, `MovingSum`, `MovingMedian` and their kin) need nothing but the `back` frames of their window in the
+    history; an output is final once the `ahead` frames behind it have arrived.  `Cumsum`, `Recur` and `Recur2` (and
+    `Integrate`, `OnePole`, `Smooth`, `PeakDecay`, `Resonator`, `Sweep`) start every push at a chunk boundary of 16384
+    frames from the state that entered that chunk, `Comb` / `Allpass` at the frame the last push ended on from the
+    `(x, y)` of its delay line: the stream keeps these records on the device, per node, and never computes a frame
+    before them again -- so the history must hold the frames from the resume point on: at most one chunk plus the
+    block plus what the nodes above look back, and where a node above looks back (a `Filt`, a window, a resampler over
+    a carrying node) the record before the newest may be the one resumed from, a further block or chunk behind.  A node is known by its place in a walk of the tree `pipeline`
+    returns (`_carrying`), so `pipeline` must build the same tree for every push: a tree whose carrying nodes changed
+    is refused rather than handed another node's state."""
 
     def __init__(self, pipeline, fs, nch=1, dtype=np.float64, history=1 << 16, device=0):
         import torch
@@ -328,6 +360,8 @@ class BlockStream:
         self.received = 0
         self.emitted = 0
         self.closed = False
+        self._carried = None  # one _Carry per carrying node of the pipeline's tree, in the order of `_carrying`; None before the first push
+        self.replanned = 0  # pushes planned again with a node resumed from its older record (`_sink_carrying`)
 
     # -- resident tail ---------------------------------------------------------------------------
     def _append(self, block):
@@ -390,7 +424,9 @@ class BlockStream:
         total = S.nframes(tree)
         if total is None or S.isknowninf(total):
             S.error("BlockStream: the pipeline must have as many frames as its input decides")
-        _streamable(tree)
+        _streamable(tree, self)
+        nodes = _carrying(tree)
+        self._same_nodes(nodes)
         upto = total if self.closed else self._final_frames(leaf, tree, int(total))
         m = upto - self.emitted
         nch_out = tree.nch
@@ -399,9 +435,67 @@ class BlockStream:
             return torch.empty((0, nch_out), dtype=tdt, device=self.dev)
         blk = S.Until(S.After(tree, self.emitted * frames) if self.emitted else tree, m * frames)
         res = torch.empty((nch_out, m), dtype=tdt, device=self.dev).t()
-        sink_into(res, blk, device=self.device)
+        self._sink_carrying(res, blk, nodes)
         self.emitted = upto
         return res
+
+    # -- carried state ---------------------------------------------------------------------------
+    def _same_nodes(self, nodes):
+        """the carrying nodes of this push's tree against the last push's, one by one: family, parameters, channels"""
+        import torch
+
+        sigs = [(type(x).__name__, x.family, tuple(sorted(x.fields().items())), len(x.children), x.nch, x.stream_doubles()) for x in nodes]
+        if self._carried is None:  # the first push decides; a later tree with other carrying nodes, or with some where there were none, is refused
+            self._carried = [_Carry(sig, torch.empty(sig[4] * sig[5], dtype=torch.float64, device=self.dev)) for sig in sigs]
+            return
+        was = [c.sig for c in self._carried]
+        if was != sigs:
+            k = next((i for i, (a, b) in enumerate(zip(was, sigs)) if a != b), min(len(was), len(sigs)))
+            S.error(f"BlockStream: the pipeline's nodes that carry state changed between pushes (entry {k} of {len(was)}: "
+                    f"{was[k][1] if k < len(was) else 'none'} {dict(was[k][2]) if k < len(was) else ''} before, "
+                    f"{sigs[k][1] if k < len(sigs) else 'none'} {dict(sigs[k][2]) if k < len(sigs) else ''} now): "
+                    "the state of one node is not applied to another")
+
+    def _sink_carrying(self, res, blk, nodes):
+        """`sink_into` with every carrying node resumed from the newest record that lies at or before the first frame anybody
+        reads of it.  The newest the stream has is tried first; where the planner refuses the plan for a node (a filter's
+        warm start, a window's `back`, a resampler's taps above the node reach before its resume frame) the plan is made
+        again with that node at the record before, down to the one the last push read from -- the first frame read never
+        moves back, so that one always serves."""
+        import torch
+
+        at_rec = [len(c.live) - 1 for c in self._carried]
+        while True:
+            for x, c, i in zip(nodes, self._carried, at_rec):
+                frame, rec = c.live[i]
+                x.carry = (frame, rec.data_ptr() if rec is not None else 0, c.spare.data_ptr())
+            stands = []
+            try:
+                sink_into(res, blk, device=self.device, report=lambda plan: stands.extend(plan.carried()))
+                break
+            except S.ErrorException as e:
+                k = _refused(e, nodes)
+                if k is None or at_rec[k] == 0:
+                    raise
+                at_rec[k] -= 1
+                self.replanned += 1
+        at = {id(x): (frame, need) for x, frame, need in stands}
+        for x, c, i in zip(nodes, self._carried, at_rec):
+            frame, need = at.get(id(x), (0, 0))
+            if need > 0 and frame != x.stream_checkpoint(x.carry[0], need):  # the planner's rule and the declared one must agree
+                S.error(f"BlockStream: internal: {x.family} read up to frame {need} from frame {x.carry[0]} left its state at frame {frame}, "
+                        f"not at {x.stream_checkpoint(x.carry[0], need)}")
+            # the records before the one read are never read again; of those behind it the stream keeps the oldest -- the
+            # next to come into reach -- and the newest
+            live = c.live[i:]
+            if frame > live[-1][0]:  # (a frame it has already: the spare holds the same state, and stays the spare)
+                live.append((frame, c.spare))
+                c.spare = None
+            keep = live if len(live) <= 3 else [live[0], live[1], live[-1]]
+            free = [rec for _, rec in c.live + live if rec is not None and all(rec is not r for _, r in keep)]
+            c.live = keep
+            if c.spare is None:
+                c.spare = free[0] if free else torch.empty_like(keep[-1][1])
 
     def push(self, block):
         if self.closed:
@@ -418,8 +512,48 @@ class BlockStream:
         return self._emit()
 
 
-def _streamable(x):
-    """Refuse what `BlockStream` cannot stream: nodes whose early outputs depend on the input's TOTAL
+class _Carry:
+    """What a `BlockStream` keeps for one carrying node: `sig`, what the node must still be at the next push; `live`, up to
+    three `(frame, record)` of the state that enters `frame`, oldest first (at first rest alone: frame 0, no record);
+    `spare`, the record the next push writes -- never one of `live`, so a push does not write what it may still read."""
+
+    def __init__(self, sig, spare):
+        self.sig, self.live, self.spare = sig, [(0, None)], spare
+
+
+def _carrying(tree):
+    """the nodes of `tree` that carry state in a stream (`stream_doubles() > 0`), one entry per node OBJECT however many
+    parents read it, in post-order with the children in their own order: the same tree gives the same list"""
+    seen, out = set(), []
+
+    def walk(x):
+        if id(x) in seen:
+            return
+        seen.add(id(x))
+        for c in getattr(x, "children", ()) or ():
+            walk(c)
+        if isinstance(x, S.StageSignal) and (x.stream_doubles() or 0) > 0:
+            out.append(x)
+
+    walk(tree)
+    return out
+
+
+def _refused(err, nodes):
+    """the entry of `nodes` that a plan was refused for being read before its resume frame (the `[resume node N]` that
+    include/sigops.h gives that refusal, which `Plan` leaves on the exception as `resume_node`), or None for any other error"""
+    lowered, ni = getattr(err, "lowered", None), getattr(err, "resume_node", -1)
+    if lowered is None or ni < 0:
+        return None
+    x = dict(lowered.carry_nodes).get(ni)
+    return next((k for k, y in enumerate(nodes) if y is x), None)
+
+
+def _streamable(x, store=None):
+    """`store`: where the stream keeps state from one push to the next (`BlockStream._emit` passes its own); None: nowhere,
+    and then every device-only node is refused with its `not_streamable`.  With a store only the node nothing would do
+    for (`stream_doubles()` is None: `SampleAt`) is.
+    Refuse what `BlockStream` cannot stream: nodes whose early outputs depend on the input's TOTAL
     length, which a stream does not know -- each push would silently apply them to the input received
     so far (ADVICE r2).  `Normpower` divides by the rms of everything (reference src/filters.jl:296-309);
     a ramp off / `FadeTo` is anchored at the end (src/ramps.jl:65-72); `lastframe`, `cycle` and `mirror`
@@ -431,10 +565,10 @@ def _streamable(x):
                 "stream does not know yet; not streamable")
     if isinstance(x, S.PaddedSignal) and any(x.pad is p for p in (S.lastframe, S.cycle, S.mirror)):  # (identity: a pad may be an ndarray)
         S.error("BlockStream: lastframe / cycle / mirror padding indexes the end of the input; not streamable")
-    if isinstance(x, S.StageSignal):
+    if isinstance(x, S.StageSignal) and (store is None or x.stream_doubles() is None):
         S.error(f"BlockStream: {x.family} {x.not_streamable}; not streamable")
     for c in getattr(x, "children", ()) or ():
-        _streamable(c)
+        _streamable(c, store)
 
 
 def filt(b, a, x, si=None, *, device=0):

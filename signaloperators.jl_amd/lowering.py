@@ -124,6 +124,7 @@ class Lowered:
         self.keep = []  # keep-alive for ctypes / numpy buffers
         self.memo = {}
         self.array_nodes = []  # (index, ArraySig)
+        self.carry_nodes = []  # (index, StageSignal) of the nodes a stream attached a carry to, in node-table order
         self.nodes = None
         self.root = -1
 
@@ -546,8 +547,13 @@ def lower(x, nframes_out=None, rng=None):
                     lw.keep.append(v)
                     v = v.ctypes.data
                 r[k] = v
+            if s.carry is not None:  # a stream's state (include/sigops.h "Carried state"); none: the fields stay 0
+                resume, cin, cout = s.carry
+                r.update(s0=int(resume), p0=cin or None, p1=cout or None)
             r["children"] = kids
             idx = lw.add(**r)
+            if s.carry is not None:
+                lw.carry_nodes.append((idx, s))
         else:
             S.error(f"Value is not a signal: {s!r}")
         lw.memo[key] = idx

@@ -519,6 +519,15 @@ def _need_every_child(self, n, skip):
     return [(c, n, 0) for c in self.children]
 
 
+SCAN_CHUNK = 16384  # the chunk of Cumsum / Recur / Recur2 (csrc/kernels.h kCumsumChunk): the frames their state is carried at
+
+
+def _scan_checkpoint(self, resume, need):
+    """checkpoint rule of the scans: the first frame of the last chunk that holds a frame read, k1 = (need - 1) // chunk -- a
+    push that ends exactly on a chunk boundary has not entered the next chunk --, and `resume` where that is no later"""
+    return max(resume, (need - 1) // SCAN_CHUNK * SCAN_CHUNK) if need > 0 else resume
+
+
 def _need_x_ahead(self, n, skip):
     """demand rule: the window of the last frame reaches `ahead` frames further; the frames before a window's `back` come
     along"""
@@ -537,12 +546,23 @@ class StageSignal(AbstractSignal):
       child's length, `None` is the child whole;
     * `node` and `fields()`: the `SO_NODE_*` kind by name and the node's `i* / l* / d* / p* / s*` fields (include/sigops.h;
       an array stands for the pointer to it and is kept alive by the lowering);
-    * `not_streamable`: why a `BlockStream` refuses it; `shard_order`, `shard_tail`: where its multi-GPU refusal stands
-      among those of a tree that holds several families (lowest first, the first one met among equals), and what the
-      refusal adds after "is not built"."""
+    * `not_streamable`: why a stream with nowhere to keep state refuses it; `shard_order`, `shard_tail`: where its
+      multi-GPU refusal stands among those of a tree that holds several families (lowest first, the first one met among
+      equals), and what the refusal adds after "is not built";
+    * `stream_doubles()`: what a `BlockStream` carries for the node from one push to the next, in Float64 per channel --
+      0: nothing (its frames depend on a window of the input, which the stream keeps); a positive count: the record of
+      include/sigops.h "Carried state"; None: nothing would do, the node is not streamable;
+    * `stream_checkpoint(resume, need)`, for a node that carries a record: the frame whose entering state the record it
+      leaves holds when it resumed at `resume` and the frames `[0, need)` are read -- the planner's rule
+      (`Plan::process_from_frame_0`), which a `BlockStream` holds the plan's report to.
+
+    `carry` is not a declaration: a `BlockStream` sets it on the nodes of one push's tree, `(resume frame, address of the
+    carry-in record, address of the carry-out record)`, and the lowering writes it into the node's `s0 / p0 / p1`.  A node
+    nobody attached one to lowers as `fields()` says."""
 
     evaltrait = "computed"
     shard_tail = ""
+    carry = None
 
     def _like(self, timed, nch, dtype):
         """the length, duration and frame rate of the child `timed`"""
@@ -568,6 +588,9 @@ class SampleAtSignal(StageSignal):
     node = "SAMPLEAT"
     not_streamable = "reads its table at any position, and a stream keeps only a tail of its input resident"
     shard_order = 0
+
+    def stream_doubles(self):  # (any frame of the table may be read)
+        return None
 
     def __init__(self, x, pos, left=0.0, right=0.0, relative=False, wrap=False, interp="linear", taps=0, cutoff=0.0):
         self.interp = interp  # "linear" | "cubic" | "sinc"
@@ -612,6 +635,12 @@ class CombSignal(StageSignal):
     shard_order = 1  # its frames depend on every frame before them: a rank cannot start in the middle, and handing the state on is not built
     demand = _need_x
 
+    def stream_doubles(self):  # (x, y) of the last frame of each of the D residue classes
+        return 2 * self.delay
+
+    def stream_checkpoint(self, resume, need):  # where the push ended
+        return need
+
     def __init__(self, x, delay, b0, bD, a):
         self.signal = x
         self.children = (x,)
@@ -641,6 +670,11 @@ class CumsumSignal(StageSignal):
     shard_order = 1  # (as Comb)
     demand = _need_x
 
+    def stream_doubles(self):  # the running total that enters a chunk
+        return 1
+
+    stream_checkpoint = _scan_checkpoint
+
     def __init__(self, x):
         self.signal = x
         self.children = (x,)
@@ -668,6 +702,9 @@ class MovingSignal(StageSignal):
     shard_order = 2  # a rank's window reaches into its neighbours' frames
     shard_tail = _HALO
     demand = _need_x_ahead
+
+    def stream_doubles(self):  # (a window of the input, which the stream keeps)
+        return 0
 
     def __init__(self, x, back, ahead, is_min):
         self.signal = x
@@ -698,6 +735,9 @@ class MovingSumSignal(StageSignal):
     shard_tail = _HALO + ", summed over the whole signal's tree"
     demand = _need_x_ahead
 
+    def stream_doubles(self):  # (as Moving: the summation tree is fixed by the absolute frame)
+        return 0
+
     def __init__(self, x, back, ahead, op):
         self.signal = x
         self.children = (x,)
@@ -724,6 +764,9 @@ class MovingRankSignal(StageSignal):
     shard_order = 4  # (as Moving)
     shard_tail = _HALO
     demand = _need_x_ahead
+
+    def stream_doubles(self):  # (as Moving)
+        return 0
 
     def __init__(self, x, back, ahead, q):
         self.signal = x
@@ -752,6 +795,11 @@ class RecurSignal(StageSignal):
                       "and that is not built")
     shard_order = 1  # (as Comb)
     demand = _need_every_child
+
+    def stream_doubles(self):  # the carry C that enters a chunk
+        return 1
+
+    stream_checkpoint = _scan_checkpoint
 
     def __init__(self, a, b, op):
         self.signal = b
@@ -784,6 +832,11 @@ class Recur2Signal(StageSignal):
                       "next, and that is not built")
     shard_order = 1  # (as Comb)
     demand = _need_every_child
+
+    def stream_doubles(self):  # the state (s0, s1) that enters a chunk
+        return 2
+
+    stream_checkpoint = _scan_checkpoint
 
     def __init__(self, a1, a2, b):
         self.signal = b
@@ -1456,7 +1509,7 @@ def Comb(*args, feedforward=0.0, direct=1.0):
     every block recomputes the frames before it (quadratic in the length, as `stream` over `Normpower` re-reads its
     input).  Blocks and windows agree with the whole sink bit for bit where `x` gives the same bits whatever number of
     frames is asked of it (arrays, formulas, maps, `SampleAt`, nested `Comb`s); a `Filt` below the node rounds by how it
-    chunks its input, and the comb carries that: agreement within the Float64 contract.  `BlockStream` and multi-GPU
+    chunks its input, and the comb carries that: agreement within the Float64 contract.  A `BlockStream` carries the delay line from push to push and gives the whole sink's bits; multi-GPU
     shards refuse the node."""
     if len(args) == 2:
         d, g = args
@@ -1499,7 +1552,7 @@ scan over the 64 runs of a tile, sequential carries over the 16 tiles of a chunk
 "Cumsum", tests/cumsum_ref.py): a window, a `stream` block and the whole sink give the same bits, and the error of
 frame n stays within about (40 + chunks) * 2**-53 * sum(|x[:n + 1]|).  `x` must have a known, finite length.  `stream` over
 the node recomputes the frames before every block (quadratic in the length, as over `Comb`): stream what follows the
-node.  `BlockStream` and multi-GPU shards refuse the node."""
+node.  A `BlockStream` carries the running total that enters a chunk and gives the whole sink's bits; multi-GPU shards refuse the node."""
 
 
 def _Integrate(x):
@@ -1560,7 +1613,7 @@ def Recur(*args):
     own, relative to `S[n] = |a[n]| S[n-1] + |b[n]|`.  The node is meant for `|a| <= 1`: where
     `|a| > 1` over hundreds of frames a product of the a can overflow and `Inf * 0` gives NaN where a loop would stay
     finite.  There is no initial state: `y[-1]` is absent, not 0.  `b` must have a known, finite length.  `stream` over the
-    node recomputes the frames before every block (as over `Cumsum`); `BlockStream` and multi-GPU shards refuse the node."""
+    node recomputes the frames before every block (as over `Cumsum`); a `BlockStream` carries the scan's state from chunk to chunk and gives the whole sink's bits; multi-GPU shards refuse the node."""
     if len(args) == 1:
         a = args[0]
         return Curried(lambda b: _Recur("Recur", 0, a, b))
@@ -1759,7 +1812,7 @@ def Recur2(*args):
     The node is meant for stable coefficients: unstable stretches overflow the composites, and an `Inf` that meets a zero
     of a composite gives NaN.  There is no initial state.  `b` must have a
     known, finite length.  `stream` over the node recomputes the frames before every block (as over `Cumsum`);
-    `BlockStream` and multi-GPU shards refuse the node."""
+    a `BlockStream` carries the scan's state from chunk to chunk and gives the whole sink's bits; multi-GPU shards refuse the node."""
     if len(args) == 2:
         a1, a2 = args
         return Curried(lambda b: _Recur2("Recur2", a1, a2, b))
@@ -1873,6 +1926,16 @@ def Resonator(*args):
     return _Resonator(args[0], args[1], args[2])
 
 
+def _shifted(x, k):
+    """`x` delayed by the whole number of frames `k`, as Float64: `k` frames of +0.0, then bit copies of `x`, cut to the length
+    of `x` -- the frames `Delay(x, k)` gives, bit for bit, without `SampleAt`'s table: frame n needs no frame of `x` but
+    n - k, so a `BlockStream`, which keeps only a tail of its input, can compute it."""
+    from .units import frames
+
+    y = _Until(_Append([ArraySig(np.zeros((k, x.nch), dtype=x.dtype), x.fs), x]), nframes(x) * frames)
+    return y if y.dtype == F64 else ToEltype(y, F64)
+
+
 def _Sweep(x, kind, fc, q):
     what = "Sweep (Recur2)"
     kind = kind if isinstance(kind, type) else type(kind)
@@ -1897,7 +1960,7 @@ def _Sweep(x, kind, fc, q):
             b0, b1, b2 = alpha, 0.0 * alpha, -alpha
         return 2.0 * cw / a0, -(1.0 - alpha) / a0, b0 / a0, b1 / a0, b2 / a0
 
-    return _formulas(what, x, [fc, q], fns, [x, _Delay(x, 1), _Delay(x, 2)])
+    return _formulas(what, x, [fc, q], fns, [x, _shifted(x, 1), _shifted(x, 2)])
 
 
 def Sweep(*args, q=math.sqrt(0.5)):
@@ -1905,7 +1968,8 @@ def Sweep(*args, q=math.sqrt(0.5)):
     biquad with a cutoff (and a resonance) that may move -- a swept low-pass, a wah, an auto-filter driven by an envelope.
     With `w = 2 pi fc / framerate`, `alpha = sin(w) / (2 q)` and `a0 = 1 + alpha` it runs as a direct form I with the
     coefficients of frame n on all taps: `Recur2(2 cos(w) / a0, -(1 - alpha) / a0, (b0 x[n] + b1 x[n-1] + b2 x[n-2]) / a0)`,
-    the taps `x[n-1]` and `x[n-2]` being `Delay(x, 1)` and `Delay(x, 2)` (bit copies with zeros in front).  `fc` is a
+    the taps `x[n-1]` and `x[n-2]` being the frames of `Delay(x, 1)` and `Delay(x, 2)` (bit copies with zeros in front), built
+    as `x` appended to one and two frames of zeros so that they need no table.  `fc` is a
     frequency or a signal of Hz at the rate of `x`, `q > 0` a number or a signal.  `Bandpass` has a peak gain of 0 dB."""
     if len(args) == 2:
         kind, fc = args
@@ -1978,7 +2042,8 @@ the frame NaN (its payload is unspecified).  Maximum and minimum round nothing a
 splitting the work gives the same bits: windows, `stream` blocks and the whole sink agree bit for bit where `x` does.
 The dependence is local: a window or a `stream` block computes its own frames from its own range of `x` plus `back`
 frames before and `ahead` after, so `stream` over the node is linear and an `x` of infinite length is accepted.
-`BlockStream` and multi-GPU shards refuse the node."""
+A `BlockStream` computes each push from the tail of the input it keeps (`back` frames of history; `ahead` frames of output wait
+for their input) and gives the whole sink's bits; multi-GPU shards refuse the node."""
 MovingMin = _moving_ctor("MovingMin", True)
 MovingMin.__doc__ = """`MovingMin(x, w, *, ahead=0, center=False)`, curried `x | MovingMin(w, ahead=...)`: the sliding-window minimum, the
 mirror image of `MovingMax`: the least sample of the clipped window under the same order, so `-0.0` beats `+0.0`, NaN
@@ -2018,7 +2083,7 @@ segment of up to 1024 frames, a suffix, whole segments and a prefix joined -- no
 cancels, and windows, `stream` blocks and the whole sink agree bit for bit where `x` does.  What lies outside the signal
 counts as `-0.0`, the additive identity: a window of only `-0.0` sums to `-0.0`.  The dependence is local: a window or a
 `stream` block computes its own frames from its own range of `x` plus `back` frames before and `ahead` after, and an `x`
-of infinite length is accepted.  `BlockStream` and multi-GPU shards refuse the node."""
+of infinite length is accepted.  A `BlockStream` streams the node like `MovingMax`, bit for bit; multi-GPU shards refuse it."""
 MovingMean = _moving_sum_ctor("MovingMean", 1)
 MovingMean.__doc__ = """`MovingMean(x, w, *, ahead=0, center=False)`, curried `x | MovingMean(w, ...)`: `MovingSum` divided by the number of
 frames of the window that lie inside the signal (one IEEE division by that count as a Float64), so an edge frame is the
@@ -2064,7 +2129,7 @@ def MovingQuantile(*args, ahead=None, center=False):
     bit where `x` does.  The dependence is local: a window or a `stream` block computes its own frames from its own range
     of `x` plus `back` frames before and `ahead` after, and an `x` of infinite length is accepted.  One form is built, a
     window of at most 1025 frames (counted after `back` and `ahead` are clipped to the length of `x`): a longer one is
-    refused here and by the planner, never computed on the host.  `BlockStream` and multi-GPU shards refuse the node."""
+    refused here and by the planner, never computed on the host.  A `BlockStream` streams the node like `MovingMax`, bit for bit; multi-GPU shards refuse it."""
     what = "MovingQuantile"
     if len(args) == 2:
         w, q = args
